@@ -11,7 +11,14 @@ Weak scaling: every rank owns 1024 slots; value = env-steps of all ranks / max-o
 with RANK / LOCAL_RANK / WORLD_SIZE / MASTER_ADDR / MASTER_PORT set, backend nccl (= RCCL) -- as the reference starts
 all of its parallelism from one command (agents/agent.py:93-108). Under torchrun it is one of the ranks.
 
-Prints ONE JSON line (rank 0) with the driver's fields plus
+A plain run does only what the headline needs: set-up, `--warmup` untimed iterations, `--steps` timed ones, the JSON line
+(rank 0) with the driver's fields, the per-iteration T_sample / T_update split and the host it ran on in `config`.
+`--dump-outputs DIR` then writes what the last timed iteration handed its caller (the nets' parameters after the update,
+the observation filter's statistics, the sampling pass's statistics) as DIR/<name>.npy; the inputs are seeded, so two
+builds run with the same arguments can be compared output for output.
+
+`--full` adds everything else this file measures (each part can still be switched off with its `--no-*` option):
+  probe        egp_host_probe right before and after the timed region (`config.probe_*`)
   roofline     K1 (stable-PD torque, the dominant kernel): algorithmic bytes of the env-substeps the timed launches
                actually STEPPED (finished slots of the rollout's tail move nothing) / their duration, measured with HIP
                events on the launch streams inside the timed region, against 8 TB/s HBM; `frac_slot_based` is the same
@@ -295,6 +302,42 @@ def k1_roofline(tim, envs_per_group, eng, every, probe=None):
                     "HBM-resident rates of the same arithmetic"}
 
 
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def dump_outputs(out_dir, tr, log):
+    """`--dump-outputs`: what one PPO iteration hands its caller -- the nets after the update (every state_dict entry), the
+    observation filter (`running_state`: n, mean, sum of squares, as it moves to the device) and the sampling pass's
+    statistics (`log.<attribute>`) -- as float32 / float64 .npy files. Past DUMP_LIMIT_BYTES every array keeps a fixed,
+    seeded sample of its elements in proportion."""
+    import numpy as np
+    import torch
+    from egopose_amd.rl_core import LoggerRL
+    arrays = {}
+    for net_name, net in tr.nets.items():
+        for k, v in net.state_dict().items():
+            v = v.detach().cpu()
+            arrays["%s.%s" % (net_name, k)] = v.numpy().astype(np.float32 if v.dtype in (torch.float32, torch.float16, torch.bfloat16)
+                                                                 else np.float64)
+    arrays["running_state"] = np.asarray(torch.as_tensor(tr.running_state.to_device_state("cpu")), dtype=np.float64)
+    for name in LoggerRL._SUMS + tuple(e[0] for e in LoggerRL._EXTREMA) + tuple(a[0] for a in LoggerRL._AVERAGES):
+        arrays["log." + name] = np.asarray(getattr(log, name), dtype=np.float64).reshape(-1)
+    total = sum(a.nbytes for a in arrays.values())
+    if total > DUMP_LIMIT_BYTES:
+        rng = np.random.default_rng(0)
+        first = sum(a.itemsize for a in arrays.values())           # one element of every array is always kept ...
+        budget, rest = DUMP_LIMIT_BYTES - first, total - first     # ... and the rest of the budget is shared in proportion
+        for name in sorted(arrays):
+            a = arrays[name].reshape(-1)
+            keep = 1 + (a.size - 1) * budget // rest
+            if keep < a.size:       # (Generator.choice without replacement does not permute the whole array)
+                arrays[name] = a[np.sort(rng.choice(a.size, keep, replace=False))]
+    os.makedirs(out_dir, exist_ok=True)
+    for name, a in arrays.items():
+        np.save(os.path.join(out_dir, name + ".npy"), a)
+    return len(arrays), sum(a.nbytes for a in arrays.values())
+
+
 def run_leg(make_trainer, steps, warmup, min_batch, every, env=None, default_dtype=None):
     """A short extra measurement of the same workload under another configuration (module docstring: `legs`)."""
     import torch
@@ -377,7 +420,16 @@ def main():
     ap.add_argument("--leg-steps", type=int, default=3, help="timed iterations of every extra leg (after --leg-warmup untimed ones)")
     ap.add_argument("--leg-warmup", type=int, default=3)
     ap.add_argument("--dry-run", action="store_true", help="launcher / rendezvous self-test: no GPU work (gloo on CPU)")
+    ap.add_argument("--full", action="store_true",
+                    help="also run the host probe, K1 events (roofline), kernel microbenchmarks, legs and CPU baselines")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed iteration computed as DIR/<name>.npy (float32 / float64, at most 64 MB)")
     args = ap.parse_args()
+    if not args.full:               # a plain run measures the headline only
+        args.no_k1_events = args.no_host_probe = args.no_kernels = args.no_legs = args.no_cpu_baseline = True
+    dump_dir = os.path.abspath(args.dump_outputs) if args.dump_outputs else None     # (before the chdir into the dataset)
+    if dump_dir is not None and args.steps < 1 and not args.dry_run:
+        raise SystemExit("--dump-outputs needs at least one timed step")
 
     env_world = os.environ.get("WORLD_SIZE")
     if args.gpus < 1:
@@ -515,6 +567,9 @@ def main():
                                   "per_iteration": "sampling pass: 1 all-gather (LoggerRL totals + observation-filter deltas, merged on the "
                                                    "device); update: 1 MAX (padded window length) + 1 all-gather (advantage moments + sample "
                                                    "counts, 5 x float64, Chan-merged on the device) + %d gradient all-reduces" % cfg.num_optim_epoch}
+        if dump_dir is not None:
+            n_arrays, n_bytes = dump_outputs(dump_dir, tr, log)
+            res["dump_outputs"] = {"dir": dump_dir, "arrays": n_arrays, "bytes": n_bytes}
     tr.close()
     if world > 1:
         torch.distributed.barrier()

@@ -78,7 +78,8 @@ struct LstmGroup {
     long c_stride;          // floats between the cells_save slabs of consecutive problems
     float *h[4];            // forward: h_out per problem (row (t, b) at h[p] + (t*B + b) * ld_h)
     const float *dh[4];     // backward: d h_out per problem
-    float *db;              // backward, optional: [P][4H] accumulates sum_t,b d_pre (atomics; zeroed by the caller)
+    float *db;              // backward, optional: [P][4H] accumulates sum_t,b d_pre (atomics; zeroed by the caller), or with
+    int db_rows;            // db_rows: [P][B][4H], row b = sum_t d_pre of row b, stored (the caller sums over b in a fixed order)
     // optional (egp_lstm_group_*_len_f32): ragged batches. order[p] = sequence (column b of the [T][B] layout) at position p,
     // workgroups take ROWS consecutive positions; steps[p] = time steps the sequence at position p needs FROM THE START
     // (its outputs at t >= steps[p] are never read). A problem that runs forward in time stops at the longest of its rows
@@ -426,7 +427,7 @@ __global__ __launch_bounds__(4 * LH) void k_lstm_bwd_mfma(const float *__restric
     for (int d = 0; d < PD - 1; ++d)      // T % PD last steps, staged in p*[0..]
         if (s0 - d >= 0) do_step(s0 - d, pg[d], pc[d], pdh[d], pc[d + 1]);
 #undef EGP_LSTM_FETCH
-    if (grp.db) {                         // db[4*unit + gate] += sum over this workgroup's rows (s_d is free again)
+    if (grp.db) {                         // the rows' sums over their steps, [row][4*unit + gate] in s_d (free again)
         __syncthreads();
 #pragma unroll
         for (int qq = 0; qq < NP; ++qq) {
@@ -434,11 +435,18 @@ __global__ __launch_bounds__(4 * LH) void k_lstm_bwd_mfma(const float *__restric
             *reinterpret_cast<f32x4 *>(&s_d[p / LH][4 * (p % LH)]) = dsum[qq];
         }
         __syncthreads();
-        for (int c = threadIdx.x; c < LG; c += NT) {
-            float a = 0.f;
+        if (grp.db_rows) {                // db[prob][row][c] = the row's sum, stored: no float atomics, the same bits every run
+            for (int p = threadIdx.x; p < ROWS * LG; p += NT) {
+                const int r = p / LG, c = p % LG;
+                if (FULL || r0 + r < B) grp.db[((long)prob * B + r0 + r) * LG + c] = s_d[r][c];
+            }
+        } else {                          // db[prob][c] += sum over this workgroup's rows
+            for (int c = threadIdx.x; c < LG; c += NT) {
+                float a = 0.f;
 #pragma unroll
-            for (int r = 0; r < ROWS; ++r) a += s_d[r][c];
-            atomicAdd(grp.db + prob * LG + c, a);
+                for (int r = 0; r < ROWS; ++r) a += s_d[r][c];
+                atomicAdd(grp.db + prob * LG + c, a);
+            }
         }
     }
 }
@@ -492,6 +500,27 @@ static void launch_bwd_mfma(int hidden, int P, const float *gates_save, const fl
     if (hidden == 128) launch_bwd_mfma_t<1, 128>(full, P, gates_save, cells_save, w_hh, T, B, g, d_pre, s);
     else if (nq >= 2) launch_bwd_mfma_t<2, 64>(full, P, gates_save, cells_save, w_hh, T, B, g, d_pre, s);
     else launch_bwd_mfma_t<1, 64>(full, P, gates_save, cells_save, w_hh, T, B, g, d_pre, s);
+}
+
+// the grouped backward behind egp_lstm_group_bwd_len_f32 (d_bias: [P][4H], atomics) and egp_lstm_group_bwd_rows_f32 ([P][B][4H])
+static int lstm_group_bwd(const float *const *dh_out, int32_t ld_dh, const float *gates_save, const float *cells_save, const float *w_hh,
+                          int32_t T, int32_t B, int32_t hidden, int32_t n_problems, int32_t reverse_mask, float *d_pre, float *d_bias,
+                          int db_rows, const int32_t *seq_order, const int32_t *seq_steps, int32_t leave_skipped, void *stream) {
+    EGP_REQUIRE((seq_order == nullptr) == (seq_steps == nullptr), "seq_order and seq_steps go together");
+    EGP_REQUIRE(hidden == 64 || hidden == 128, "egp_lstm kernels are built for hidden size 64 and 128");
+    EGP_REQUIRE(n_problems >= 1 && n_problems <= 4, "1..4 problems per group");
+    EGP_REQUIRE(T >= 0 && B >= 0, "negative size");
+    if (T == 0 || B == 0) return EGP_OK;
+    EGP_REQUIRE(dh_out && gates_save && cells_save && w_hh && d_pre && ld_dh >= hidden, "NULL pointer / d h_out row stride below the hidden size");
+    LstmGroup g = {};
+    g.ld_g = 4 * hidden * n_problems; g.rev_mask = reverse_mask; g.ld_dh = ld_dh; g.c_stride = (long)T * B * hidden; g.db = d_bias; g.db_rows = db_rows;
+    for (int p = 0; p < n_problems; ++p) {
+        EGP_REQUIRE(dh_out[p], "NULL d h_out");
+        g.dh[p] = dh_out[p];
+    }
+    g.order = seq_order; g.steps = seq_steps; g.leave_skipped = seq_steps && leave_skipped;
+    launch_bwd_mfma(hidden, n_problems, gates_save, cells_save, w_hh, T, B, g, d_pre, (hipStream_t)stream);
+    return lstm_launch_check("k_lstm_bwd_mfma (group)");
 }
 
 extern "C" {
@@ -564,21 +593,20 @@ int egp_lstm_group_bwd_f32(const float *const *dh_out, int32_t ld_dh, const floa
 int egp_lstm_group_bwd_len_f32(const float *const *dh_out, int32_t ld_dh, const float *gates_save, const float *cells_save, const float *w_hh,
                                int32_t T, int32_t B, int32_t hidden, int32_t n_problems, int32_t reverse_mask, float *d_pre, float *d_bias,
                                const int32_t *seq_order, const int32_t *seq_steps, int32_t leave_skipped, void *stream) {
-    EGP_REQUIRE((seq_order == nullptr) == (seq_steps == nullptr), "seq_order and seq_steps go together");
-    EGP_REQUIRE(hidden == 64 || hidden == 128, "egp_lstm kernels are built for hidden size 64 and 128");
-    EGP_REQUIRE(n_problems >= 1 && n_problems <= 4, "1..4 problems per group");
-    EGP_REQUIRE(T >= 0 && B >= 0, "negative size");
-    if (T == 0 || B == 0) return EGP_OK;
-    EGP_REQUIRE(dh_out && gates_save && cells_save && w_hh && d_pre && ld_dh >= hidden, "NULL pointer / d h_out row stride below the hidden size");
-    LstmGroup g = {};
-    g.ld_g = 4 * hidden * n_problems; g.rev_mask = reverse_mask; g.ld_dh = ld_dh; g.c_stride = (long)T * B * hidden; g.db = d_bias;
-    for (int p = 0; p < n_problems; ++p) {
-        EGP_REQUIRE(dh_out[p], "NULL d h_out");
-        g.dh[p] = dh_out[p];
+    return lstm_group_bwd(dh_out, ld_dh, gates_save, cells_save, w_hh, T, B, hidden, n_problems, reverse_mask, d_pre, d_bias, 0, seq_order,
+                          seq_steps, leave_skipped, stream);
+}
+
+int egp_lstm_group_bwd_rows_f32(const float *const *dh_out, int32_t ld_dh, const float *gates_save, const float *cells_save, const float *w_hh,
+                                int32_t T, int32_t B, int32_t hidden, int32_t n_problems, int32_t reverse_mask, float *d_pre, float *d_bias_rows,
+                                const int32_t *seq_order, const int32_t *seq_steps, int32_t leave_skipped, void *stream) {
+    EGP_REQUIRE(d_bias_rows, "NULL d_bias_rows");
+    if (T == 0 && B > 0 && n_problems >= 1 && n_problems <= 4) {     // nothing to sweep: every row's sum is zero
+        EGP_HIP_CHECK(hipMemsetAsync(d_bias_rows, 0, sizeof(float) * (size_t)n_problems * B * 4 * hidden, (hipStream_t)stream));
+        return EGP_OK;
     }
-    g.order = seq_order; g.steps = seq_steps; g.leave_skipped = seq_steps && leave_skipped;
-    launch_bwd_mfma(hidden, n_problems, gates_save, cells_save, w_hh, T, B, g, d_pre, (hipStream_t)stream);
-    return lstm_launch_check("k_lstm_bwd_mfma (group)");
+    return lstm_group_bwd(dh_out, ld_dh, gates_save, cells_save, w_hh, T, B, hidden, n_problems, reverse_mask, d_pre, d_bias_rows, 1, seq_order,
+                          seq_steps, leave_skipped, stream);
 }
 
 }  // extern "C"

@@ -218,11 +218,12 @@ class LstmGroup(torch.autograd.Function):
         esz = h_buf.element_size()
         ptrs = (C.c_void_p * P)(*[douts[p // width].data_ptr() + esz * (p % width) * H for p in pord])
         dpre = torch.empty(T * B, P * 4 * H, dtype=x2.dtype, device=x2.device)
-        db = torch.zeros(P, 4 * H, dtype=x2.dtype, device=x2.device)
+        db_rows = torch.empty(P, B, 4 * H, dtype=x2.dtype, device=x2.device)      # every row written: sums over t, reduced below in a fixed order
         order, steps = (ragged.order, ragged.steps) if ragged is not None else (None, None)
         leave = int(bool(ctx.leave) and not ctx.needs_input_grad[0])     # (d_x = d_pre W_in reads every row)
-        L.check(lib.egp_lstm_group_bwd_len_f32(ptrs, W, _p(gates), _p(cells), _p(w_hh_all), T, B, H, P, kmask, _p(dpre), _p(db),
-                                               _p(order), _p(steps), leave, _s()), "egp_lstm_group_bwd_len_f32")
+        L.check(lib.egp_lstm_group_bwd_rows_f32(ptrs, W, _p(gates), _p(cells), _p(w_hh_all), T, B, H, P, kmask, _p(dpre), _p(db_rows),
+                                                _p(order), _p(steps), leave, _s()), "egp_lstm_group_bwd_rows_f32")
+        db = db_rows.sum(1)
         d3 = dpre.view(T, B, P * 4 * H)
         use_g = G.enabled()
         nfc = nf * 4 * H

@@ -418,6 +418,12 @@ int egp_lstm_group_fwd_len_f32(const float *gates_x, const float *w_hh, int32_t 
 int egp_lstm_group_bwd_len_f32(const float *const *dh_out, int32_t ld_dh, const float *gates_save, const float *cells_save, const float *w_hh,
                                int32_t T, int32_t B, int32_t hidden, int32_t n_problems, int32_t reverse_mask, float *d_pre, float *d_bias,
                                const int32_t *seq_order, const int32_t *seq_steps, int32_t leave_skipped, void *stream);
+/* egp_lstm_group_bwd_len_f32 with the bias gradient left per row: d_bias_rows [n_problems][B][4H] (required, every element is
+ * written, no zeroing needed) receives, for each row b, the sum over t of d_pre. The caller sums over b in an order of its
+ * choosing; no float atomics, so the same inputs give the same bits on every run. */
+int egp_lstm_group_bwd_rows_f32(const float *const *dh_out, int32_t ld_dh, const float *gates_save, const float *cells_save, const float *w_hh,
+                                int32_t T, int32_t B, int32_t hidden, int32_t n_problems, int32_t reverse_mask, float *d_pre, float *d_bias_rows,
+                                const int32_t *seq_order, const int32_t *seq_steps, int32_t leave_skipped, void *stream);
 
 /* ----------------------------------------------------------------------------------------
  * K8: dynamics terms on the GPU. From (qpos, qvel) per env: body frame positions (mjData.xpos[1:]),

@@ -25,11 +25,19 @@ def test_shipped_picks_file_is_well_formed():
 
 
 def test_bucket_rows_is_a_no_op_when_disabled_or_on_cpu():
-    assert not gemm_tuning.enabled()
-    x = torch.randn(5 * gemm_tuning.ROW_BUCKET + 3, 4)
-    y, n = bucket_rows(x)
-    assert y is x and n is None
-    assert gemm_tuning.pad_to(8192, 8192) == 0 and gemm_tuning.pad_to(8193, 8192) == 8191
+    # a Trainer on the GPU switches the tuning on for its whole process: an earlier test of the same run may have built one
+    was_on = gemm_tuning.enabled() and torch.cuda.is_available()
+    if was_on:
+        gemm_tuning.disable()
+    try:
+        assert not gemm_tuning.enabled()
+        x = torch.randn(5 * gemm_tuning.ROW_BUCKET + 3, 4)
+        y, n = bucket_rows(x)
+        assert y is x and n is None
+        assert gemm_tuning.pad_to(8192, 8192) == 0 and gemm_tuning.pad_to(8193, 8192) == 8191
+    finally:
+        if was_on:
+            gemm_tuning.enable()
 
 
 @pytest.fixture

@@ -13,6 +13,7 @@ import torch
 import yaml
 
 from conftest import REPO, load_golden
+from oracle.ref_build import compiled_driver
 
 
 def _workspace(tmp_path, skel, n_takes=2, n_frames=90):
@@ -83,19 +84,20 @@ def test_config_matches_reference_parse(tmp_path, skel, monkeypatch):
         Config("does_not_exist")
 
 
-REF_DRIVER = "/root/reference/ego_pose/ego_mimic.py"
+REF_DRIVER = compiled_driver("ego_mimic")
+NO_REF = "build() compiles the reference's drivers into oracle/_ref/ only where a reference checkout is found (oracle/ref_build.py)"
 
 
 def _driver_env():
     return dict(os.environ, PYTHONPATH=REPO + os.pathsep + os.path.join(REPO, "egopose_amd", "compat"), HIP_VISIBLE_DEVICES="")
 
 
-@pytest.mark.skipif(not os.path.exists(REF_DRIVER), reason="the reference tree only exists in the build container")
+@pytest.mark.skipif(not os.path.exists(REF_DRIVER), reason=NO_REF)
 def test_unmodified_reference_driver_runs_on_the_compat_packages(tmp_path, skel):
-    """Row (b): `python <reference>/ego_pose/ego_mimic.py --cfg subject_03` executed AS IS (the file under /root/reference,
-    not a restatement) with egopose_amd/compat on PYTHONPATH and a config whose max_iter_num is 0: the whole module-level
-    set-up (imports, Config, env + experts, nets, optimizers, AgentEgo(dtype=float64, ...)) and an empty main_loop run
-    through this package's classes. No MI355X in the build container, so the driver picks its CPU device and nothing
+    """Row (b): `python <reference>/ego_pose/ego_mimic.py --cfg subject_03` executed AS IS (the reference's file as build()
+    byte-compiled it into oracle/_ref/, not a restatement) with egopose_amd/compat on PYTHONPATH and a config whose
+    max_iter_num is 0: the whole module-level set-up (imports, Config, env + experts, nets, optimizers,
+    AgentEgo(dtype=float64, ...)) and an empty main_loop run through this package's classes. No MI355X in the build container, so the driver picks its CPU device and nothing
     is sampled; the iterations themselves are covered on the GPU by tests/test_dropin_gpu.py."""
     root = _workspace(tmp_path, skel)
     cfg_path = os.path.join(root, "config", "egomimic", "subject_03.yml")
@@ -119,10 +121,10 @@ def test_unmodified_reference_driver_runs_on_the_compat_packages(tmp_path, skel)
     assert len(origins) == 9 and all(o.startswith(os.path.join(REPO, "egopose_amd", "compat")) for o in origins), origins
 
 
-REF_FORECAST_DRIVER = "/root/reference/ego_pose/ego_forecast.py"
+REF_FORECAST_DRIVER = compiled_driver("ego_forecast")
 
 
-@pytest.mark.skipif(not os.path.exists(REF_FORECAST_DRIVER), reason="the reference tree only exists in the build container")
+@pytest.mark.skipif(not os.path.exists(REF_FORECAST_DRIVER), reason=NO_REF)
 def test_unmodified_forecast_driver_runs_on_the_compat_packages(tmp_path, skel, monkeypatch):
     """Row f2 through row (b): `python <reference>/ego_pose/ego_forecast.py --cfg subject_03` executed AS IS on egopose_amd/compat
     with max_iter_num 0 -- its imports (models.video_forecast_net, ego_pose.utils.egoforecast_config + egomimic_config), the warm

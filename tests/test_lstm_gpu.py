@@ -153,6 +153,32 @@ def test_grouped_sweeps_match_separate_ones(T, B, D, H):
 
 
 @pytest.mark.gpu
+@pytest.mark.parametrize("B,H", [(1280, 64), (37, 128)])
+def test_grouped_backward_is_bit_reproducible(B, H):
+    """The same grouped sweep differentiated twice gives the same bits in every gradient: the bias gradient is summed in a
+    fixed order (per-row sums from the kernel, then one reduction), not with float atomics across workgroups."""
+    from egopose_amd import lstm as hl
+    dev = torch.device("cuda", 0)
+    torch.manual_seed(5)
+    T, D = 60, 24
+    cells = [torch.nn.LSTMCell(D, H).to(dev) for _ in range(4)]
+    x = torch.randn(T, B, D, device=dev)
+    ws = [torch.randn(T, B, H, device=dev) for _ in range(4)]
+
+    def grads():
+        for c in cells:
+            c.zero_grad()
+        hs = hl.lstm_group(x, cells, [False, True, False, True])
+        sum((h * w).sum() for h, w in zip(hs, ws)).backward()
+        return [p.grad.clone() for c in cells for p in c.parameters()]
+
+    first = grads()
+    for _ in range(3):
+        for a, b in zip(first, grads()):
+            assert torch.equal(a, b)
+
+
+@pytest.mark.gpu
 def test_grouped_video_contexts_match_per_net_contexts():
     """nets.grouped_video_context for (value_vs_net, policy_vs_net) == each net computing its own context."""
     import numpy as np

@@ -1,6 +1,6 @@
 #!/bin/bash
 # Round profile set (run on the GPU box through gpurun): writes gpurun_out/profiles_round/
-#   bench_kernel_stats.csv      rocprofv3 --kernel-trace --stats over the default `python bench.py`
+#   bench_kernel_stats.csv      rocprofv3 --kernel-trace --stats over `python bench.py --full`
 #   bench_line_under_rocprof.json   the JSON line that run printed
 #   pmc_bench_fetch_write.csv   FETCH_SIZE / WRITE_SIZE per egp kernel (separate --pmc passes, kernel-trace only)
 #   pmc_k1_traffic.json         HBM bytes per env-substep of the dominant kernel from those passes
@@ -10,12 +10,12 @@ OUT=$GRAFT_REPO_ROOT/gpurun_out/profiles_round
 rm -rf $OUT; mkdir -p $OUT
 # (headline only: the extra legs / microbenchmarks of the default run launch the same kernels under other conditions
 #  and would blur the per-kernel averages the bench line's roofline is checked against)
-rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/raw -o b -- python bench.py --no-legs --no-kernels > $OUT/bench.log 2>&1
+rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/raw -o b -- python bench.py --full --no-legs --no-kernels > $OUT/bench.log 2>&1
 grep '^{' $OUT/bench.log | tail -1 > $OUT/bench_line_under_rocprof.json
 cp "$(find $OUT/raw -name '*kernel_stats.csv' | head -1)" $OUT/bench_kernel_stats.csv
 rm -rf $OUT/raw
 for c in FETCH_SIZE WRITE_SIZE; do
-  timeout 900 rocprofv3 --pmc $c --kernel-trace --output-format csv -d $OUT/$c -o b -- python bench.py --steps 1 --warmup 0 --no-cpu-baseline --no-k1-events --no-legs --no-kernels > $OUT/$c.log 2>&1
+  timeout 900 rocprofv3 --pmc $c --kernel-trace --output-format csv -d $OUT/$c -o b -- python bench.py --full --steps 1 --warmup 0 --no-cpu-baseline --no-k1-events --no-legs --no-kernels > $OUT/$c.log 2>&1
 done
 python - <<PY
 import csv, glob, collections, json
@@ -61,7 +61,7 @@ print("\n".join(rows))
 PY
 # matrix-core utilisation of the update's kernels (own PMC pass, kernel-trace only): the split-operand GEMM, the persistent
 # LSTM recurrences and whatever library GEMM is left
-timeout 900 rocprofv3 --pmc MfmaUtil VALUBusy --kernel-trace --output-format csv -d $OUT/mfma -o b -- python bench.py --steps 1 --warmup 0 --no-cpu-baseline --no-k1-events --no-legs --no-kernels > $OUT/mfma.log 2>&1
+timeout 900 rocprofv3 --pmc MfmaUtil VALUBusy --kernel-trace --output-format csv -d $OUT/mfma -o b -- python bench.py --full --steps 1 --warmup 0 --no-cpu-baseline --no-k1-events --no-legs --no-kernels > $OUT/mfma.log 2>&1
 python - <<PY
 import csv, glob, collections
 OUT = "$OUT"
