@@ -164,8 +164,9 @@ class LstmGroup(torch.autograd.Function):
         w_in = torch.cat([w_ih[p] for p in pord], 0).index_select(0, bperm)                 # (P*4H, D)
         bias = (torch.cat([b_ih[p] for p in pord]) + torch.cat([b_hh[p] for p in pord])).index_select(0, bperm)
         rows = None
+        # (the row-list projection is one k range of D columns: the persistent kernel needs at least one 32-column k-tile)
         if ragged is not None and ragged.rows is not None and 0 < nf and G.enabled() and G.fused_rows_available() \
-                and ragged.T == T and ragged.rows.shape[0] >= 4096:
+                and ragged.T == T and ragged.rows.shape[0] >= 4096 and D >= 32:
             rows = ragged.rows
         seq_base, gates_buf = None, None
         if frames is not None and G.enabled():
