@@ -188,6 +188,7 @@ struct Group {
     bool polled = false;                      // the launch in flight publishes to h_flag
     bool prof_now = false;                    // this env-step brackets its K1 launches with events
     bool server_job = false;                  // form of the env-step in flight (fixed when it is posted)
+    bool server_form = false;                 // form of the group's first env-step: every later one must take the same
     char err[256] = "";
     // timing (leader only)
     double phys_s = 0.0, wait_s = 0.0, k1_ms = 0.0, ev_overhead_ms = 0.0;
@@ -782,8 +783,10 @@ int egp_engine_create(egp_ctx *ctx, egp_physics *phys, const egp_engine_desc *d,
         // ends (2 x 256 one-env workgroups on 256 CUs went as far as the kernel-side timeout in round 4). One 350-register workgroup
         // fits a CU: 4 envs per CU with one env per wave (1 024 slots on 256 CUs). Beyond that -- more slots, or fewer CUs to be had
         // (a CU mask, a co-tenant, a smaller part) -- a wave serves 2 or 4 envs in turn (k_pd_server_tree58_multi): the smallest
-        // count whose grid the chip holds, by the kernel's own residency probe. Device dynamics (110 kB of LDS per workgroup) has the
-        // one-env form only. EGP_SERVER_KE forces a count (tests), EGP_SERVER=0 the per-substep form.
+        // count whose grid the chip holds, by the kernel's own residency probe. Device dynamics has the one-env form (~104 kB of LDS
+        // per workgroup) and the two-env form (k_pd_server_tree58_multi_dyn<2>, ~135 kB); four envs' float64 factor rows next to the
+        // K8 scratch would need ~196 kB of the 160 KiB, so beyond 8 envs per CU it keeps the per-substep form.
+        // EGP_SERVER_KE forces a count (tests; a count without a kernel ends in the per-substep form), EGP_SERVER=0 the per-substep form.
         const char *sv = getenv("EGP_SERVER");
         const char *fk = getenv("EGP_SERVER_KE");
         const bool usable = ctx->tree58 && ctx->pd_variant == 0 && !(sv && atoi(sv) == 0);
@@ -793,7 +796,7 @@ int egp_engine_create(egp_ctx *ctx, egp_physics *phys, const egp_engine_desc *d,
             const int ke = choices[c];
             if (fk && atoi(fk) != ke) continue;
             E->server_ke_forced = fk != nullptr;
-            if (E->device_dynamics && ke != 1) continue;
+            if (!egp_pd_server_has_kernel(E->device_dynamics, ke)) continue;
             long blocks = 0;
             for (int g = 0; g < E->n_groups; ++g) {
                 const long m = (long)E->n_env * (g + 1) / E->n_groups - (long)E->n_env * g / E->n_groups;
@@ -1033,6 +1036,11 @@ int egp_engine_step_async(egp_engine *E, int32_t group, const double *action, co
     G.has_active = active_host != nullptr;
     if (active_host) memcpy(G.active, active_host, E->n_env * sizeof(int));
     G.server_job = server_mode(E, G);
+    // the resident form reads and writes generation 0 of the device-dynamics rows (d_qM / d_bias) and never toggles dyn_gen; the
+    // per-substep form alternates the two. One engine must not mix them: server_mode is fixed for its lifetime
+    EGP_REQUIRE(!E->device_dynamics || G.job == 0 || G.server_job == G.server_form,
+                "device dynamics: the form of the env-step (resident / per substep) changed during the engine's lifetime");
+    G.server_form = G.server_job;
     if (G.server_job) {
         assign_slices(G.srv, G.n_threads, G.has_active ? G.active : nullptr);
         G.srv.base = G.srv.seq;

@@ -87,6 +87,8 @@ int egp_launch_pd_server(egp_ctx *ctx, const double *qpos, long ld_qpos, const d
                          double *out_qpos, double *out_prev_qpos, double *out_qvel, double *out_ee, const int *active, bool device_dynamics,
                          int envs_per_wave = 1, const int *block_env0 = nullptr, int n_blocks = 0);
 size_t egp_pd_server_dyn_lds_bytes();
+size_t egp_pd_server_multi_dyn_lds_bytes(int envs_per_wave);
+bool egp_pd_server_has_kernel(bool device_dynamics, int envs_per_wave);
 int egp_pd_server_resident_blocks(int device, bool device_dynamics, int envs_per_wave = 1);
 int egp_launch_dynamics_strided(egp_ctx *ctx, const double *qpos, long ld_q, const double *qvel, long ld_v, int32_t n, double *qM,
                                 long ld_m, double *bias, long ld_b, double *xpos, hipStream_t stream, const int *list = nullptr,

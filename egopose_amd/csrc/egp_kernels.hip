@@ -965,6 +965,258 @@ __global__ __launch_bounds__(256) void k_pd_server_tree58_multi(DevModel m, PdLd
     }
 }
 
+// DYN form of the multi-env resident K1 (device_dynamics engines beyond one env per wave): K8 inside, as k_pd_server_tree58<true>
+// has it, for KE envs per wave served in turn, as k_pd_server_tree58_multi has them. A sibling kernel rather than a template
+// parameter of either: both keep the code they generate.
+// Per substep: both envs' qpos | qvel rows are requested first (their PCIe round trips overlap); then every env's solve with the
+// factors and the bias the PREVIOUS substep left behind (the reference's timing: see k_pd_server_tree58), its torque row stored;
+// and only when ALL torques of the wave are out, env by env, K8 on the row just read + the in-place factorisation for the next
+// substep -- the slice's physics thread waits for every torque of its slice, so ~22 us of K8 + factors per env sit behind the host's
+// physics step, never in front of a torque.
+// LDS (dynamic): the tree tables once per workgroup | one K8 scratch area per WAVE, which its envs share in time (it is dead once
+// qM and the bias are written) | the factor rows [4][KE][PD_NM_MAX]: K8 writes the sparse inertia row straight into the env's row
+// (the padding behind nM, the zero slot included, is never written), the factorisation replaces it in place | per env one
+// qpos[64] | qvel[64] | bias[64] row: the state row just read and the bias the env's previous substep left behind | the sweeps'
+// index tables, 2 x [PD_NV][64] shorts.
+// For KE = 2: 9.9 + 50.7 + 61.4 + 12.3 + 14.8 kB = ~149 kB of the 160 KiB a workgroup may declare; KE = 4 would need ~223 kB and
+// KE = 3 ~186 kB with float64 factors: not offered (pd_server_multi_dyn_lds_bytes).
+// The early request of the next state row under the factorisation (have_next of the one-env kernel) is left out: with two envs per
+// wave the second env's K8 already runs while the host steps, and a row requested before it would have to be held in registers
+// across a whole K8.
+template <int KE>
+__global__ __launch_bounds__(256) void k_pd_server_tree58_multi_dyn(DevModel m, PdLd ld, const double *qpos, const double *qvel,
+                                                                    const double *__restrict__ action, const double *qM, const double *C,
+                                                                    int n, double *torque, PdServe sv) {
+    extern __shared__ double s_dynmem[];
+    __shared__ unsigned long long s_go[2];
+    __shared__ int s_abort;
+    if (sv.probe) { server_residency_probe(sv); return; }
+    const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+    const long be0 = sv.block_env0[blockIdx.x], be1 = sv.block_env0[blockIdx.x + 1];
+    const long env0 = be0 + wave;                      // wave w takes be0 + w, be0 + w + 4, ... (see k_pd_server_tree58_multi)
+    const int row = lane < PD_NV ? lane : PD_NV - 1;
+    const int act = row >= 6 ? row - 6 : 0;
+    const int slice = sv.block_slice[blockIdx.x];
+    bool live[KE];
+    unsigned live_mask = 0u;            // (the same as bits, for the loops over the envs that are kept rolled)
+#pragma unroll
+    for (int e = 0; e < KE; ++e) {
+        live[e] = env0 + 4 * e < be1 && env0 + 4 * e < n && (!sv.active || sv.active[env0 + 4 * e] != 0);
+        live_mask |= live[e] ? 1u << e : 0u;
+    }
+    if (__syncthreads_or(live_mask != 0u ? 1 : 0) == 0) return;
+    const double c_kp = row >= 6 ? m.jkp[act] : 0.0, c_kd = row >= 6 ? m.jkd[act] : 0.0;
+    const double c_ref = m.a_ref[act], c_scale = m.a_scale[act], c_lim = m.torque_lim[act];
+    const double kd_dt = c_kd * m.sub_dt;
+    double target[KE];
+#pragma unroll
+    for (int e = 0; e < KE; ++e) target[e] = c_ref + (live[e] ? action[(env0 + 4 * e) * ld.action + act] : 0.0) * c_scale;
+    constexpr int QM_IT = PD_NM_MAX / 64;
+    constexpr int TB_DOUBLES = (int)((sizeof(egp_dyn::DynTables) + 7) / 8);
+    egp_dyn::DynTables *tb = reinterpret_cast<egp_dyn::DynTables *>(s_dynmem);
+    double *s_scr = s_dynmem + TB_DOUBLES + wave * egp_dyn::DY_ENV_DOUBLES;                             // K8 scratch of this wave
+    double *s_fac = s_dynmem + TB_DOUBLES + 4 * egp_dyn::DY_ENV_DOUBLES;                                // [4 waves][KE][PD_NM_MAX]
+    double *s_q = s_fac + (size_t)4 * KE * PD_NM_MAX + (size_t)wave * KE * 192;                         // per env: qpos[64] | qvel[64] | bias[64]
+    // sparse index of entry (K, lane's row) for the sweep towards the root (K a descendant: s_up) and of (row, K) for the sweep back
+    // (K an ancestor: s_lo) -- the same for every env -- or, where the tree has no such entry, a slot of the row's padding that
+    // stays zero (nM = 910 of PD_NM_MAX = 960 doubles). [K][lane], in the dynamic LDS on purpose: k_pd_server_tree58_multi keeps them
+    // in registers, here the 116 addresses made from them would be carried across K8 and the elimination
+    constexpr int ZERO_SLOT = PD_NM_MAX - 1;
+    short *s_up = reinterpret_cast<short *>(s_fac + (size_t)4 * KE * (PD_NM_MAX + 192));
+    short *s_lo = s_up + PD_NV * 64;
+    for (int i = threadIdx.x; i < PD_NV * 64; i += 256) {
+        const int K = i >> 6, r = (i & 63) < PD_NV ? (i & 63) : PD_NV - 1;
+        const short id = m.m_map[r * PD_NV + K];
+        s_up[i] = (K > r && id >= 0) ? id : (short)ZERO_SLOT;
+        s_lo[i] = (K < r && id >= 0) ? id : (short)ZERO_SLOT;
+    }
+    {
+        const int words = sizeof(egp_dyn::DynTables) / 4;
+        const int *src = reinterpret_cast<const int *>(sv.dyn);
+        int *dst = reinterpret_cast<int *>(tb);
+        for (int i = threadIdx.x; i < words; i += 256) dst[i] = src[i];
+    }
+    // what the env's last mj_step (the previous launch) or the reset's forward left in HBM
+#pragma unroll
+    for (int e = 0; e < KE; ++e) {
+        double *F = s_fac + (size_t)(wave * KE + e) * PD_NM_MAX;
+        const double *src = qM + (env0 + 4 * e) * ld.qM;
+#pragma unroll
+        for (int k = 0; k < QM_IT; ++k) {
+            const int i = lane + 64 * k;
+            F[i] = (live[e] && i < m.nM) ? src[i] : 0.0;
+        }
+    }
+    if (threadIdx.x == 0) s_abort = 0;
+    const bool tracer = sv.trace && blockIdx.x == 0 && threadIdx.x == 0;
+    const int id_diag = m.m_map[row * PD_NV + row];
+    const short *up_l = s_up + lane, *lo_l = s_lo + lane;       // (entry K of the lane: a constant offset from these)
+    // the env's inertia row in F -> the factors of M + Kd dt in its place (k_pd_server_tree58_multi's layout)
+    auto factor_in_place = [&](double *F) {
+        double a[PD_NV];
+        double dinv = 0.0;
+#pragma unroll
+        for (int j = 0; j < PD_NV; ++j) {       // (the row of the symmetric matrix: entry ids are below the zero slot, so min() picks the one that exists)
+            const int up = up_l[j * 64], lo = lo_l[j * 64];
+            const int id = j == row ? id_diag : (up < lo ? up : lo);
+            a[j] = F[id] + (j == row ? kd_dt : 0.0);
+        }
+        tree_factor<PD_NV - 1>(a, dinv, row);
+        egp_dyn::wave_sync();           // every lane has its row: the inertia entries may go
+#pragma unroll
+        for (int K = 0; K < PD_NV; ++K) {
+            const int id = up_l[K * 64];
+            if (lane < PD_NV && id != ZERO_SLOT) F[id] = a[K];
+        }
+        if (lane < PD_NV) F[id_diag] = dinv;
+        egp_dyn::wave_sync();
+    };
+    __syncthreads();
+    // before the first go word: the bias the env's last mj_step left behind into its held row, the factors of its inertia row.
+    // (This loop and the K8 loop below stay rolled: one copy of K8 and of the elimination each, and no registers held across them.)
+#pragma unroll 1
+    for (int e = 0; e < KE; ++e) {
+        if ((live_mask >> e & 1u) == 0u || m.action_torque) continue;       // (wave-uniform)
+        if (lane < PD_NV) s_q[e * 192 + 128 + lane] = C[(env0 + 4 * e) * ld.bias + lane];
+        factor_in_place(s_fac + (size_t)(wave * KE + e) * PD_NM_MAX);       // (its wave_syncs order the held row too)
+    }
+    for (int sub = 0; sub < sv.n_sub; ++sub) {
+        if (threadIdx.x == 0) {
+            const unsigned long long want = sv.base + (unsigned long long)sub;
+            const long long t0 = wall_clock64();
+            unsigned long long v;
+            for (;;) {
+                v = scalar_poll_u64(sv.go + slice * 8);
+                if ((v >> 1) >= want) break;
+                for (int z = 0; z < sv.poll_sleep; ++z) __builtin_amdgcn_s_sleep(1);
+                if (wall_clock64() - t0 > sv.timeout_ticks) { s_abort = 1; break; }
+            }
+            s_go[sub & 1] = v;
+            if (tracer) { sv.trace[sub * 8 + 0] = t0; sv.trace[sub * 8 + 1] = wall_clock64(); }
+        }
+        __syncthreads();
+        if (s_abort) {
+            if (threadIdx.x == 0) __hip_atomic_store(sv.err, 1, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);
+            return;
+        }
+        if (m.action_torque) {                  // action_type 'torque' (humanoid_v1.py:170-172): the clipped control itself
+#pragma unroll
+            for (int e = 0; e < KE; ++e)
+                if (live[e] && lane < PD_NV && row >= 6)
+                    __hip_atomic_store(reinterpret_cast<unsigned long long *>(torque + (env0 + 4 * e) * m.nu + act),
+                                       (unsigned long long)__double_as_longlong(fmin(fmax(target[e], -c_lim), c_lim)), __ATOMIC_RELAXED,
+                                       __HIP_MEMORY_SCOPE_SYSTEM);
+            continue;
+        }
+        // every live env's qpos | qvel row first, lane = index (the bias is not in the host row), into the env's LDS row
+        {
+            double rq[KE], rv[KE];
+#pragma unroll
+            for (int e = 0; e < KE; ++e) {
+                rq[e] = rv[e] = 0.0;
+                if (!live[e]) continue;
+                const long env = env0 + 4 * e;
+                if (lane < sv.nq) rq[e] = sys_load_f64(qpos + env * ld.qpos + lane);
+                if (lane < sv.nv) rv[e] = sys_load_f64(qvel + env * ld.qvel + lane);
+            }
+#pragma unroll
+            for (int e = 0; e < KE; ++e) {
+                s_q[e * 192 + lane] = rq[e];
+                s_q[e * 192 + 64 + lane] = rv[e];
+            }
+            egp_dyn::wave_sync();
+        }
+        // the torques of all envs of the wave ...
+#pragma unroll
+        for (int e = 0; e < KE; ++e) {
+            if (!live[e]) continue;             // (wave-uniform)
+            const long env = env0 + 4 * e;
+            const double *F = s_fac + (size_t)(wave * KE + e) * PD_NM_MAX;
+            const double r_q = s_q[e * 192 + 7 + act], r_v = s_q[e * 192 + 64 + row], r_c = s_q[e * 192 + 128 + row];
+            const double eq = row >= 6 ? r_q - target[e] : 0.0;
+            double b = -r_c - c_kp * eq - c_kd * r_v;
+            if (tracer && e == 0) sv.trace[sub * 8 + 2] = b != 12345.678 ? wall_clock64() : 0;     // (stamps of block 0: its first env, then its last)
+            double cf[PD_NV];                   // the two sweeps of k_pd_server_tree58_multi
+#pragma unroll
+            for (int K = 0; K < PD_NV; ++K) cf[K] = F[up_l[K * 64]];
+            const double d_own = F[id_diag];
+#pragma unroll
+            for (int K = PD_NV - 1; K >= 0; --K) b = fma(-cf[K], readlane_f64(b, K), b);      // L^T y = b: leaves -> root
+            b *= d_own;
+#pragma unroll
+            for (int K = 0; K < PD_NV; ++K) cf[K] = F[lo_l[K * 64]];
+#pragma unroll
+            for (int J = 0; J < PD_NV; ++J) b = fma(-cf[J], readlane_f64(b, J), b);           // L x = z: root -> leaves
+            if (tracer && e == 0) sv.trace[sub * 8 + 3] = b != 12345.678 ? wall_clock64() : 0;
+            if (lane < PD_NV && row >= 6) {
+                const double ev = r_v + b * m.sub_dt;
+                const double tau = -c_kp * eq - c_kd * ev;
+                __hip_atomic_store(reinterpret_cast<unsigned long long *>(torque + env * m.nu + act),
+                                   (unsigned long long)__double_as_longlong(fmin(fmax(tau, -c_lim), c_lim)), __ATOMIC_RELAXED,
+                                   __HIP_MEMORY_SCOPE_SYSTEM);
+            }
+            if (tracer) sv.trace[sub * 8 + (e == 0 ? 4 : 5)] = wall_clock64();
+        }
+        // ... and then, while the host steps, what that mj_step leaves behind for the NEXT compute_torque of every env: M and C at
+        // the state just read, and the factors
+        egp_dyn::wave_sync();                   // (every lane has read its bias entries: K8 may replace them)
+#pragma unroll 1
+        for (int e = 0; e < KE; ++e) {
+            if ((live_mask >> e & 1u) == 0u) continue;
+            const long env = env0 + 4 * e;
+            double *F = s_fac + (size_t)(wave * KE + e) * PD_NM_MAX;
+            double *q = s_q + e * 192;
+            egp_dyn::dynamics_wave(*tb, s_scr, q, q + 64, lane, true, F, q + 128, nullptr);
+            egp_dyn::wave_sync();
+            if (sub == sv.n_sub - 1) {          // across launches: the INERTIA row, before the factors take its place
+                double *dst = sv.qM_dev + env * ld.qM;
+#pragma unroll
+                for (int k = 0; k < QM_IT; ++k) {
+                    const int i = lane + 64 * k;
+                    if (i < m.nM) dst[i] = F[i];
+                }
+                if (lane < PD_NV) sv.bias_dev[env * ld.bias + lane] = q[128 + lane];
+            }
+            factor_in_place(F);
+        }
+        if (tracer) sv.trace[sub * 8 + 6] = wall_clock64();
+    }
+    // epilogue (see k_pd_server_tree58): the final state of the wave's envs to HBM once the slice's last step is drained
+    {
+        const int slot = sv.n_sub & 1;
+        if (threadIdx.x == 0) {
+            const unsigned long long want = sv.base + (unsigned long long)sv.n_sub;
+            const long long t0 = wall_clock64();
+            unsigned long long v;
+            for (;;) {
+                v = scalar_poll_u64(sv.go + slice * 8);
+                if ((v >> 1) >= want) break;
+                for (int z = 0; z < sv.poll_sleep; ++z) __builtin_amdgcn_s_sleep(1);
+                if (wall_clock64() - t0 > sv.timeout_ticks) { s_abort = 1; break; }
+            }
+            s_go[slot] = v;
+        }
+        __syncthreads();
+        if (s_abort) {
+            if (threadIdx.x == 0) __hip_atomic_store(sv.err, 1, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);
+            return;
+        }
+#pragma unroll
+        for (int e = 0; e < KE; ++e) {
+            if (!live[e]) continue;
+            const long env = env0 + 4 * e;
+            if (lane < sv.nq) {
+                const long d = env * sv.nq + lane;
+                const double q = sys_load_f64(qpos + env * ld.qpos + lane);
+                sv.out_prev_qpos[d] = sv.out_qpos[d];
+                sv.out_qpos[d] = q;
+            }
+            if (lane < sv.nv) sv.out_qvel[env * sv.nv + lane] = sys_load_f64(qvel + env * ld.qvel + lane);
+            if (lane < 15) sv.out_ee[env * 15 + lane] = sys_load_f64(sv.ee_host + env * 15 + lane);
+        }
+    }
+}
+
 // Generic path (any nv <= 64): one wavefront per env, system in LDS.
 template <typename TIO>
 __global__ __launch_bounds__(64) void k_pd_torque_lds(DevModel m, PdLd ld, const TIO *__restrict__ qpos,
@@ -2177,12 +2429,30 @@ size_t egp_pd_server_dyn_lds_bytes() {
     return ((sizeof(egp_dyn::DynTables) + 7) / 8 + 4 * (size_t)egp_dyn::DY_ENV_DOUBLES + 4 * 192) * sizeof(double);
 }
 
+// k_pd_server_tree58_multi_dyn<KE>: tables | K8 scratch per wave | factor rows per env | state + bias row per env | index tables
+constexpr size_t pd_server_multi_dyn_lds_bytes(int ke) {
+    return ((sizeof(egp_dyn::DynTables) + 7) / 8 + 4 * (size_t)egp_dyn::DY_ENV_DOUBLES + (size_t)4 * ke * (PD_NM_MAX + 192)) * sizeof(double) +
+           2 * PD_NV * 64 * sizeof(short);
+}
+// the static part: s_go, s_abort (rounded up). 160 KiB is what a gfx950 workgroup may declare; two envs per wave fit, three
+// (~186 kB) and four (~223 kB) do not with float64 factors
+constexpr size_t PD_SERVER_STATIC_LDS = 64;
+static_assert(pd_server_multi_dyn_lds_bytes(2) + PD_SERVER_STATIC_LDS <= 160 * 1024, "k_pd_server_tree58_multi_dyn<2> does not fit the LDS");
+static_assert(pd_server_multi_dyn_lds_bytes(3) + PD_SERVER_STATIC_LDS > 160 * 1024, "three envs per wave fit now: offer them");
+size_t egp_pd_server_multi_dyn_lds_bytes(int envs_per_wave) { return pd_server_multi_dyn_lds_bytes(envs_per_wave); }
+
 namespace {
 // the resident K1's variants: (device dynamics, envs per wavefront) -> kernel, dynamic LDS
 struct ServerKernel { const void *fn; size_t lds; };
 ServerKernel server_kernel(bool device_dynamics, int ke) {
     const size_t multi = (size_t)4 * ke * PD_NM_MAX * sizeof(double);
-    if (device_dynamics) return {ke == 1 ? reinterpret_cast<const void *>(&k_pd_server_tree58<true>) : nullptr, egp_pd_server_dyn_lds_bytes()};
+    if (device_dynamics) {
+        switch (ke) {
+            case 1: return {reinterpret_cast<const void *>(&k_pd_server_tree58<true>), egp_pd_server_dyn_lds_bytes()};
+            case 2: return {reinterpret_cast<const void *>(&k_pd_server_tree58_multi_dyn<2>), pd_server_multi_dyn_lds_bytes(2)};
+            default: return {nullptr, 0};          // more envs per wave do not fit the LDS (see pd_server_multi_dyn_lds_bytes)
+        }
+    }
     switch (ke) {
         case 1: return {reinterpret_cast<const void *>(&k_pd_server_tree58<false>), 0};
         case 2: return {reinterpret_cast<const void *>(&k_pd_server_tree58_multi<2>), multi};
@@ -2199,6 +2469,9 @@ int server_kernel_prepare(const ServerKernel &k) {
     return EGP_OK;
 }
 }  // namespace
+
+// whether the resident K1 exists in this variant at all (device dynamics: one or two envs per wave)
+bool egp_pd_server_has_kernel(bool device_dynamics, int envs_per_wave) { return server_kernel(device_dynamics, envs_per_wave).fn != nullptr; }
 
 // How many workgroups of the resident K1 (variant: device dynamics, `envs_per_wave`) the chip holds at once: the engine runs the
 // resident form only when every workgroup of every group is resident at the same time -- they wait on the host, and a workgroup
@@ -2285,7 +2558,9 @@ int egp_launch_pd_server(egp_ctx *ctx, const double *qpos, long ld_qpos, const d
                device_dynamics ? const_cast<double *>(bias) : nullptr, nullptr, block_env0, row_contig};
     EGP_REQUIRE(envs_per_wave == 1 || (block_env0 && n_blocks > 0), "the multi-env K1 needs the workgroups' env ranges");
     const dim3 grid(envs_per_wave == 1 ? (n + 3) / 4 : n_blocks);
-    if (device_dynamics) {
+    if (device_dynamics && envs_per_wave == 2) {
+        k_pd_server_tree58_multi_dyn<2><<<grid, dim3(256), k.lds, stream>>>(ctx->dm, ld, qpos, qvel, action, qM, bias, n, torque, sv);
+    } else if (device_dynamics) {
         k_pd_server_tree58<true><<<grid, dim3(256), k.lds, stream>>>(ctx->dm, ld, qpos, qvel, action, qM, bias, n, torque, sv);
     } else if (envs_per_wave == 1) {
         k_pd_server_tree58<false><<<grid, dim3(256), 0, stream>>>(ctx->dm, ld, qpos, qvel, action, qM, bias, n, torque, sv);

@@ -666,7 +666,8 @@ int egp_debug_burn(int64_t us, int32_t blocks, float *sink, void *stream);
  * trades go/done words with the physics threads through pinned memory; EGP_SERVER=0 turns it off), else 1 */
 int egp_engine_substeps_per_launch(egp_engine *e);
 /* the resident K1's shape: envs a wavefront serves in turn per substep (1: four envs per workgroup, one per wave; 2 / 4 when the
- * slots do not fit the chip that way -- more than 4 envs per CU, or fewer CUs to be had; EGP_SERVER_KE forces a count) and, in
+ * slots do not fit the chip that way -- more than 4 envs per CU, or fewer CUs to be had; EGP_SERVER_KE forces a count; device-dynamics
+ * engines have 1 and 2 only: four envs' float64 factor rows do not fit the LDS next to the K8 scratch, they step per substep then) and, in
  * `resident_capacity` (may be NULL), how many workgroups of that kernel the chip holds at once as the kernel's own residency probe
  * counted them at engine creation (the occupancy calculator's figure when EGP_SERVER_PROBE=0). The reference scales its sampler
  * by the number of worker processes (agents/agent.py:93-100); this is the engine's counterpart. 0 = per-substep form. */

@@ -13,6 +13,7 @@ def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--envs", type=int, default=1024)
     ap.add_argument("--groups", type=int, default=2)
+    ap.add_argument("--device-dynamics", action="store_true", help="inertia and bias force of every substep from K8 inside the resident K1")
     ap.add_argument("--step", action="store_true", help="also run two env-steps from a fixed state and print a checksum of the final qpos")
     a = ap.parse_args()
     import torch
@@ -24,8 +25,8 @@ def main():
     p = subject_03_params()
     ctx = EgpContext(sk, p["jkp"], p["jkd"], p["a_ref"], p["a_scale"], p["torque_lim"], p["b_diffw"], p["reward_weights"], device=0)
     ph = SurrogatePhysics(sk, a.envs)
-    eng = RolloutEngine(ctx, ph, a.envs, n_threads=4, n_groups=a.groups)
-    out = {"envs": a.envs, "cus_reported": torch.cuda.get_device_properties(0).multi_processor_count,
+    eng = RolloutEngine(ctx, ph, a.envs, n_threads=4, n_groups=a.groups, device_dynamics=a.device_dynamics)
+    out = {"envs": a.envs, "device_dynamics": bool(eng.device_dynamics), "cus_reported": torch.cuda.get_device_properties(0).multi_processor_count,
            "envs_per_wave": eng.envs_per_wave, "resident_capacity": eng.resident_capacity, "substeps_per_launch": eng.substeps_per_launch,
            "HSA_CU_MASK": os.environ.get("HSA_CU_MASK"), "ROC_GLOBAL_CU_MASK": os.environ.get("ROC_GLOBAL_CU_MASK")}
     if a.step:

@@ -25,7 +25,9 @@ def main():
     p = subject_03_params()
     ctx = EgpContext(sk, p["jkp"], p["jkd"], p["a_ref"], p["a_scale"], p["torque_lim"], p["b_diffw"], p["reward_weights"])
     ph = SurrogatePhysics(sk, n)
-    dyn = os.environ.get("EGP_DEVICE_DYNAMICS", "0") == "1"          # K8 inside the resident kernel (stamp 5: K8 + factors done)
+    # K8 inside the resident kernel: stamp 5 = K8 + factors done with one env per wave; with EGP_SERVER_KE=2 stamp 5 = the wave's last
+    # env stored (as without device dynamics) and stamp 6 = K8 + factors of all its envs done
+    dyn = os.environ.get("EGP_DEVICE_DYNAMICS", "0") == "1"
     eng = RolloutEngine(ctx, ph, n, n_threads=default_threads(), n_groups=groups, device_dynamics=dyn)
     rng = np.random.RandomState(0)
     q0 = np.tile(sk.default_qpos() if hasattr(sk, "default_qpos") else np.r_[0, 0, 1.0, 1, 0, 0, 0, np.zeros(52)], (n, 1))
@@ -60,7 +62,8 @@ def main():
         r = dev[s] - t0
         print("  sub %2d  %8.2f %8.2f %8.2f %8.2f %8.2f   | wait %.2f load %.2f solve %.2f store %.2f%s" % (
             s, r[0], r[1], r[2], r[3], r[4], r[1] - r[0], r[2] - r[1], r[3] - r[2], r[4] - r[3],
-            ("  then (last env of the wave stored / K8 + factors done) %.2f" % (r[5] - r[4])) if dev[s, 5] > 0 else ""))
+            ("  then (last env of the wave stored / K8 + factors done) %.2f" % (r[5] - r[4])) if dev[s, 5] > 0 else "") +
+            (("  then (K8 + factors of the wave's envs done) %.2f" % (r[6] - max(r[4], r[5]))) if dev[s, 6] > 0 else ""))
     print("host (owner of slice 0), us since the step was posted:  wait start | first row in | go written")
     for s in range(fs):
         print("  sub %2d  %8.2f %8.2f %8.2f   | waited %.2f physics %.2f" % (s, host[s, 0], host[s, 1], host[s, 2], host[s, 1] - host[s, 0], host[s, 2] - host[s, 1]))
