@@ -494,7 +494,7 @@ struct WsStage {
             const int row = r0 + 2 * (t & 63);
             one[0] = row == ones_row;
             one[1] = row + 1 == ones_row;
-            shift = row == rows - 1;
+            shift = rows >= 2 && row == rows - 1;          // (a one-row operand has no earlier row: the k-tile's base moves instead, see issue)
             off[0] = (unsigned)max(min(row, rows - 2), 0) * 4u;
         } else {
             one[1] = false;
@@ -510,6 +510,12 @@ struct WsStage {
     // of loads across the unrolled, branching producer loop and falls back to "everything older than the last few", which
     // collapses the four-deep prefetch into one. Staged registers: k-contiguous -> 16-byte pieces q[2 u], q[2 u + 1] =
     // k 0..3, 4..7 of row u; row pairs -> p[j] = (row 0, row 1) at k j; scalar form -> f[8 u + j].
+    // The thread's unpack flags under this binding. The producer loop keeps them PER REGISTER SET: a set is staged up to four
+    // k-tiles after its loads were issued, and by then `bind` may have run for the next work item.
+    __device__ __forceinline__ unsigned flags() const {
+        if constexpr (KC) return 0u;
+        else return (one[0] ? 1u : 0u) | (one[1] ? 2u : 0u) | (shift ? 4u : 0u);
+    }
     static constexpr int NLOAD = KC ? R / 32 : (PAIR ? 8 : R / 8);            // load instructions per k-tile and thread
     using Regs = std::conditional_t<KC, f32x4[R / 32], std::conditional_t<PAIR, f32x2[8], float[R / 8]>>;
     // k0: first k of the tile; `panel`: the wave's k-panel (wave-uniform), used by the row-contiguous forms;
@@ -545,7 +551,8 @@ struct WsStage {
         }
     }
     // after ws_wait: v[8 u + j] = element (row u of the thread, k = 8 panel + j) of the tile in all forms
-    __device__ __forceinline__ void unpack(const Regs &r, float (&v)[R / 8]) const {
+    // `f`: flags() as they were when the set's loads were issued
+    __device__ __forceinline__ void unpack(const Regs &r, float (&v)[R / 8], unsigned f) const {
         if constexpr (KC) {
 #pragma unroll
             for (int u = 0; u < R / 64; ++u)
@@ -554,15 +561,15 @@ struct WsStage {
         } else if constexpr (PAIR) {
 #pragma unroll
             for (int j = 0; j < 8; ++j) {
-                const float a = shift ? r[j][1] : r[j][0];
-                v[j] = one[0] ? 1.f : a;
-                v[8 + j] = one[1] ? 1.f : r[j][1];
+                const float a = (f & 4u) ? r[j][1] : r[j][0];
+                v[j] = (f & 1u) ? 1.f : a;
+                v[8 + j] = (f & 2u) ? 1.f : r[j][1];
             }
         } else {
 #pragma unroll
             for (int u = 0; u < R / 64; ++u)
 #pragma unroll
-                for (int j = 0; j < 8; ++j) v[8 * u + j] = one[u] ? 1.f : r[8 * u + j];
+                for (int j = 0; j < 8; ++j) v[8 * u + j] = ((f >> u) & 1u) ? 1.f : r[8 * u + j];
         }
     }
 };
@@ -690,6 +697,7 @@ __global__ __launch_bounds__(512) void k_gemm_ws(GemmArgs g) {
         typename SA::Regs ra[NSET];
         typename SB::Regs rb[NSET];
         int zrel[NSET] = {0, 0, 0, 0};
+        unsigned fla[NSET] = {0, 0, 0, 0}, flb[NSET] = {0, 0, 0, 0};     // WsStage::flags() of the item each set was loaded for
         SA sa;
         SB sb;
         int bound = -1;
@@ -733,6 +741,8 @@ __global__ __launch_bounds__(512) void k_gemm_ws(GemmArgs g) {
             const int kz = cur.kbeg + cur.s * BK;
             const int k0 = last ? cur.kend - BK : kz;
             zrel[SET] = kz - k0;
+            fla[SET] = sa.flags();
+            flb[SET] = sb.flags();
 #if defined(EGP_WS_SKIP) && EGP_WS_SKIP == 3      // timing probe: no operand loads at all (the staged registers hold whatever they held)
             if (g.M < 0)
 #endif
@@ -740,7 +750,13 @@ __global__ __launch_bounds__(512) void k_gemm_ws(GemmArgs g) {
                 const bool a_second = A_KC && g.A2 && k0 >= g.a_split;        // (a_split is a multiple of BK: a k-tile has one source)
                 sa.load(a_second ? g.A2 : g.A, a_second ? g.lda2 : g.lda, a_second ? k0 - g.a_split : k0, wave, ra[SET], a_second,
                         !A_KC && g.a_krows != nullptr, ka);
-                sb.load(b_second ? g.B2 : g.B, b_second ? g.ldb2 : g.ldb, k0, wave, rb[SET], false, !B_KC && !b_second && g.b_krows != nullptr, kb);
+                // a second source of ONE column has no row pair to read: its pairs start one element early (the element wanted is
+                // the pair's second, as for `shift`), except in the k-tile at k0 = 0, whose pairs end on the next k-row's element
+                // (the launcher asks for K > 32 then) -- no load leaves the operand either way
+                const int b_early = __builtin_amdgcn_readfirstlane(b_second && g.N - g.b_split == 1 && k0 > 0 ? 1 : 0);      // (wave-uniform: a scalar base)
+                if (b_early) flb[SET] |= 4u;
+                sb.load(b_second ? g.B2 - b_early : g.B, b_second ? g.ldb2 : g.ldb, k0, wave, rb[SET], false,
+                        !B_KC && !b_second && g.b_krows != nullptr, kb);
             } else {
                 sa.load(g.A, g.lda, k0, wave, ra[SET], false, false, ka);
                 sb.load(g.B, g.ldb, k0, wave, rb[SET], false, false, kb);
@@ -756,8 +772,8 @@ __global__ __launch_bounds__(512) void k_gemm_ws(GemmArgs g) {
             ws_wait<YOUNGER>(rb[SET]);
             EGP_TRW(1, 33);
             float va[BM / 8], vb[BN / 8];
-            sa.unpack(ra[SET], va);
-            sb.unpack(rb[SET], vb);
+            sa.unpack(ra[SET], va, fla[SET]);
+            sb.unpack(rb[SET], vb, flb[SET]);
             if (zrel[SET] > 0) {
                 ws_zero_head<BM>(va, zrel[SET], pa_panel);
                 ws_zero_head<BN>(vb, zrel[SET], pb_panel);
@@ -1175,6 +1191,7 @@ int egp_gemm_f32(const egp_gemm_desc *d, void *stream) {
     const bool partial = splits > 1 || ones;
     EGP_REQUIRE(!partial || d->workspace, "split-K / bias-gradient launches need a workspace (egp_gemm_workspace_floats)");
     EGP_REQUIRE(!partial || (!d->bias && !d->relu && !d->mask), "no epilogue on split-K launches");
+    EGP_REQUIRE(!d->accumulate || partial, "accumulate goes with split-K / bias-gradient launches only (a plain product would overwrite C)");
     EGP_REQUIRE(!ones || !d->b_kcontig, "the ones column (bias gradient) goes with B given as [k][n]");
     // (Round 3, measured and not kept: launching the column remainder of N = 300 as a 64-column-tile product of its own
     //  -- [0, 256) on 128-column tiles + [256, 300) on 64-column tiles, 2.58 instead of 3 tile units -- makes the update 1 ms
@@ -1200,6 +1217,7 @@ int egp_gemm_f32(const egp_gemm_desc *d, void *stream) {
                     "a_split must be a multiple of 32 and leave at least 32 columns to A2 (a k-tile reads one source)");
         EGP_REQUIRE(!d->A2 || splits == 1, "A2 does not go with split-K");
         EGP_REQUIRE(!d->B2 || (d->b_split > 0 && d->b_split % 128 == 0 && d->b_split < d->N + ones), "b_split must be a multiple of 128 inside (0, N)");
+        EGP_REQUIRE(!d->B2 || d->N - d->b_split != 1 || d->K > BK, "a single-column B2 needs K > 32 (its first k-tile reads one element past each row)");
         EGP_REQUIRE(!d->c_rows || !partial, "c_rows (scatter) does not go with split-K / bias-gradient launches");
         EGP_REQUIRE(!d->a_rows || d->a_src_rows > 0, "a_rows needs a_src_rows (rows of the gathered source)");
         EGP_REQUIRE(!d->b_krows || d->b_src_rows > 0, "b_krows needs b_src_rows (rows of the gathered source)");

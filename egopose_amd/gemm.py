@@ -105,6 +105,8 @@ def gemm(A, B, a_kcontig=True, b_kcontig=True, bias=None, relu=False, mask=None,
     k and n; `c_rows` -- result row m goes to out[c_rows[m]] (`out` required, rows nobody writes keep their content);
     `a_krows` -- A given as (K, M): k-row k is A[a_krows[k]] (with `b_krows`: a weight gradient over a subset of the rows)."""
     A, B = _mat(A, "A"), _mat(B, "B")
+    if accumulate and not (splits > 1 or want_bias_grad):
+        raise ValueError("accumulate goes with splits > 1 or want_bias_grad (a plain product overwrites `out`)")
     M, K = (A.shape if a_kcontig else A.shape[::-1])
     N, Kb = (B.shape if b_kcontig else B.shape[::-1])
     a_split = b_split = 0

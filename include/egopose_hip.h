@@ -266,7 +266,8 @@ int egp_gae_standardize_f32(float *adv, int32_t n, const double *stats, void *st
  *   splits > 1: split-K, partial sums through `workspace` and a fixed-order reduction (deterministic); no epilogue then.
  *   bias_grad != NULL (needs b_kcontig = 0): B gets a virtual column of ones, its result -- the column sums of A given
  *              as [k][m], i.e. the bias gradient of a weight-gradient product -- goes to bias_grad[M].
- *   accumulate: split-K / bias_grad launches add to C (and bias_grad) instead of overwriting.
+ *   accumulate: split-K / bias_grad launches add to C (and bias_grad) instead of overwriting. Set on any other launch
+ *              (splits <= 1 and bias_grad == NULL, whose epilogue overwrites C) it is refused with EGP_E_INVALID.
  * workspace: egp_gemm_workspace_floats(M, N, bias_grad != NULL, splits) floats, caller-owned, needed when splits > 1 or
  * bias_grad is set. All pointers are device memory, rows need 4-byte alignment only. */
 typedef struct egp_gemm_desc {
