@@ -91,6 +91,36 @@ class PpoLossDesc(C.Structure):
                 ("losses", vp), ("workspace", vp)]
 
 
+class MinibatchPlanDesc(C.Structure):
+    """egp_minibatch_plan_desc (include/egopose_hip.h)."""
+    _fields_ = [("n", C.c_int32), ("state_dim", C.c_int32), ("act_dim", C.c_int32), ("batch", C.c_int32),
+                ("perm", vp),
+                ("states", vp), ("ld_states", C.c_int64),
+                ("actions", vp), ("ld_act", C.c_int64),
+                ("returns", vp), ("adv", vp), ("fixed_logp", vp), ("exps", vp),
+                ("out_states", vp), ("out_actions", vp), ("out_returns", vp), ("out_adv", vp), ("out_fixed_logp", vp), ("out_exps", vp),
+                ("mb_n_exp", vp)]
+
+
+class PpoLossMbDesc(C.Structure):
+    """egp_ppo_loss_mb_desc (include/egopose_hip.h)."""
+    _fields_ = [("n", C.c_int32), ("act_dim", C.c_int32),
+                ("pred", vp), ("returns", vp),
+                ("mean", vp), ("ld_mean", C.c_int64),
+                ("actions", vp), ("ld_act", C.c_int64),
+                ("log_std", vp),
+                ("adv", vp), ("fixed_logp", vp), ("exps", vp),
+                ("n_exp", vp),
+                ("clip_eps", C.c_double),
+                ("d_pred", vp),
+                ("d_mean", vp), ("ld_dmean", C.c_int64),
+                ("d_log_std", vp),
+                ("losses", vp)]
+
+
+PPO_LOSS_MB_MAX_ROWS = 16384
+
+
 class AdamSegment(C.Structure):
     """egp_adam_segment (include/egopose_hip.h)."""
     _fields_ = [("begin", C.c_int64), ("end", C.c_int64),
@@ -186,6 +216,8 @@ SIGNATURES = {
     "egp_gemm_f32": (C.c_int, [C.POINTER(GemmDesc), vp]),
     "egp_ppo_loss_workspace_bytes": (_i64, [_i32, _i32, _i32]),
     "egp_ppo_loss_f32": (C.c_int, [C.POINTER(PpoLossDesc), vp]),
+    "egp_minibatch_plan_f32": (C.c_int, [C.POINTER(MinibatchPlanDesc), vp]),
+    "egp_ppo_loss_mb_f32": (C.c_int, [C.POINTER(PpoLossMbDesc), vp]),
     "egp_adam_workspace_bytes": (_i64, []),
     "egp_adam_step_f32": (C.c_int, [_i32, C.POINTER(AdamSegment), vp, vp, vp, vp, vp, vp, vp]),
     "egp_adam_step_f64": (C.c_int, [_i32, C.POINTER(AdamSegment), vp, vp, vp, vp, vp, vp, vp, vp]),

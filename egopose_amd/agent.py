@@ -423,7 +423,7 @@ class AgentPPO(AgentPG):
         `head` is the policy's action mean when the fused loss kernel runs (`_fused_losses`), else its log-probabilities.
         `counts` = (global rows, global exploration rows) when the caller has exchanged them already."""
         if self.use_mini_batch:
-            raise NotImplementedError("mini-batch PPO is not on the ego_mimic path (AgentEgo forces full batch)")
+            return self._update_policy_minibatch(states, actions, returns, advantages, exps)
         fused = self._fused_losses()
         if first_pass is None:
             ind, n_ind = self._exploration_rows(exps, states.shape[0])
@@ -483,6 +483,87 @@ class AgentPPO(AgentPG):
             self._optim_step()
             losses.append((v_loss.detach(), s_loss.detach()))
         self.update_stats = {"value_loss": [float(v) for v, _ in losses], "surr_loss": [float(s) for _, s in losses]}
+
+    # -- shuffled mini-batch epochs (agents/agent_ppo.py:24-44) ----------------------------------------
+    def _update_policy_minibatch(self, states, actions, returns, advantages, exps):
+        """Every epoch shuffles the batch (NumPy's global generator, as the reference: a run seeded like the reference's shuffles
+        identically) and takes one value step and one policy step per window of `opt_batch_size` rows; the last window may be
+        short. Two forms: the fused one (`_fused_losses`: float32 on the GPU, Gaussian head) keeps the whole update on the
+        device; the plain one is the reference's formulation in torch ops, on any device and dtype."""
+        if D.world_size() > 1:
+            raise RuntimeError("AgentPPO(use_mini_batch=True) runs on one rank: with %d ranks the number of rows, and so the number of "
+                               "optimizer steps per epoch, differs between ranks and the gradient exchange would not line up "
+                               "(use the full-batch update for multi-GPU runs)" % D.world_size())
+        with to_test(*self.update_modules):
+            with torch.no_grad():
+                fixed_log_probs = self.cn.policy_net.get_log_prob(self.trans_policy(states), actions)
+        n, batch = states.shape[0], int(self.opt_batch_size)
+        n_iter = int(math.ceil(n / batch))
+        if self._fused_losses() and 1 <= batch <= O.L.PPO_LOSS_MB_MAX_ROWS and n > 0:
+            return self._update_policy_minibatch_fused(states, actions, returns, advantages, fixed_log_probs, exps, batch, n_iter)
+        cols = (states, actions, returns, advantages, fixed_log_probs, exps)
+        v_losses, s_losses = [], []
+        for _ in range(self.opt_num_epochs):
+            perm = np.arange(n)
+            np.random.shuffle(perm)
+            perm = torch.from_numpy(perm).to(states.device)
+            cols = tuple(c[perm] for c in cols)              # (the reference permutes the already permuted columns)
+            for i in range(n_iter):
+                states_b, actions_b, returns_b, advantages_b, fixed_b, exps_b = (c[i * batch:min((i + 1) * batch, n)] for c in cols)
+                ind = exps_b.nonzero().squeeze(1)
+                for _ in range(self.value_opt_niter):
+                    self._zero_grads()
+                    pred = self.cn.value_net(self.trans_value(states_b))
+                    v_loss = (pred - returns_b).pow(2).mean()
+                    v_loss.backward()
+                    self._optim_step(which=(0,))
+                s_loss = self.ppo_loss(states_b, actions_b, advantages_b, fixed_b, ind)
+                self._zero_grads()
+                s_loss.backward()
+                self._optim_step(which=(1,))
+                v_losses.append(v_loss.detach())
+                s_losses.append(s_loss.detach())
+        self.update_stats = {"value_loss": [float(v) for v in v_losses], "surr_loss": [float(s) for s in s_losses]}
+
+    def _update_policy_minibatch_fused(self, states, actions, returns, advantages, fixed_log_probs, exps, batch, n_iter):
+        """One optim.minibatch_plan per epoch (the permuted columns and every window's exploration-row count, left on the device),
+        then per window: both nets on slice views of the plan's buffers, ONE optim.ppo_losses_mb (rows with exps == 0 masked
+        instead of gathered away: no nonzero(), no shape that depends on the data), autograd from (values, action mean), and one
+        fused step -- critic and actor have disjoint parameters, so the value step and the policy step share it. The host reads
+        nothing between the first plan and the losses after the last epoch."""
+        dev = states.device
+        n, A = states.shape[0], actions.shape[1]
+        log_std = self.cn.policy_net.action_log_std
+        learn_std = bool(log_std.requires_grad)
+        src = [states if states.stride(1) == 1 else states.contiguous(), actions if actions.stride(1) == 1 else actions.contiguous()] + \
+              [c.reshape(-1).contiguous() for c in (returns, advantages, fixed_log_probs, exps)]
+        buf = [torch.empty(c.shape, dtype=torch.float32, device=dev) for c in src]
+        counts = torch.empty(n_iter, dtype=torch.int32, device=dev)
+        rec = torch.zeros(max(1, self.opt_num_epochs), n_iter, 2, dtype=torch.float64, device=dev)
+        d_pred = torch.empty(batch, 1, dtype=torch.float32, device=dev)
+        d_mean = torch.empty(batch, A, dtype=torch.float32, device=dev)
+        states_p, actions_p, returns_p, adv_p, fixed_p, exps_p = buf
+        cur = np.arange(n)
+        for epoch in range(self.opt_num_epochs):
+            perm = np.arange(n)
+            np.random.shuffle(perm)
+            cur = cur[perm]                                  # the reference permutes the permuted columns: compose, gather from the originals
+            O.minibatch_plan(*src, torch.from_numpy(cur).to(dev), batch, out=buf, mb_n_exp=counts)
+            for i in range(n_iter):
+                lo, hi = i * batch, min((i + 1) * batch, n)
+                pred = self.cn.value_net(self.trans_value(states_p[lo:hi]))
+                mean = self._policy_mean(self.trans_policy(states_p[lo:hi]))
+                self._zero_grads()
+                _, _, _, d_ls = O.ppo_losses_mb(pred.detach(), returns_p[lo:hi], mean.detach(), actions_p[lo:hi], log_std.detach(), adv_p[lo:hi],
+                                                fixed_p[lo:hi], exps_p[lo:hi], counts[i:i + 1], self.clip_epsilon, d_pred=d_pred[:hi - lo],
+                                                d_mean=d_mean[:hi - lo], want_d_log_std=learn_std, losses_out=rec[epoch, i])
+                torch.autograd.backward([pred, mean], [d_pred[:hi - lo], d_mean[:hi - lo]])
+                if learn_std:
+                    log_std.grad = d_ls.view_as(log_std)
+                self._optim_step()
+        self._epochs_enqueued()
+        host = rec[:self.opt_num_epochs].reshape(-1, 2).tolist()
+        self.update_stats = {"value_loss": [r[0] for r in host], "surr_loss": [r[1] for r in host]}
 
     def _policy_mean(self, x):
         return self.cn.policy_net.mean_std(x)[0]

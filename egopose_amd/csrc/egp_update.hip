@@ -4,10 +4,12 @@
 //   k_ppo_loss   agents/agent_pg.py:19-26 (critic MSE), agents/agent_ppo.py:58-65 (clipped surrogate) over
 //                core/distributions.py:6-25 / utils/math.py:14-17 (diagonal Gaussian log-density), plus what autograd would
 //                send back to `values_pred` and `action_mean`
+//   k_minibatch_plan / k_ppo_loss_mb   the mini-batch epochs (agents/agent_ppo.py:24-44): the epoch's shuffle as one gather of the
+//                update's columns + per-window exploration-row counts, and k_ppo_loss for one window with data-independent shapes
 //   k_sqnorm     torch.nn.utils.clip_grad_norm_'s total norm (agents/agent_ppo.py:53-56)
 //   k_adam       torch.optim.Adam.step for every parameter group of both optimizers (agent_ppo.py:24-30)
 //
-// All three are one pass over their operands (HBM-bound, a few MB): what they replace is ~45 launch-bound library kernels per
+// The loss and optimizer kernels are one pass over their operands (HBM-bound, a few MB): what they replace is ~45 launch-bound library kernels per
 // epoch. Reductions are float64 in a fixed order: per-workgroup partials, summed in index order by a one-workgroup launch.
 #include <hip/hip_runtime.h>
 
@@ -58,6 +60,61 @@ __device__ __forceinline__ double block_sum(double v, double *s_red) {
     return (s_red[0] + s_red[1]) + (s_red[2] + s_red[3]);
 }
 
+// ---- the per-row arithmetic of the surrogate, shared by k_ppo_loss and k_ppo_loss_mb. A 16-lane group owns a row; lane l
+// takes action dimensions l, l + 16, ... (`ok` = the group has a row: lanes without one run along for the shuffles).
+constexpr int LOSS_MAXD = LOSS_MAX_ACT / LOSS_GROUP;
+
+// log-density of the row under N(mean, exp(log_std)), summed over the group; leaves z_j = (a_j - mean_j) / std_j and 1 / std_j
+__device__ __forceinline__ float row_logp(bool ok, int l, int act_dim, const float *__restrict__ act_row, const float *__restrict__ mean_row,
+                                          const float *__restrict__ log_std, float (&z)[LOSS_MAXD], float (&istd)[LOSS_MAXD]) {
+    const float half_log_2pi = 0.91893853320467274178f;
+    float acc = 0.f;
+#pragma unroll
+    for (int k = 0; k < LOSS_MAXD; ++k) {
+        const int j = l + LOSS_GROUP * k;
+        z[k] = 0.f; istd[k] = 0.f;
+        if (ok && j < act_dim) {
+            const float ls = log_std[j];
+            istd[k] = expf(-ls);
+            z[k] = (act_row[j] - mean_row[j]) * istd[k];
+            // normal_log_density per element: -z^2 / 2 - 0.5 log(2 pi) - log_std
+            acc += -0.5f * z[k] * z[k] - half_log_2pi - ls;
+        }
+    }
+#pragma unroll
+    for (int off = LOSS_GROUP / 2; off > 0; off >>= 1) acc += __shfl_xor(acc, off, LOSS_GROUP);
+    return acc;
+}
+
+// surr = min(ratio A, clamp(ratio, lo, hi) A) -> `surr`; returns d loss / d logp for loss = -inv_n_exp * sum surr (neg_inv = -inv_n_exp)
+__device__ __forceinline__ float row_surrogate(bool ok, float logp, float fixed, float adv, float lo, float hi, float neg_inv, float &surr) {
+    const float ratio = expf(logp - fixed);
+    const float clamped = fminf(fmaxf(ratio, lo), hi);
+    const float surr1 = ratio * adv, surr2 = clamped * adv;
+    surr = fminf(surr1, surr2);
+    // d surr / d ratio with torch.min's tie rule (half each way) and clamp's sub-gradient (1 inside [lo, hi], ends included)
+    const float inside = (ratio >= lo && ratio <= hi) ? 1.f : 0.f;
+    float g_ratio;
+    if (surr1 < surr2) g_ratio = adv;
+    else if (surr1 > surr2) g_ratio = adv * inside;
+    else g_ratio = 0.5f * adv + 0.5f * adv * inside;
+    // loss = -inv_n_exp * sum surr;  d loss / d logp = -inv_n_exp * g_ratio * ratio
+    return ok ? neg_inv * g_ratio * ratio : 0.f;
+}
+
+// d logp / d mean_j = z_j / std_j -> the row of d_mean;  d logp / d log_std_j = z_j^2 - 1 -> the lane's running sums
+__device__ __forceinline__ void row_grads(bool ok, int l, int act_dim, float g_logp, const float (&z)[LOSS_MAXD], const float (&istd)[LOSS_MAXD],
+                                          float *__restrict__ d_mean_row, float (&dls)[LOSS_MAXD]) {
+#pragma unroll
+    for (int k = 0; k < LOSS_MAXD; ++k) {
+        const int j = l + LOSS_GROUP * k;
+        if (ok && j < act_dim) {
+            d_mean_row[j] = g_logp * z[k] * istd[k];
+            dls[k] += g_logp * (z[k] * z[k] - 1.f);
+        }
+    }
+}
+
 __global__ __launch_bounds__(LOSS_BLOCK) void k_ppo_loss(LossArgs a) {
     __shared__ double s_red[4];
     __shared__ float s_grp[LOSS_BLOCK / LOSS_GROUP][LOSS_MAX_ACT];        // d_log_std sums of the block's 16 row groups
@@ -81,62 +138,27 @@ __global__ __launch_bounds__(LOSS_BLOCK) void k_ppo_loss(LossArgs a) {
         // ---- actor: a 16-lane group per row, lane l takes action dimensions l, l + 16, ...
         const int grp = t / LOSS_GROUP, l = t % LOSS_GROUP;
         constexpr int GPB = LOSS_BLOCK / LOSS_GROUP;
-        constexpr int MAXD = LOSS_MAX_ACT / LOSS_GROUP;
+        constexpr int MAXD = LOSS_MAXD;
         float dls[MAXD];
 #pragma unroll
         for (int k = 0; k < MAXD; ++k) dls[k] = 0.f;
         const float lo = (float)(1.0 - a.clip_eps), hi = (float)(1.0 + a.clip_eps);
         const float neg_inv = (float)(-a.inv_n_exp);
-        const float half_log_2pi = 0.91893853320467274178f;
         for (long r0 = (long)blockIdx.x * GPB; r0 < a.n_pol; r0 += (long)a.pol_blocks * GPB) {
             const long i = r0 + grp;
             const bool ok = i < a.n_pol;
             const long s = ok ? (a.rows ? (long)a.rows[i] : i) : 0;
-            float z[MAXD], istd[MAXD];
-            float acc = 0.f;
-#pragma unroll
-            for (int k = 0; k < MAXD; ++k) {
-                const int j = l + LOSS_GROUP * k;
-                z[k] = 0.f; istd[k] = 0.f;
-                if (ok && j < a.act_dim) {
-                    const float ls = a.log_std[j];
-                    istd[k] = expf(-ls);
-                    z[k] = (a.actions[s * a.ld_act + j] - a.mean[i * a.ld_mean + j]) * istd[k];
-                    // normal_log_density per element: -z^2 / 2 - 0.5 log(2 pi) - log_std
-                    acc += -0.5f * z[k] * z[k] - half_log_2pi - ls;
-                }
-            }
-#pragma unroll
-            for (int off = LOSS_GROUP / 2; off > 0; off >>= 1) acc += __shfl_xor(acc, off, LOSS_GROUP);
-            const float logp = acc;
+            float z[LOSS_MAXD], istd[LOSS_MAXD];
+            const float logp = row_logp(ok, l, a.act_dim, a.actions + s * a.ld_act, a.mean + i * a.ld_mean, a.log_std, z, istd);
             float fixed = logp;
             if (ok) {
                 if (a.write_fixed) { if (l == 0) a.fixed_logp[i] = logp; }
                 else fixed = a.fixed_logp[i];
             }
-            const float adv = ok ? a.adv[s] : 0.f;
-            const float ratio = expf(logp - fixed);
-            const float clamped = fminf(fmaxf(ratio, lo), hi);
-            const float surr1 = ratio * adv, surr2 = clamped * adv;
-            const float surr = fminf(surr1, surr2);
-            // d surr / d ratio with torch.min's tie rule (half each way) and clamp's sub-gradient (1 inside [lo, hi], ends included)
-            const float inside = (ratio >= lo && ratio <= hi) ? 1.f : 0.f;
-            float g_ratio;
-            if (surr1 < surr2) g_ratio = adv;
-            else if (surr1 > surr2) g_ratio = adv * inside;
-            else g_ratio = 0.5f * adv + 0.5f * adv * inside;
-            // loss = -inv_n_exp * sum surr;  d loss / d logp = -inv_n_exp * g_ratio * ratio
-            const float g_logp = ok ? neg_inv * g_ratio * ratio : 0.f;
+            float surr;
+            const float g_logp = row_surrogate(ok, logp, fixed, ok ? a.adv[s] : 0.f, lo, hi, neg_inv, surr);
             if (ok && l == 0) s_sum += (double)surr;
-#pragma unroll
-            for (int k = 0; k < MAXD; ++k) {
-                const int j = l + LOSS_GROUP * k;
-                if (ok && j < a.act_dim) {
-                    // d logp / d mean_j = z_j / std_j;  d logp / d log_std_j = z_j^2 - 1
-                    a.d_mean[i * a.ld_dmean + j] = g_logp * z[k] * istd[k];
-                    dls[k] += g_logp * (z[k] * z[k] - 1.f);
-                }
-            }
+            row_grads(ok, l, a.act_dim, g_logp, z, istd, a.d_mean + i * a.ld_dmean, dls);
         }
         if (want_dls) {
 #pragma unroll
@@ -182,6 +204,167 @@ __global__ __launch_bounds__(LOSS_BLOCK) void k_ppo_loss_final(LossArgs a, int n
         for (int j = t; j < a.act_dim; j += LOSS_BLOCK) {
             double d = 0.0;
             for (int b = 0; b < a.pol_blocks; ++b) d += a.part[(long)b * stride + 2 + j];
+            a.d_log_std[j] = (float)d;
+        }
+    }
+}
+
+// ------------------------------------------------------------------------------------------------ mini-batch epochs
+// agents/agent_ppo.py:24-44: every epoch shuffles the batch, then takes optimizer steps on windows of opt_batch_size rows. A
+// window is a few dozen rows, so everything here is launch latency: one launch lays the epoch out (k_minibatch_plan), one launch
+// per window forms both losses (k_ppo_loss_mb), and the number of exploration rows of a window never leaves the device.
+
+constexpr int PLAN_BLOCK = 256;
+constexpr int PLAN_MAX_BLOCKS = 1024;
+
+struct PlanArgs {
+    int n, state_dim, act_dim, batch, n_win;
+    const long long *perm;
+    const float *states, *actions, *returns, *adv, *fixed_logp, *exps;
+    long ld_states, ld_act;
+    float *o_states, *o_actions, *o_returns, *o_adv, *o_fixed_logp, *o_exps;
+    int *mb_n_exp;
+    int wide_states, wide_act;
+};
+
+// rows of `width` floats: dst row r = src row perm[r]; the grid strides over the (row, column) elements
+template <typename V>
+__device__ __forceinline__ void plan_copy_rows(const PlanArgs &a, const float *__restrict__ src, long ld_src, float *__restrict__ dst, int width) {
+    constexpr int W = (int)(sizeof(V) / sizeof(float));
+    const int wv = width / W;
+    const long total = (long)a.n * wv;
+    for (long e = (long)blockIdx.x * PLAN_BLOCK + threadIdx.x; e < total; e += (long)gridDim.x * PLAN_BLOCK) {
+        const long r = e / wv;
+        const int c = (int)(e - r * wv);
+        const long long sr = a.perm[r];
+        if (sr < 0 || sr >= a.n) continue;                       // (not a permutation: the row is left alone, nothing is read out of range)
+        *reinterpret_cast<V *>(dst + r * width + (long)c * W) = *reinterpret_cast<const V *>(src + sr * ld_src + (long)c * W);
+    }
+}
+
+__global__ __launch_bounds__(PLAN_BLOCK) void k_minibatch_plan(PlanArgs a) {
+    __shared__ int s_cnt[PLAN_BLOCK / 64];
+    if (a.wide_states) plan_copy_rows<float4>(a, a.states, a.ld_states, a.o_states, a.state_dim);
+    else plan_copy_rows<float>(a, a.states, a.ld_states, a.o_states, a.state_dim);
+    if (a.wide_act) plan_copy_rows<float4>(a, a.actions, a.ld_act, a.o_actions, a.act_dim);
+    else plan_copy_rows<float>(a, a.actions, a.ld_act, a.o_actions, a.act_dim);
+    for (long r = (long)blockIdx.x * PLAN_BLOCK + threadIdx.x; r < a.n; r += (long)gridDim.x * PLAN_BLOCK) {
+        const long long sr = a.perm[r];
+        if (sr < 0 || sr >= a.n) continue;
+        a.o_returns[r] = a.returns[sr];
+        a.o_adv[r] = a.adv[sr];
+        a.o_fixed_logp[r] = a.fixed_logp[sr];
+        a.o_exps[r] = a.exps[sr];
+    }
+    // exploration rows per window: windows stride over the workgroups, a window's rows over the workgroup's threads; each wave
+    // counts with ballot + popcount and the four wave counts are added in order. Every entry is written: nothing to zero first.
+    const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+    for (int w = blockIdx.x; w < a.n_win; w += gridDim.x) {
+        const long begin = (long)w * a.batch;
+        const long end = begin + a.batch < a.n ? begin + a.batch : a.n;
+        int cnt = 0;
+        for (long r0 = begin; r0 < end; r0 += PLAN_BLOCK) {          // (uniform trip count: the ballot sees whole waves)
+            const long r = r0 + threadIdx.x;
+            bool on = false;
+            if (r < end) {
+                const long long sr = a.perm[r];
+                on = sr >= 0 && sr < a.n && a.exps[sr] != 0.f;
+            }
+            cnt += __popcll(__ballot(on));
+        }
+        __syncthreads();
+        if (lane == 0) s_cnt[wave] = cnt;
+        __syncthreads();
+        if (threadIdx.x == 0) a.mb_n_exp[w] = s_cnt[0] + s_cnt[1] + s_cnt[2] + s_cnt[3];
+    }
+}
+
+constexpr int MB_BLOCK = 512;                      // one workgroup per window: 32 row groups of 16 lanes
+constexpr int MB_GROUPS = MB_BLOCK / LOSS_GROUP;
+constexpr int MB_WAVES = MB_BLOCK / 64;
+
+struct LossMbArgs {
+    int n, act_dim;
+    const float *pred, *returns, *mean, *actions, *log_std, *adv, *fixed_logp, *exps;
+    long ld_mean, ld_act, ld_dmean;
+    const int *n_exp;
+    double clip_eps;
+    float *d_pred, *d_mean, *d_log_std;
+    double *losses;
+};
+
+__device__ __forceinline__ double block_sum_mb(double v, double *s_red) {
+    // as block_sum, for the MB_BLOCK threads of k_ppo_loss_mb: lane butterflies, then the eight wave sums in index order
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) v += __shfl_down(v, off, 64);
+    const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+    __syncthreads();
+    if (lane == 0) s_red[wave] = v;
+    __syncthreads();
+    double tot = 0.0;
+#pragma unroll
+    for (int w = 0; w < MB_WAVES; ++w) tot += s_red[w];
+    return tot;
+}
+
+// Both losses of ONE window of the permuted batch, with fixed shapes: the policy head was evaluated on every row, the rows with
+// exps == 0 get d_mean = 0 (exact zeros in every weight gradient: what leaving them out of the batch gives) and stay out of the
+// surrogate's sums; its mean divides by the count k_minibatch_plan left on the device. A window is a few thousand rows at most,
+// so one workgroup walks it and adds its own partials in index order: no workspace, no second launch.
+__global__ __launch_bounds__(MB_BLOCK) void k_ppo_loss_mb(LossMbArgs a) {
+    __shared__ double s_red[MB_WAVES];
+    __shared__ float s_grp[MB_GROUPS][LOSS_MAX_ACT];
+    const int t = threadIdx.x;
+    const bool want_dls = a.d_log_std != nullptr;
+    // ---- critic
+    double v_sum = 0.0;
+    const double inv_n_val = 1.0 / (double)(a.n > 0 ? a.n : 1);
+    const float two_inv = (float)(2.0 * inv_n_val);
+    for (int i = t; i < a.n; i += MB_BLOCK) {
+        const float d = a.pred[i] - a.returns[i];
+        v_sum += (double)d * (double)d;
+        a.d_pred[i] = two_inv * d;
+    }
+    // ---- actor
+    const int cnt = *a.n_exp;
+    const double inv_n_exp = 1.0 / (double)cnt;                 // an empty window: 1 / 0, the surrogate loss below is 0 * inf = NaN (torch's empty .mean())
+    const int grp = t / LOSS_GROUP, l = t % LOSS_GROUP;
+    float dls[LOSS_MAXD];
+#pragma unroll
+    for (int k = 0; k < LOSS_MAXD; ++k) dls[k] = 0.f;
+    const float lo = (float)(1.0 - a.clip_eps), hi = (float)(1.0 + a.clip_eps);
+    const float neg_inv = (float)(-inv_n_exp);
+    double s_sum = 0.0;
+    for (int r0 = 0; r0 < a.n; r0 += MB_GROUPS) {
+        const long i = r0 + grp;
+        const bool in = i < a.n;
+        const bool ok = in && a.exps[i] != 0.f;
+        const long s = in ? i : 0;
+        float z[LOSS_MAXD], istd[LOSS_MAXD];
+        const float logp = row_logp(ok, l, a.act_dim, a.actions + s * a.ld_act, a.mean + s * a.ld_mean, a.log_std, z, istd);
+        float surr;
+        const float g_logp = row_surrogate(ok, logp, ok ? a.fixed_logp[i] : logp, ok ? a.adv[i] : 0.f, lo, hi, neg_inv, surr);
+        if (ok && l == 0) s_sum += (double)surr;
+        row_grads(ok, l, a.act_dim, g_logp, z, istd, a.d_mean + s * a.ld_dmean, dls);
+        if (in && !ok)
+            for (int j = l; j < a.act_dim; j += LOSS_GROUP) a.d_mean[i * a.ld_dmean + j] = 0.f;
+    }
+    const double vs = block_sum_mb(v_sum, s_red);
+    const double ss = block_sum_mb(s_sum, s_red);
+    if (t == 0) {
+        a.losses[0] = vs * inv_n_val;
+        a.losses[1] = -ss * inv_n_exp;
+    }
+    if (want_dls) {
+#pragma unroll
+        for (int k = 0; k < LOSS_MAXD; ++k) {
+            const int j = l + LOSS_GROUP * k;
+            if (j < a.act_dim) s_grp[grp][j] = dls[k];
+        }
+        __syncthreads();
+        for (int j = t; j < a.act_dim; j += MB_BLOCK) {          // the 32 row groups in index order
+            double d = 0.0;
+            for (int g = 0; g < MB_GROUPS; ++g) d += (double)s_grp[g][j];
             a.d_log_std[j] = (float)d;
         }
     }
@@ -343,6 +526,56 @@ int egp_ppo_loss_f32(const egp_ppo_loss_desc *d, void *stream) {
     if (rc != EGP_OK) return rc;
     k_ppo_loss_final<<<dim3(1), dim3(LOSS_BLOCK), 0, (hipStream_t)stream>>>(a, (int)(pb + vb));
     return after_launch("k_ppo_loss_final");
+}
+
+int egp_minibatch_plan_f32(const egp_minibatch_plan_desc *d, void *stream) {
+    EGP_REQUIRE(d, "descriptor is NULL");
+    EGP_REQUIRE(d->n >= 0 && d->state_dim >= 1 && d->act_dim >= 1 && d->batch >= 1, "bad sizes (n >= 0, state_dim / act_dim / batch >= 1)");
+    if (d->n == 0) return EGP_OK;
+    EGP_REQUIRE(d->perm && d->states && d->actions && d->returns && d->adv && d->fixed_logp && d->exps, "NULL source column");
+    EGP_REQUIRE(d->out_states && d->out_actions && d->out_returns && d->out_adv && d->out_fixed_logp && d->out_exps && d->mb_n_exp,
+                "NULL destination");
+    EGP_REQUIRE(d->ld_states >= d->state_dim && d->ld_act >= d->act_dim, "row stride smaller than the row");
+    PlanArgs a{};
+    a.n = d->n; a.state_dim = d->state_dim; a.act_dim = d->act_dim; a.batch = d->batch;
+    a.n_win = (int)(((long)d->n + d->batch - 1) / d->batch);
+    a.perm = (const long long *)d->perm;
+    a.states = d->states; a.actions = d->actions; a.returns = d->returns; a.adv = d->adv; a.fixed_logp = d->fixed_logp; a.exps = d->exps;
+    a.ld_states = d->ld_states; a.ld_act = d->ld_act;
+    a.o_states = d->out_states; a.o_actions = d->out_actions; a.o_returns = d->out_returns; a.o_adv = d->out_adv;
+    a.o_fixed_logp = d->out_fixed_logp; a.o_exps = d->out_exps;
+    a.mb_n_exp = d->mb_n_exp;
+    // 16-byte moves when every row base on both sides is 16-byte aligned, single floats otherwise
+    auto wide = [](const void *src, long ld, const void *dst, int width) {
+        return width % 4 == 0 && ld % 4 == 0 && (uintptr_t)src % 16 == 0 && (uintptr_t)dst % 16 == 0;
+    };
+    a.wide_states = wide(d->states, a.ld_states, d->out_states, d->state_dim) ? 1 : 0;
+    a.wide_act = wide(d->actions, a.ld_act, d->out_actions, d->act_dim) ? 1 : 0;
+    const int widest = d->state_dim > d->act_dim ? d->state_dim : d->act_dim;
+    long blocks = ((long)d->n * (a.wide_states ? widest / 4 : widest) + PLAN_BLOCK - 1) / PLAN_BLOCK;
+    blocks = blocks < 1 ? 1 : (blocks > PLAN_MAX_BLOCKS ? PLAN_MAX_BLOCKS : blocks);
+    k_minibatch_plan<<<dim3((unsigned)blocks), dim3(PLAN_BLOCK), 0, (hipStream_t)stream>>>(a);
+    return after_launch("k_minibatch_plan");
+}
+
+int egp_ppo_loss_mb_f32(const egp_ppo_loss_mb_desc *d, void *stream) {
+    EGP_REQUIRE(d, "descriptor is NULL");
+    EGP_REQUIRE(d->n >= 1 && d->n <= EGP_PPO_LOSS_MB_MAX_ROWS, "a window has 1 .. EGP_PPO_LOSS_MB_MAX_ROWS rows");
+    EGP_REQUIRE(d->act_dim >= 1 && d->act_dim <= LOSS_MAX_ACT, "bad act_dim (1 .. 256)");
+    EGP_REQUIRE(d->pred && d->returns && d->mean && d->actions && d->log_std && d->adv && d->fixed_logp && d->exps && d->n_exp, "NULL operand");
+    EGP_REQUIRE(d->d_pred && d->d_mean && d->losses, "NULL result");
+    EGP_REQUIRE(d->ld_mean >= d->act_dim && d->ld_act >= d->act_dim && d->ld_dmean >= d->act_dim, "row stride smaller than the row");
+    LossMbArgs a{};
+    a.n = d->n; a.act_dim = d->act_dim;
+    a.pred = d->pred; a.returns = d->returns; a.mean = d->mean; a.actions = d->actions; a.log_std = d->log_std; a.adv = d->adv;
+    a.fixed_logp = d->fixed_logp; a.exps = d->exps;
+    a.ld_mean = d->ld_mean; a.ld_act = d->ld_act; a.ld_dmean = d->ld_dmean;
+    a.n_exp = d->n_exp;
+    a.clip_eps = d->clip_eps;
+    a.d_pred = d->d_pred; a.d_mean = d->d_mean; a.d_log_std = d->d_log_std;
+    a.losses = d->losses;
+    k_ppo_loss_mb<<<dim3(1), dim3(MB_BLOCK), 0, (hipStream_t)stream>>>(a);
+    return after_launch("k_ppo_loss_mb");
 }
 
 int64_t egp_adam_workspace_bytes(void) { return (int64_t)(EGP_ADAM_MAX_SEGMENTS + 1) * NORM_BLOCKS * (int64_t)sizeof(double); }

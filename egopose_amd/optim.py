@@ -3,6 +3,10 @@
   ppo_losses(...)   critic MSE (agents/agent_pg.py:19-26) + clipped surrogate (agents/agent_ppo.py:58-65 over
                     core/distributions.py:6-25) and their gradients w.r.t. `values_pred` / `action_mean` in ONE launch; the caller
                     back-propagates from those two tensors (no scalar-loss graph)
+  minibatch_plan(...)  one launch per mini-batch epoch (agents/agent_ppo.py:25-31): the update's six columns gathered through the
+                    epoch's permutation into the caller's buffers + the number of exploration rows of every window, on the device
+  ppo_losses_mb(...)   ppo_losses for ONE window of those buffers with shapes that do not depend on the data: the rows with
+                    exps == 0 are masked (d_mean = 0), the surrogate's mean divides by the window's device-side count
   FlatUpdater       clip_policy_grad (agent_ppo.py:53-56) + optimizer_value.step() + optimizer_policy.step() (agent_ppo.py:24-30)
                     as two launches over flat buffers. The caller's torch.optim.Adam objects stay the source of every
                     hyper-parameter (`set_optimizer_lr` keeps working) and see the moments as their own state; the parameters of
@@ -85,6 +89,104 @@ def ppo_losses(pred, returns, mean, actions, log_std, adv, fixed_logp, write_fix
     d.d_log_std = d_ls.data_ptr() if d_ls is not None else None
     d.losses, d.workspace = losses.data_ptr(), ws.data_ptr()
     L.check(lib.egp_ppo_loss_f32(C.byref(d), L.current_stream()), "egp_ppo_loss_f32")
+    return losses, d_pred, d_mean, d_ls
+
+
+def _f32_vector(name, t, want):
+    if not (t.is_cuda and t.dtype == torch.float32 and t.is_contiguous() and t.numel() == want):
+        raise ValueError("%s must be a contiguous float32 HIP tensor of %d elements" % (name, want))
+    return t
+
+
+def _f32_rows(name, t, n, width=None):
+    if not (t.is_cuda and t.dtype == torch.float32 and t.dim() == 2 and t.shape[0] == n and (width is None or t.shape[1] == width)
+            and t.shape[1] >= 1 and t.stride(1) == 1 and (n <= 1 or t.stride(0) >= t.shape[1])):
+        raise ValueError("%s must be (%d, %s) float32 on the HIP device with unit column stride" % (name, n, "width" if width is None else width))
+    return t
+
+
+def minibatch_plan(states, actions, returns, adv, fixed_logp, exps, perm, batch, out=None, mb_n_exp=None):
+    """-> (out, mb_n_exp). `out` = the six columns with row r taken from source row perm[r] (dense float32 buffers of the sources'
+    shapes, allocated here unless given); mb_n_exp int32[ceil(N / batch)] = rows with exps != 0 in every window of `batch` rows.
+    `perm`: int64 permutation of 0 .. N-1 on the device. One launch; nothing is read back."""
+    lib = L.load()
+    N = states.shape[0]
+    batch = int(batch)
+    if batch < 1:
+        raise ValueError("batch must be >= 1")
+    _f32_rows("states", states, N)
+    _f32_rows("actions", actions, N)
+    cols = [states, actions] + [_f32_vector(k, t.reshape(-1), N) for k, t in (("returns", returns), ("adv", adv), ("fixed_logp", fixed_logp), ("exps", exps))]
+    if not (perm.is_cuda and perm.dtype == torch.int64 and perm.is_contiguous() and perm.numel() == N):
+        raise ValueError("perm must be a contiguous int64 HIP tensor with one entry per row")
+    dev = states.device
+    n_win = (N + batch - 1) // batch
+    if out is None:
+        out = [torch.empty(c.shape, dtype=torch.float32, device=dev) for c in (states, actions, returns, adv, fixed_logp, exps)]
+    if len(out) != 6:
+        raise ValueError("out must hold six destination buffers")
+    for c, o in zip(cols, out):
+        if not (o.is_cuda and o.dtype == torch.float32 and o.is_contiguous() and o.numel() == c.numel()) or o.data_ptr() == c.data_ptr() and N > 0:
+            raise ValueError("every destination must be a contiguous float32 HIP buffer of its source's size, distinct from it")
+    if mb_n_exp is None:
+        mb_n_exp = torch.empty(n_win, dtype=torch.int32, device=dev)
+    if not (mb_n_exp.is_cuda and mb_n_exp.dtype == torch.int32 and mb_n_exp.is_contiguous() and mb_n_exp.numel() == n_win):
+        raise ValueError("mb_n_exp must be a contiguous int32 HIP tensor of %d elements" % n_win)
+    d = L.MinibatchPlanDesc()
+    d.n, d.state_dim, d.act_dim, d.batch = N, states.shape[1], actions.shape[1], batch
+    d.perm = perm.data_ptr()
+    d.states, d.ld_states = states.data_ptr(), states.stride(0) if N > 1 else states.shape[1]
+    d.actions, d.ld_act = actions.data_ptr(), actions.stride(0) if N > 1 else actions.shape[1]
+    d.returns, d.adv, d.fixed_logp, d.exps = (c.data_ptr() for c in cols[2:])
+    d.out_states, d.out_actions, d.out_returns, d.out_adv, d.out_fixed_logp, d.out_exps = (o.data_ptr() for o in out)
+    d.mb_n_exp = mb_n_exp.data_ptr()
+    L.check(lib.egp_minibatch_plan_f32(C.byref(d), L.current_stream()), "egp_minibatch_plan_f32")
+    return out, mb_n_exp
+
+
+def ppo_losses_mb(pred, returns, mean, actions, log_std, adv, fixed_logp, exps, n_exp, clip_eps, d_pred=None, d_mean=None,
+                  want_d_log_std=False, losses_out=None):
+    """-> (losses float64[2] on the device, d_pred (n, 1), d_mean (n, A), d_log_std (1, A) or None) of one window of n rows.
+    `mean` covers EVERY row of the window; `exps` (n,) marks the exploration rows, `n_exp` is the int32 device tensor of one
+    element that holds their number (the window's entry of minibatch_plan's mb_n_exp). No host read, no data-dependent shape."""
+    lib = L.load()
+    n, A = mean.shape[0], mean.shape[1]
+    if not 1 <= n <= L.PPO_LOSS_MB_MAX_ROWS:
+        raise ValueError("a window has 1 .. %d rows, got %d" % (L.PPO_LOSS_MB_MAX_ROWS, n))
+    dev = pred.device
+    pred1, ret1, adv1, fix1, exp1 = (_f32_vector(k, t.reshape(-1), n) for k, t in
+                                     (("pred", pred), ("returns", returns), ("adv", adv), ("fixed_logp", fixed_logp), ("exps", exps)))
+    _f32_rows("mean", mean, n)
+    _f32_rows("actions", actions, n, A)
+    if not (log_std.is_cuda and log_std.dtype == torch.float32 and log_std.numel() == A and A <= 256):
+        raise ValueError("log_std must hold act_dim <= 256 float32 values on the HIP device")
+    if not (n_exp.is_cuda and n_exp.dtype == torch.int32 and n_exp.numel() == 1):
+        raise ValueError("n_exp must be an int32 HIP tensor of one element")
+    ls = log_std.reshape(-1).contiguous()
+    if d_pred is None:
+        d_pred = torch.empty(n, 1, dtype=torch.float32, device=dev)
+    if d_mean is None:
+        d_mean = torch.empty(n, A, dtype=torch.float32, device=dev)
+    _f32_vector("d_pred", d_pred.reshape(-1), n)
+    _f32_rows("d_mean", d_mean, n, A)
+    d_ls = torch.empty(1, A, dtype=torch.float32, device=dev) if want_d_log_std else None
+    losses = losses_out if losses_out is not None else torch.empty(2, dtype=torch.float64, device=dev)
+    if not (losses.is_cuda and losses.dtype == torch.float64 and losses.is_contiguous() and losses.numel() == 2):
+        raise ValueError("losses_out must be a contiguous float64 HIP tensor of 2 elements")
+    d = L.PpoLossMbDesc()
+    d.n, d.act_dim = n, A
+    d.pred, d.returns = pred1.data_ptr(), ret1.data_ptr()
+    d.mean, d.ld_mean = mean.data_ptr(), mean.stride(0) if n > 1 else A
+    d.actions, d.ld_act = actions.data_ptr(), actions.stride(0) if n > 1 else A
+    d.log_std = ls.data_ptr()
+    d.adv, d.fixed_logp, d.exps = adv1.data_ptr(), fix1.data_ptr(), exp1.data_ptr()
+    d.n_exp = n_exp.data_ptr()
+    d.clip_eps = float(clip_eps)
+    d.d_pred = d_pred.data_ptr()
+    d.d_mean, d.ld_dmean = d_mean.data_ptr(), d_mean.stride(0) if n > 1 else A
+    d.d_log_std = d_ls.data_ptr() if d_ls is not None else None
+    d.losses = losses.data_ptr()
+    L.check(lib.egp_ppo_loss_mb_f32(C.byref(d), L.current_stream()), "egp_ppo_loss_mb_f32")
     return losses, d_pred, d_mean, d_ls
 
 

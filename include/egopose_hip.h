@@ -332,6 +332,51 @@ typedef struct egp_ppo_loss_desc {
 int64_t egp_ppo_loss_workspace_bytes(int32_t n, int32_t n_pol, int32_t act_dim);
 int egp_ppo_loss_f32(const egp_ppo_loss_desc *desc, void *stream);
 
+/* Mini-batch PPO (agents/agent_ppo.py:24-44): every epoch shuffles the batch and steps on windows of opt_batch_size rows.
+ *
+ * egp_minibatch_plan_f32 -- one launch per epoch: the six float32 columns of the update gathered through the epoch's
+ * permutation into caller-owned contiguous buffers (out row r = source row perm[r]; pure moves, 16 bytes at a time when
+ * state_dim / act_dim is a multiple of 4 and the row bases are 16-byte aligned), and mb_n_exp[i] = number of rows with exps != 0
+ * in window i = [i * batch, min((i + 1) * batch, n)) of the permuted batch (int32, ceil(n / batch) entries, every one written:
+ * integer counts, exact and order-independent). ld_states / ld_act: source row strides in elements; the destinations are
+ * dense. perm must be a permutation of 0 .. n-1 (an entry outside that range is skipped, its row left unwritten). */
+struct egp_minibatch_plan_desc {
+    int32_t n, state_dim, act_dim, batch;
+    const int64_t *perm;
+    const float *states; int64_t ld_states;
+    const float *actions; int64_t ld_act;
+    const float *returns; const float *adv; const float *fixed_logp; const float *exps;
+    float *out_states; float *out_actions; float *out_returns; float *out_adv; float *out_fixed_logp; float *out_exps;
+    int32_t *mb_n_exp;
+};
+typedef struct egp_minibatch_plan_desc egp_minibatch_plan_desc;
+int egp_minibatch_plan_f32(const egp_minibatch_plan_desc *desc, void *stream);
+
+/* egp_ppo_loss_mb_f32 -- both losses of ONE window (n rows, contiguous in the plan's buffers) in one launch whose shapes do not
+ * depend on the data: `mean` is the policy head on EVERY row of the window; rows with exps == 0 get d_mean = 0 exactly and stay
+ * out of the surrogate's sums (policy and value parameters are disjoint, so the weight gradients are those of the reference's
+ * gathered exploration rows, agent_ppo.py:37-39). The surrogate's mean divides by *n_exp, the window's entry of mb_n_exp, read
+ * on the device; a window without exploration rows gives d_mean = d_log_std = 0 and losses[1] = NaN (torch's mean of nothing).
+ *     losses[0] = sum (pred - returns)^2 / n,  d_pred = 2 (pred - returns) / n,  losses[1] = -sum_{exps != 0} surr / *n_exp
+ * Per-row arithmetic is egp_ppo_loss_f32's (same device code); sums in float64, fixed order. d_log_std may be NULL. */
+#define EGP_PPO_LOSS_MB_MAX_ROWS 16384
+struct egp_ppo_loss_mb_desc {
+    int32_t n, act_dim;
+    const float *pred; const float *returns;
+    const float *mean; int64_t ld_mean;
+    const float *actions; int64_t ld_act;
+    const float *log_std;
+    const float *adv; const float *fixed_logp; const float *exps;
+    const int32_t *n_exp;
+    double clip_eps;
+    float *d_pred;
+    float *d_mean; int64_t ld_dmean;
+    float *d_log_std;
+    double *losses;
+};
+typedef struct egp_ppo_loss_mb_desc egp_ppo_loss_mb_desc;
+int egp_ppo_loss_mb_f32(const egp_ppo_loss_mb_desc *desc, void *stream);
+
 /* egp_adam_step_* -- gradient-norm clip + Adam over FLAT parameter buffers: clip_policy_grad (agents/agent_ppo.py:53-56,
  * torch.nn.utils.clip_grad_norm_: coef = min(1, max_norm / (||g||_2 + 1e-6))) followed by optimizer_value.step() /
  * optimizer_policy.step() (agent_ppo.py:24-30; torch.optim.Adam, no amsgrad) in two launches for all parameter sets.
