@@ -245,6 +245,8 @@ SIGNATURES = {
     "egp_mlp_pack_floats": (C.c_int64, [_i32, _i32]),
     "egp_mlp_pack_f32": (C.c_int, [vp, C.c_int64, _i32, _i32, vp, vp]),
     "egp_policy_gaussian_f32": (C.c_int, [vp, C.c_int64, _i32, vp, vp, _i32, _i32, C.POINTER(MlpLayer), _i32, _i32, vp, vp, vp, vp, vp]),
+    "egp_policy_forecast_f32": (C.c_int, [vp, C.c_int64, _i32, vp, vp, _i32, C.POINTER(MlpLayer), vp, vp, C.c_int64, _i32,
+                                          C.POINTER(MlpLayer), _i32, _i32, vp, vp, vp, vp, vp]),
     "egp_policy_gaussian_staged_f32": (C.c_int, [vp, C.c_int64, _i32, vp, vp, _i32, _i32, C.POINTER(MlpLayer), _i32, _i32, vp, vp, vp, vp, vp, vp,
                                                  C.c_int64, vp]),
     "egp_physics_register": (C.c_int, [C.POINTER(PhysicsVtable), _i32, C.POINTER(vp)]),

@@ -16,6 +16,10 @@
 // The weights of the next pass are requested BEFORE the partial sums are written and reduced (they do not depend on the
 // activations), and the first layer's before the input rows are gathered: the dependent global round trips of a tick
 // (context-row index -> context row, tile statistics -> filtered observation) overlap the weight stream.
+//
+// ego_forecast (egp_policy_forecast_f32, forecast_body below): the state first goes through one step of the state LSTM cell
+// (models/rnn.py:29-36, models/video_forecast_net.py:88-93) -- its gate pre-activations are one more layer of the same passes, its
+// epilogue the gates -- and x = [context row | h']; h / c are updated in place.
 #include <hip/hip_runtime.h>
 
 #include <stdint.h>
@@ -518,6 +522,222 @@ __global__ __launch_bounds__(512) void k_policy_gaussian_w8(POL_KERNEL_ARGS) {
     policy_body<R, 8, PF, FILTER>(POL_KERNEL_PASS);
 }
 
+// ---------------------------------------------------------------------------------------------------------------- forecast
+// The ego_forecast policy step (egp_policy_forecast_f32): the state goes through one step of the state LSTM
+// (models/rnn.py:29-36 in step mode, as models/video_forecast_net.py:88-93 calls it) before it joins the video context:
+//   pre = [W_ih | W_hh] [s | h] + (b_ih + b_hh);  c' = sigmoid(f) c + sigmoid(i) tanh(g);  h' = sigmoid(o) tanh(c');  x = [ctx | h']
+// The gate pre-activations are layer 0 of the same pass machinery (L.wp[0]: the cell, input [s | h] in `cur`, 4 Hs outputs with
+// the four gates of a unit in adjacent columns 4 u .. 4 u + 3, so a pass of POL_GC x 64 columns holds 80 whole units and the gate
+// epilogue is one 16-byte LDS read per wave partial); its epilogue writes h' behind the context columns that the prologue has
+// gathered into `nxt` -- the MLP's input -- and h' / c' back to the caller's rows. Layers 1 .. L.n - 1 are the MLP and the head.
+// In place: a workgroup's h / c rows are read in the prologue (into LDS) and written in layer 0's epilogue, behind barriers;
+// no workgroup touches another's rows, and rows >= n are neither read nor written.
+template <int R, int NW, int PF>
+__device__ __forceinline__ void forecast_body(const float *__restrict__ ctx_rows, long ctx_row_stride, int ctx_dim,
+                                              const long long *__restrict__ t_idx, const double *__restrict__ state, int state_dim,
+                                              float *h_io, float *c_io, long hc_stride, int hs, int n,
+                                              const PolLayers &L, int act_kind, int xs, const float *__restrict__ log_std,
+                                              const float *__restrict__ noise, double *__restrict__ action, float *__restrict__ mean_out) {
+    constexpr int T = NW * 64;
+    constexpr int PS = POL_GC * 64 + 4;
+    extern __shared__ __attribute__((aligned(16))) float s_f[];     // cur[R][xs] | nxt[R][xs] | part[NW][R][PS] | small operands | c[R][hs]
+    float *cur = s_f, *nxt = s_f + R * xs, *part = s_f + 2 * R * xs;
+    float *s_bias = part + NW * R * PS;
+    const int out_last = L.out_dim[L.n - 1];
+    const int osd4 = (out_last + 3) & ~3;
+    float *s_sd = s_bias + L.sum_out4, *s_noise = s_sd + osd4, *s_c = s_noise + R * osd4;
+    const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+    const int r0 = blockIdx.x * R;
+    const int in_c = state_dim + hs, in_cp = (in_c + 3) & ~3;        // the cell's input [s | h]
+    const int in_m = ctx_dim + hs, in_mp = (in_m + 3) & ~3;          // the MLP's input [ctx | h']
+
+    // the rows' context-row indices first: index -> context row is the longest dependent chain of the prologue
+    long tix[R];
+#pragma unroll
+    for (int r = 0; r < R; ++r) tix[r] = ctx_dim > 0 ? (long)t_idx[min(r0 + r, n - 1)] : 0;
+    // L2 warm-up over the packed weights (cell + MLP in one range), as in policy_body
+    constexpr int POL_WARM = 8;
+    float warm[POL_WARM];
+    {
+        const int per_xcd = (gridDim.x + 7) >> 3, me = blockIdx.x >> 3;
+        const int lo = (int)((long)L.warm_lines * me / per_xcd), hi = (int)((long)L.warm_lines * (me + 1) / per_xcd);
+#pragma unroll
+        for (int u = 0; u < POL_WARM; ++u) {
+            const int i = min(lo + tid + u * T, max(hi - 1, 0));
+            warm[u] = L.wp[0][(long)i * 32];
+        }
+    }
+    // the cell's own first blocks
+    PolStage<PF> st;
+    int nkq = (L.in_dim[0] + 3) >> 2;
+    int kq0 = wave * nkq / NW, kq1 = (wave + 1) * nkq / NW;
+    pol_preload<PF>(st, L.wp[0], nkq, 0, min((L.out_dim[0] + 63) >> 6, POL_GC), kq0, max(kq1, kq0 + 1), lane);
+    // inputs: cur = [s | h | 0], nxt = [ctx | (h' later) | 0], s_c = c; rows >= n are zeros
+    for (int k = tid; k < in_cp; k += T) {
+#pragma unroll
+        for (int r = 0; r < R; ++r) {
+            const int row = r0 + r;
+            float v = 0.0f;
+            if (row < n && k < in_c)
+                v = k < state_dim ? (float)state[(long)row * state_dim + k] : h_io[(long)row * hc_stride + (k - state_dim)];
+            cur[r * xs + k] = v;
+        }
+    }
+    for (int k = tid; k < hs; k += T) {
+#pragma unroll
+        for (int r = 0; r < R; ++r) s_c[r * hs + k] = r0 + r < n ? c_io[(long)(r0 + r) * hc_stride + k] : 0.0f;
+    }
+    for (int k = tid; k < in_mp; k += T) {
+#pragma unroll
+        for (int r = 0; r < R; ++r) {
+            const int row = r0 + r;
+            nxt[r * xs + k] = (row < n && k < ctx_dim) ? ctx_rows[(long)row * ctx_row_stride + tix[r] * ctx_dim + k] : 0.0f;
+        }
+    }
+    // the small operands of the epilogues: every layer's bias | exp(log_std) | the rows' noise
+    {
+        int off = 0;
+        for (int l = 0; l < L.n; ++l) {
+            const int o = L.out_dim[l];
+            for (int j = tid; j < o; j += T) s_bias[off + j] = L.bias[l][j];
+            off += (o + 3) & ~3;
+        }
+        if (noise) {
+            for (int j = tid; j < out_last; j += T) s_sd[j] = expf(log_std[j]);
+            for (int e = tid; e < R * out_last; e += T) {
+                const int r = e / out_last;
+                s_noise[e] = r0 + r < n ? noise[(long)(r0 + r) * out_last + (e - r * out_last)] : 0.0f;
+            }
+        }
+    }
+    __syncthreads();
+    {
+        float sink = 0.0f;
+#pragma unroll
+        for (int u = 0; u < POL_WARM; ++u) sink += warm[u];
+        asm volatile("" ::"v"(sink));
+    }
+
+    int bias_off = 0;
+    for (int l = 0; l < L.n; ++l) {
+        const int out = L.out_dim[l];
+        const int ng_all = (out + 63) >> 6;
+        const bool last = l == L.n - 1, cell = l == 0;
+        const float *wl = L.wp[l];
+        for (int g0 = 0; g0 < ng_all; g0 += POL_GC) {
+            const int ng = min(POL_GC, ng_all - g0);
+            f32x4 acc[POL_GC][R / 4];
+#pragma unroll
+            for (int g = 0; g < POL_GC; ++g)
+#pragma unroll
+                for (int h = 0; h < R / 4; ++h) acc[g][h] = f32x4{0.f, 0.f, 0.f, 0.f};
+            if (kq1 > kq0) {
+                switch (ng) {
+                    case 1: pol_pass<1, R, PF>(st, wl, nkq, g0, kq0, kq1, cur, xs, lane, acc); break;
+                    case 2: pol_pass<2, R, PF>(st, wl, nkq, g0, kq0, kq1, cur, xs, lane, acc); break;
+                    case 3: pol_pass<3, R, PF>(st, wl, nkq, g0, kq0, kq1, cur, xs, lane, acc); break;
+                    case 4: pol_pass<4, R, PF>(st, wl, nkq, g0, kq0, kq1, cur, xs, lane, acc); break;
+                    default: pol_pass<5, R, PF>(st, wl, nkq, g0, kq0, kq1, cur, xs, lane, acc); break;
+                }
+            }
+            // the next pass's first blocks: same layer's next column chunk, or the next layer
+            {
+                int nl = l, ng0 = g0 + POL_GC;
+                if (ng0 >= ng_all) { nl = l + 1; ng0 = 0; }
+                if (nl < L.n) {
+                    const int nkq_n = (L.in_dim[nl] + 3) >> 2;
+                    const int a = wave * nkq_n / NW, b = (wave + 1) * nkq_n / NW;
+                    const int ng_n = min(POL_GC, ((L.out_dim[nl] + 63) >> 6) - ng0);
+                    pol_preload<PF>(st, L.wp[nl], nkq_n, ng0, ng_n, a, max(b, a + 1), lane);
+                }
+            }
+            // partial sums -> LDS: register i of lane 4 b + j = out[row 4 h + j][column 64 g + 4 b + i]
+#pragma unroll
+            for (int g = 0; g < POL_GC; ++g)
+                if (g < ng) {
+#pragma unroll
+                    for (int h = 0; h < R / 4; ++h)
+                        *reinterpret_cast<f32x4 *>(part + ((wave * R) + 4 * h + (lane & 3)) * PS + 64 * g + (lane & ~3)) = acc[g][h];
+                }
+            __syncthreads();
+            const int c_base = 64 * g0;
+            const int cw = min(out - c_base, POL_GC * 64);               // real columns of this chunk
+            if (cell) {
+                // gate epilogue: one thread per unit, columns 4 u .. 4 u + 3 = (i, f, g, o); fixed summation order
+                for (int j = tid; j < (cw >> 2); j += T) {
+                    const int u = (c_base >> 2) + j;
+                    const f32x4 bv = *reinterpret_cast<const f32x4 *>(s_bias + 4 * u);
+                    f32x4 v[R];
+#pragma unroll
+                    for (int r = 0; r < R; ++r) v[r] = bv;
+#pragma unroll
+                    for (int w = 0; w < NW; ++w)
+#pragma unroll
+                        for (int r = 0; r < R; ++r) v[r] += *reinterpret_cast<const f32x4 *>(part + (w * R + r) * PS + 4 * j);
+#pragma unroll
+                    for (int r = 0; r < R; ++r) {
+                        const float gi = pol_act(v[r][0], 2), gf = pol_act(v[r][1], 2), gg = tanhf(v[r][2]), go = pol_act(v[r][3], 2);
+                        const float cn = gf * s_c[r * hs + u] + gi * gg;
+                        const float hn = go * tanhf(cn);
+                        nxt[r * xs + ctx_dim + u] = hn;
+                        const int row = r0 + r;
+                        if (row < n) {
+                            h_io[(long)row * hc_stride + u] = hn;
+                            c_io[(long)row * hc_stride + u] = cn;
+                        }
+                    }
+                }
+            } else {
+                const int cw4 = last ? cw : min((cw + 3) & ~3, ng * 64);      // hidden layers: the pad columns of the last quad become zeros
+                for (int c = tid; c < cw4; c += T) {
+                    const int col = c_base + c;
+                    const bool real = c < cw;
+                    const float bv = real ? s_bias[bias_off + col] : 0.0f;
+                    float v[R];
+#pragma unroll
+                    for (int r = 0; r < R; ++r) v[r] = bv;
+#pragma unroll
+                    for (int w = 0; w < NW; ++w)                         // fixed order: deterministic
+#pragma unroll
+                        for (int r = 0; r < R; ++r) v[r] += part[(w * R + r) * PS + c];
+                    if (!last) {
+#pragma unroll
+                        for (int r = 0; r < R; ++r) nxt[r * xs + col] = real ? pol_act(v[r], act_kind) : 0.0f;
+                    } else {
+                        const float sd = noise ? s_sd[col] : 0.0f;
+#pragma unroll
+                        for (int r = 0; r < R; ++r) {
+                            const int row = r0 + r;
+                            if (row >= n) continue;
+                            const float a = noise ? fmaf(sd, s_noise[r * out + col], v[r]) : v[r];
+                            action[(long)row * out + col] = (double)a;
+                            if (mean_out) mean_out[(long)row * out + col] = v[r];
+                        }
+                    }
+                }
+            }
+            __syncthreads();
+        }
+        bias_off += (out + 3) & ~3;
+        if (!last) {
+            nkq = (L.in_dim[l + 1] + 3) >> 2;
+            kq0 = wave * nkq / NW; kq1 = (wave + 1) * nkq / NW;
+            float *t = cur; cur = nxt; nxt = t;
+        }
+    }
+}
+
+template <int R, int PF>
+__global__ __launch_bounds__(256) void k_policy_forecast_w4(const float *__restrict__ ctx_rows, long ctx_row_stride, int ctx_dim,
+                                                            const long long *__restrict__ t_idx, const double *__restrict__ state,
+                                                            int state_dim, float *h_io, float *c_io, long hc_stride, int hs, int n,
+                                                            PolLayers L, int act_kind, int xs, const float *__restrict__ log_std,
+                                                            const float *__restrict__ noise, double *__restrict__ action,
+                                                            float *__restrict__ mean_out) {
+    forecast_body<R, 4, PF>(ctx_rows, ctx_row_stride, ctx_dim, t_idx, state, state_dim, h_io, c_io, hc_stride, hs, n, L, act_kind, xs,
+                            log_std, noise, action, mean_out);
+}
+
 }  // namespace
 
 #ifdef EGP_POLICY_TRACE
@@ -627,6 +847,62 @@ extern "C" int egp_policy_gaussian_f32(const float *ctx_rows, int64_t ctx_row_st
                                        double *action, float *mean_out, void *stream) {
     return policy_launch(ctx_rows, ctx_row_stride, ctx_dim, t_idx, state, state_dim, n, layers, n_layers, activation, log_std, noise, action,
                          mean_out, nullptr, nullptr, 0, stream);
+}
+
+// The ego_forecast policy step: one step of the state LSTM cell (models/rnn.py:29-36, models/video_forecast_net.py:88-93), then
+// [ctx | h'] -> MLP -> Gaussian head as above, h' / c' written back in place. `cell` is the gate layer in egp_mlp_layer form
+// (include/egopose_hip.h gives the column order); see forecast_body.
+extern "C" int egp_policy_forecast_f32(const float *ctx_rows, int64_t ctx_row_stride, int32_t ctx_dim, const int64_t *t_idx,
+                                       const double *state, int32_t state_dim, const egp_mlp_layer *cell, float *h, float *c,
+                                       int64_t hc_row_stride, int32_t n, const egp_mlp_layer *layers, int32_t n_layers,
+                                       int32_t activation, const float *log_std, const float *noise, double *action, float *mean_out,
+                                       void *stream) {
+    EGP_REQUIRE(n >= 0, "n < 0");
+    if (n == 0) return EGP_OK;
+    EGP_REQUIRE(state && cell && h && c && h != c && layers && action, "NULL pointer (or h == c)");
+    EGP_REQUIRE(ctx_dim >= 0 && (ctx_dim == 0 || (ctx_rows && t_idx)), "bad context");
+    EGP_REQUIRE(!noise || log_std, "noise needs log_std");
+    EGP_REQUIRE(n_layers >= 1 && n_layers + 1 <= POL_MAX_LAYERS, "1..7 layers (hidden layers + output layer) behind the cell");
+    EGP_REQUIRE(activation >= 0 && activation <= 2, "activation: 0 tanh, 1 relu, 2 sigmoid");
+    EGP_REQUIRE(cell->wt && cell->bias && ((uintptr_t)cell->wt & 15) == 0, "cell: NULL or misaligned packed weights");
+    EGP_REQUIRE(cell->out_dim >= 4 && cell->out_dim % 4 == 0 && cell->out_dim <= 2048, "cell: out_dim = 4 x hidden size, at most 2048");
+    const int hs = cell->out_dim / 4;
+    EGP_REQUIRE(state_dim >= 1 && cell->in_dim == state_dim + hs && cell->in_dim <= 2048, "cell: in_dim = state_dim + hidden size, at most 2048");
+    EGP_REQUIRE(hc_row_stride >= hs, "h / c row stride below the hidden size");
+    PolLayers L;
+    L.wp[0] = cell->wt; L.bias[0] = cell->bias; L.in_dim[0] = cell->in_dim; L.out_dim[0] = cell->out_dim;
+    int kmax = cell->in_dim > ctx_dim + hs ? cell->in_dim : ctx_dim + hs, prev = ctx_dim + hs;
+    L.sum_out4 = cell->out_dim;
+    long lines = egp_mlp_pack_floats(cell->in_dim, cell->out_dim) / 32;
+    bool contiguous = true;
+    const float *follow = cell->wt + egp_mlp_pack_floats(cell->in_dim, cell->out_dim);
+    for (int l = 0; l < n_layers; ++l) {
+        EGP_REQUIRE(layers[l].wt && layers[l].bias, "NULL layer");
+        EGP_REQUIRE(((uintptr_t)layers[l].wt & 15) == 0, "packed weights must be 16-byte aligned");
+        EGP_REQUIRE(layers[l].in_dim == prev && layers[l].out_dim > 0, "layer dims do not chain (first layer: ctx_dim + hidden size)");
+        L.wp[l + 1] = layers[l].wt; L.bias[l + 1] = layers[l].bias;
+        L.in_dim[l + 1] = layers[l].in_dim; L.out_dim[l + 1] = layers[l].out_dim;
+        prev = layers[l].out_dim;
+        if (prev > kmax) kmax = prev;
+        L.sum_out4 += (prev + 3) & ~3;
+        if (layers[l].wt != follow) contiguous = false;
+        follow = layers[l].wt + egp_mlp_pack_floats(layers[l].in_dim, layers[l].out_dim);
+        lines += egp_mlp_pack_floats(layers[l].in_dim, layers[l].out_dim) / 32;
+    }
+    L.n = n_layers + 1;
+    EGP_REQUIRE(kmax <= 2048, "layer wider than 2048");
+    L.warm_lines = contiguous && lines < (1l << 30) ? (int)lines : 0;
+    constexpr int R = 4, NW = 4, PF = 2;              // the tile policy_tile() chose for the same passes
+    const int xs = ((kmax + 31) & ~31) + 4;
+    const size_t out4 = (size_t)((prev + 3) & ~3);
+    const size_t lds = ((size_t)2 * R * xs + (size_t)NW * R * (POL_GC * 64 + 4) + (size_t)L.sum_out4 + out4 + R * out4 + (size_t)R * hs) * sizeof(float);
+    EGP_REQUIRE(lds <= 150 * 1024, "layers too wide for the LDS tile");
+    k_policy_forecast_w4<R, PF><<<dim3((n + R - 1) / R), dim3(NW * 64), lds, (hipStream_t)stream>>>(
+        ctx_rows, (long)ctx_row_stride, ctx_dim, (const long long *)t_idx, state, state_dim, h, c, (long)hc_row_stride, hs, n, L, activation, xs,
+        log_std, noise, action, mean_out);
+    hipError_t e = hipGetLastError();
+    if (e != hipSuccess) { egp::set_error("k_policy_forecast launch failed: %s", hipGetErrorString(e)); return EGP_E_HIP; }
+    return EGP_OK;
 }
 
 extern "C" int egp_policy_gaussian_staged_f32(const float *ctx_rows, int64_t ctx_row_stride, int32_t ctx_dim, const int64_t *t_idx,

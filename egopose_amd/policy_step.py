@@ -2,12 +2,15 @@
 and the Gaussian head of the reference's `policy_net.select_action` (core/agent.py:38-44, models/policy_gaussian.py:
 19-27, models/mlp.py:5-25) for a whole env group in one launch. The module keeps transposed float32 copies of the
 weights, packed for the kernel's matrix-core tiles, in persistent buffers (`refresh()` re-reads the live parameters,
-addresses stay fixed for hipGraphs)."""
+addresses stay fixed for hipGraphs). `FusedForecastPolicy` is the ego_forecast form (`egp_policy_forecast_f32`): one step
+of VideoForecastNet's state LSTM cell (models/video_forecast_net.py:88-93, models/rnn.py:29-36) in front of the same MLP,
+the cell's h / c updated in place."""
 from __future__ import annotations
 
 import ctypes as C
 
 import torch
+from torch import nn
 
 from . import _lib as L
 
@@ -23,9 +26,23 @@ def supported(policy_net) -> bool:
             and max(l.out_features for l in net.affine_layers) <= 2048)
 
 
+def supported_forecast(policy_net, vs_net) -> bool:
+    """True when `supported(policy_net)` and `vs_net` is a VideoForecastNet whose state net is one float32 nn.LSTMCell
+    (with biases, one direction) inside the kernel's limits. (`s_net_type == 'id'` passes the state through unchanged:
+    that is FusedGaussianPolicy's input already.)"""
+    s_net = getattr(vs_net, "s_net", None)
+    cell = getattr(s_net, "rnn_f", None)
+    if not (supported(policy_net) and getattr(vs_net, "s_net_type", None) == "lstm" and isinstance(cell, nn.LSTMCell)
+            and cell.bias and not getattr(s_net, "bi_dir", False) and cell.weight_ih.dtype == torch.float32):
+        return False
+    S, Hs = cell.input_size, cell.hidden_size
+    return (S >= 1 and Hs >= 1 and 4 * Hs <= 2048 and S + Hs <= 2048 and len(policy_net.net.affine_layers) + 1 <= 7
+            and policy_net.net.affine_layers[0].in_features == vs_net.v_hdim + Hs and vs_net.v_hdim + Hs <= 2048)
+
+
 class FusedGaussianPolicy:
 
-    def __init__(self, policy_net, device):
+    def __init__(self, policy_net, device, _front=()):
         if not supported(policy_net):
             raise ValueError("policy net is not a float32 PolicyGaussian over an MLP")
         self.lib = L.load()
@@ -34,9 +51,12 @@ class FusedGaussianPolicy:
         self.act = _ACT_CODE[policy_net.net.activation]
         # the kernel's packed weight form (include/egopose_hip.h: egp_mlp_layer): one 64-column x 4-feature block per wave load
         # (ONE buffer, layer after layer: the kernel's L2 warm-up walks it as a single range)
-        sizes = [int(self.lib.egp_mlp_pack_floats(l.in_features, l.out_features)) for l in self.layers]
+        # (`_front`: (in, out) of packed layers a subclass keeps in front of the MLP's, in the same allocation)
+        dims = list(_front) + [(l.in_features, l.out_features) for l in self.layers]
+        sizes = [int(self.lib.egp_mlp_pack_floats(i, o)) for i, o in dims]
         self.wt_all = torch.zeros(sum(sizes), dtype=torch.float32, device=device)
-        self.wt = list(torch.split(self.wt_all, sizes))
+        parts = list(torch.split(self.wt_all, sizes))
+        self.front_wt, self.wt = parts[:len(_front)], parts[len(_front):]
         self.bias = [torch.empty(l.out_features, dtype=torch.float32, device=device) for l in self.layers]
         self.log_std = torch.empty(self.layers[-1].out_features, dtype=torch.float32, device=device)
         self.desc = (L.MlpLayer * len(self.layers))()
@@ -93,3 +113,57 @@ class FusedGaussianPolicy:
                                                         p(action_out), p(mean_out), None, None, 0, L.current_stream()),
                 "egp_policy_gaussian_filter_f32")
         return action_out
+
+
+class FusedForecastPolicy(FusedGaussianPolicy):
+    """The ego_forecast tick in one launch (`egp_policy_forecast_f32`): state LSTM cell step, [context | h'] -> MLP -> Gaussian
+    head, h / c written back in place. The cell's packed gate layer sits in front of the MLP's in `wt_all`."""
+
+    def __init__(self, policy_net, vs_net, device):
+        if not supported_forecast(policy_net, vs_net):
+            raise ValueError("not a float32 PolicyGaussian over an MLP behind a VideoForecastNet with an LSTMCell state net")
+        self.cell = vs_net.s_net.rnn_f
+        self.S, self.Hs = self.cell.input_size, self.cell.hidden_size
+        self.cell_bias = torch.empty(4 * self.Hs, dtype=torch.float32, device=device)
+        super().__init__(policy_net, device, _front=[(self.S + self.Hs, 4 * self.Hs)])
+        self.cell_desc = (L.MlpLayer * 1)()
+        self.cell_desc[0].wt = self.front_wt[0].data_ptr()
+        self.cell_desc[0].bias = self.cell_bias.data_ptr()
+        self.cell_desc[0].in_dim, self.cell_desc[0].out_dim = self.S + self.Hs, 4 * self.Hs
+
+    @torch.no_grad()
+    def refresh(self):
+        """Pack the live parameters of the cell and of the MLP into the kernel's buffers."""
+        super().refresh()
+        c, S, Hs = self.cell, self.S, self.Hs
+        # the kernel's gate layer (include/egopose_hip.h): row 4 u + g = [W_ih[g Hs + u] | W_hh[g Hs + u]], bias b_ih + b_hh alike
+        w = torch.cat((c.weight_ih, c.weight_hh), 1).view(4, Hs, S + Hs).transpose(0, 1).reshape(4 * Hs, S + Hs).contiguous()
+        L.check(self.lib.egp_mlp_pack_f32(C.c_void_p(w.data_ptr()), S + Hs, S + Hs, 4 * Hs, C.c_void_p(self.front_wt[0].data_ptr()),
+                                          L.current_stream()), "egp_mlp_pack_f32")
+        self.cell_bias.copy_((c.bias_ih + c.bias_hh).view(4, Hs).t().reshape(-1))
+
+    def __call__(self, ctx_rows, t_idx, state, h, c, action_out, noise=None, mean_out=None):
+        """ctx_rows: float32 [n][T][H], t_idx: int64 [n], state: float64 [n][S], h / c: float32 [n][Hs] (row slices of the
+        per-slot buffers; updated in place), noise: float32 [n][nu] or None (mean action), action_out: float64 [n][nu]."""
+        n, T, H = ctx_rows.shape
+        if state.shape[1] != self.S or H + self.Hs != self.in_dim:
+            raise ValueError("state dim %d / context dim %d do not fit the cell (%d -> %d) and the policy input %d"
+                             % (state.shape[1], H, self.S, self.Hs, self.in_dim))
+        assert ctx_rows.dtype == torch.float32 and ctx_rows.stride(2) == 1 and ctx_rows.stride(1) == H
+        assert t_idx.dtype == torch.int64 and t_idx.is_contiguous() and state.dtype == torch.float64 and state.is_contiguous()
+        for t in (h, c):
+            assert t.dtype == torch.float32 and t.shape == (n, self.Hs) and t.stride(1) == 1 and t.stride(0) == h.stride(0) >= self.Hs
+        assert h.data_ptr() != c.data_ptr()
+        assert action_out.dtype == torch.float64 and action_out.is_contiguous() and action_out.shape == (n, self.nu)
+        if noise is not None:
+            assert noise.dtype == torch.float32 and noise.is_contiguous() and noise.shape == (n, self.nu)
+        if mean_out is not None:
+            assert mean_out.dtype == torch.float32 and mean_out.is_contiguous() and mean_out.shape == (n, self.nu)
+        p = lambda t: C.c_void_p(t.data_ptr()) if t is not None else C.c_void_p(0)
+        L.check(self.lib.egp_policy_forecast_f32(p(ctx_rows), int(ctx_rows.stride(0)), H, p(t_idx), p(state), self.S, self.cell_desc,
+                                                 p(h), p(c), int(h.stride(0)), n, self.desc, len(self.layers), self.act, p(self.log_std),
+                                                 p(noise), p(action_out), p(mean_out), L.current_stream()), "egp_policy_forecast_f32")
+        return action_out
+
+    def with_filter(self, *args, **kwargs):
+        raise NotImplementedError("the forecast step has no filter-fused form")

@@ -280,8 +280,12 @@ class LockstepRollout:
         a, b = self.groups[g]
         # the exploration noise of the tick sits in self._g_noise[g]: the caller copies it there from the rollout's noise
         # block (drawn once per rollout for every tick and slot, `sample`), so the body itself draws nothing
-        if self._fused is not None:              # one HIP launch: concat + MLP + Gaussian head
-            self._fused(self.v_out[a:b], self._g_tidx[g], self._g_state[g], self._g_act[g], noise=self._g_noise[g])
+        if self._fused is not None:              # one HIP launch: (forecast: state LSTM cell step +) concat + MLP + Gaussian head
+            if self._s_hc is not None:
+                self._fused(self.v_out[a:b], self._g_tidx[g], self._g_state[g], self._s_hc[0][a:b], self._s_hc[1][a:b], self._g_act[g],
+                            noise=self._g_noise[g])
+            else:
+                self._fused(self.v_out[a:b], self._g_tidx[g], self._g_state[g], self._g_act[g], noise=self._g_noise[g])
             return
         mean, std = self._mean_std(self._policy_input(g, self._g_tidx[g], self._g_state[g]))
         self._g_act[g].copy_(torch.addcmul(mean, std, self._g_noise[g].to(mean.dtype)))
@@ -310,8 +314,12 @@ class LockstepRollout:
         self._g_act = [torch.zeros(b - a, self.ctx.nu, dtype=f64, device=dev) for a, b in self.groups]
         self._g_noise = [torch.zeros(b - a, self.ctx.nu, dtype=torch.float32, device=dev) for a, b in self.groups]
         self._fused = None
-        if self.use_fused and not self.forecast and ndt == torch.float32 and policy_step.supported(self.policy_net):
-            self._fused = policy_step.FusedGaussianPolicy(self.policy_net, dev)
+        if self.use_fused and ndt == torch.float32:
+            if self._s_hc is not None:           # forecast with a state LSTM: its cell step rides in the same launch
+                if policy_step.supported_forecast(self.policy_net, self.policy_vs_net):
+                    self._fused = policy_step.FusedForecastPolicy(self.policy_net, self.policy_vs_net, dev)
+            elif policy_step.supported(self.policy_net):      # (forecast with s_net_type 'id': the state goes in unchanged)
+                self._fused = policy_step.FusedGaussianPolicy(self.policy_net, dev)
         self._graph_key = key
         self._graphs = None
         if not self.use_graphs:
@@ -546,6 +554,11 @@ class LockstepRollout:
                 else:
                     self._policy_body(g)
                 rec["actions"][k, a:b] = self._g_act[g]
+            elif self.mean_action and self.forecast and self._fused is not None:
+                # evaluation: the fused step without a noise operand writes the mean (and steps the state LSTM)
+                hc = () if self._s_hc is None else (self._s_hc[0][a:b], self._s_hc[1][a:b])
+                self._fused(self.v_out[a:b], t_idx, rec["states"][k, a:b], *hc, rec["actions"][k, a:b], noise=None)
+                rec["exps"][k, a:b] = 0
             else:
                 mean, std = self._mean_std(self._policy_input(g, t_idx, rec["states"][k, a:b]))
                 if self.mean_action:

@@ -540,6 +540,25 @@ int egp_policy_gaussian_filter_f32(egp_ctx *ctx, const float *ctx_rows, int64_t 
                                    const egp_mlp_layer *layers, int32_t n_layers, int32_t activation, const float *log_std,
                                    const float *noise, double *action, float *mean_out, const void *stage_src, void *stage_dst,
                                    int64_t stage_bytes, void *stream);
+/* The ego_forecast policy step in one launch: the state goes through ONE STEP of the state LSTM before it joins the video
+ * context (VideoForecastNet in test mode, models/video_forecast_net.py:88-93, over the step-mode cell of models/rnn.py:29-36;
+ * torch's nn.LSTMCell, gate order i, f, g, o), then the MLP and the Gaussian head exactly as egp_policy_gaussian_f32:
+ *   s = float(state[r]);  pre = W_ih s + b_ih + W_hh h[r] + b_hh
+ *   c' = sigmoid(f) c[r] + sigmoid(i) tanh(g);  h' = sigmoid(o) tanh(c')
+ *   x[r] = [ctx_rows[r*ctx_row_stride + t_idx[r]*ctx_dim ...] | h'] -> layers -> action[r] (and mean_out[r])
+ * h and c (float32, row r at r * hc_row_stride, hidden size Hs = cell->out_dim / 4) are updated IN PLACE: a row is read before it
+ * is written, and only rows 0 .. n - 1 are touched -- the rollout passes row slices of its per-slot buffers.
+ * `cell` is the gate pre-activation as one more packed layer: in_dim = state_dim + Hs, out_dim = 4 Hs,
+ *   wt   = egp_mlp_pack_f32 of the [4 Hs][state_dim + Hs] matrix whose row 4 u + g is [W_ih[g Hs + u] | W_hh[g Hs + u]]
+ *          (the four gates g = 0..3 = i, f, g, o of unit u in adjacent columns), bias[4 u + g] = b_ih[g Hs + u] + b_hh[g Hs + u].
+ * `layers` (n_layers <= 7) are the MLP and the output layer; layers[0].in_dim = ctx_dim + Hs. Limits: state_dim >= 1, Hs >= 1,
+ * 4 Hs <= 2048, state_dim + Hs <= 2048, ctx_dim >= 0 (ctx_rows / t_idx may be NULL when it is 0). float32 accumulation in a
+ * fixed order (a row's result does not depend on n or on the row's position); expf / tanhf, no fast approximations. No
+ * allocation, no synchronisation: the launch can be captured in a hipGraph. n == 0 returns EGP_OK. */
+int egp_policy_forecast_f32(const float *ctx_rows, int64_t ctx_row_stride, int32_t ctx_dim, const int64_t *t_idx,
+                            const double *state, int32_t state_dim, const egp_mlp_layer *cell, float *h, float *c,
+                            int64_t hc_row_stride, int32_t n, const egp_mlp_layer *layers, int32_t n_layers, int32_t activation,
+                            const float *log_std, const float *noise, double *action, float *mean_out, void *stream);
 
 /* ----------------------------------------------------------------------------------------
  * Host physics boundary (replaces mujoco_py's MjSim inside HumanoidEnv: envs/common/mujoco_env.py:84-105,

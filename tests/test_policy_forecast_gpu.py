@@ -1,0 +1,295 @@
+"""The ego_forecast policy step in one launch (`egp_policy_forecast_f32`, policy_step.FusedForecastPolicy): one step of the
+state LSTM cell, [video context | h'] -> MLP -> Gaussian head, h / c updated in place -- against the reference's own
+vectors, against float64 torch at the configs' widths, and inside the lockstep rollout."""
+import copy
+import os
+
+import numpy as np
+import pytest
+import torch
+
+from conftest import load_golden
+
+pytestmark = pytest.mark.gpu
+
+DEV = "cuda"
+
+
+def _nets(S, Hs=128, H=128, hidden=(300, 200), nu=52, seed=11):
+    from egopose_amd.nets import MLP, PolicyGaussian, VideoForecastNet
+    torch.manual_seed(seed)
+    vs = VideoForecastNet(16, S, H, 4, "lstm", None, Hs, "lstm", False).to(DEV)
+    pol = PolicyGaussian(MLP(H + Hs, hidden, "relu"), nu, log_std=-0.7).to(DEV)
+    with torch.no_grad():
+        pol.action_mean.weight.mul_(10.0)
+        pol.action_mean.bias.normal_()
+        pol.action_log_std.normal_(std=0.3)
+    return vs, pol
+
+
+@pytest.fixture(scope="module")
+def cfg_nets():
+    """(vs net, policy, fused step) at the configs' widths, one per state width; built once."""
+    from egopose_amd import policy_step
+    out = {}
+    for S in (115, 116):
+        vs, pol = _nets(S)
+        assert policy_step.supported_forecast(pol, vs)
+        out[S] = (vs, pol, policy_step.FusedForecastPolicy(pol, vs, torch.device(DEV)))
+    return out
+
+
+def _inputs(n, S, Hs=128, H=128, T=1, nu=52, seed=5):
+    g = torch.Generator(device=DEV).manual_seed(seed)
+    r = lambda *s, **k: torch.randn(*s, generator=g, device=DEV, **k)
+    return dict(ctx=r(n, T, H), t_idx=torch.randint(0, T, (n,), generator=g, device=DEV), state=r(n, S, dtype=torch.float64) * 2,
+                h=torch.tanh(r(n, Hs)), c=r(n, Hs), noise=r(n, nu))
+
+
+def _step(fp, d, noise=True, n=None):
+    """One kernel step on (clones of) the inputs -> (h', c', action, mean)."""
+    n = d["state"].shape[0] if n is None else n
+    h, c = d["h"][:n].clone(), d["c"][:n].clone()
+    act = torch.empty(n, fp.nu, dtype=torch.float64, device=DEV)
+    mean = torch.empty(n, fp.nu, device=DEV)
+    fp(d["ctx"][:n], d["t_idx"][:n], d["state"][:n], h, c, act, noise=d["noise"][:n] if noise else None, mean_out=mean)
+    return h, c, act, mean
+
+
+# ------------------------------------------------------------------------------------------------ 1. reference vectors
+def test_forecast_step_matches_the_reference_state_lstm_vectors():
+    """forecast.npz: the REFERENCE stepped its state LSTM (S = 5, Hs = 7) over st_seq and wrote cat(v_out, h) to test_out.
+    Row 0 of an n = 3 call replays it: h after step k == test_out[k][8:] at 1e-5 (the float32 kernel family against reference
+    float64, as test_hip_parity's policy vectors). Rows 1, 2 get scaled inputs and are held against a float64 nn.LSTMCell; the
+    mean of all rows against the float64 policy over [v_out | h]."""
+    from egopose_amd.nets import MLP, PolicyGaussian, VideoForecastNet
+    from egopose_amd import policy_step
+    g = load_golden("forecast.npz")
+    cdim, sdim, vh, sh, margin = (int(v) for v in g["dims"])
+    assert (sdim, sh, vh) == (5, 7, 8)
+    vs = VideoForecastNet(cdim, sdim, vh, margin, "lstm", None, sh, "lstm", False)
+    vs.load_state_dict({k[3:]: torch.as_tensor(g[k], dtype=torch.float32) for k in g.files if k.startswith("sd_")})
+    vs = vs.to(DEV)
+    torch.manual_seed(2)
+    pol = PolicyGaussian(MLP(vh + sh, [10, 6], "relu"), 4, log_std=-1.0).to(DEV)
+    assert policy_step.supported_forecast(pol, vs)
+    fp = policy_step.FusedForecastPolicy(pol, vs, torch.device(DEV))
+    cell64, pol64 = copy.deepcopy(vs.s_net.rnn_f).double(), copy.deepcopy(pol).double()
+    n = 3
+    scale = torch.tensor([1.0, 0.5, -1.5], dtype=torch.float64, device=DEV)
+    ctx = (torch.as_tensor(g["v_out"], device=DEV) * scale[:, None]).float().view(n, 1, vh).contiguous()
+    t_idx = torch.zeros(n, dtype=torch.int64, device=DEV)
+    h, c = torch.zeros(n, sh, device=DEV), torch.zeros(n, sh, device=DEV)
+    h64, c64 = h.double(), c.double()
+    act, mean = torch.empty(n, 4, dtype=torch.float64, device=DEV), torch.empty(n, 4, device=DEV)
+    for k in range(g["st_seq"].shape[0]):
+        state = (torch.as_tensor(g["st_seq"][k], device=DEV) * scale[:, None]).contiguous()          # (3, 5) float64
+        fp(ctx, t_idx, state, h, c, act, mean_out=mean)
+        with torch.no_grad():
+            h64, c64 = cell64(state.float().double(), (h64, c64))
+            mean64, _ = pol64.mean_std(torch.cat((ctx[:, 0].double(), h64), 1))
+        np.testing.assert_allclose(h[0].cpu().numpy(), g["test_out"][k][vh:], rtol=1e-5, atol=1e-5, err_msg="step %d" % k)
+        np.testing.assert_allclose(h.cpu().numpy(), h64.cpu().numpy(), rtol=1e-5, atol=1e-5, err_msg="h, step %d" % k)
+        np.testing.assert_allclose(c.cpu().numpy(), c64.cpu().numpy(), rtol=1e-5, atol=1e-5, err_msg="c, step %d" % k)
+        np.testing.assert_allclose(mean.cpu().numpy(), mean64.cpu().numpy(), rtol=1e-5, atol=1e-5, err_msg="mean, step %d" % k)
+        np.testing.assert_array_equal(act.cpu().numpy(), mean.double().cpu().numpy())            # noise None: action = mean
+
+
+# ------------------------------------------------------------------------------------------------ 2. config widths
+@pytest.mark.parametrize("S", [115, 116])
+@pytest.mark.parametrize("n", [1, 5, 9])
+def test_forecast_step_at_config_widths_against_float64(cfg_nets, S, n):
+    """Three consecutive steps (h / c of one row zeroed before the second, as a reset does) of kernel, float32 torch path
+    (VideoForecastNet.s_step + mean_std + addcmul, what the rollout ran before) and the same chain in float64 torch. Per
+    quantity the kernel's largest error may be at most 4 x the float32 torch path's (another summation order over k <= 256
+    moves float32 results by a few ulp), and never more than 2e-4 (the rollout tests' bound). Both measured errors are
+    printed (`pytest -s`) and stand in the assertion message."""
+    vs, pol, fp = cfg_nets[S]
+    cell64, pol64 = copy.deepcopy(vs.s_net.rnn_f).double(), copy.deepcopy(pol).double()
+    d = _inputs(n, S, seed=100 + n)
+    gen = torch.Generator(device=DEV).manual_seed(n)
+    h_k, c_k = d["h"].clone(), d["c"].clone()
+    h_t, c_t = d["h"].clone(), d["c"].clone()
+    h_r, c_r = d["h"].double(), d["c"].double()
+    ctx_row = d["ctx"][:, 0]
+    act_k, mean_k = torch.empty(n, 52, dtype=torch.float64, device=DEV), torch.empty(n, 52, device=DEV)
+    err_k, err_t = dict(h=0.0, c=0.0, mean=0.0, action=0.0), dict(h=0.0, c=0.0, mean=0.0, action=0.0)
+    worst = lambda a, b: float((a.double() - b).abs().max())
+    for step in range(3):
+        state = torch.randn(n, S, dtype=torch.float64, device=DEV, generator=gen) * 2
+        noise = torch.randn(n, 52, device=DEV, generator=gen)
+        if step == 1:
+            for t in (h_k, c_k, h_t, c_t, h_r, c_r):
+                t[n // 2] = 0
+        fp(d["ctx"], d["t_idx"], state, h_k, c_k, act_k, noise=noise, mean_out=mean_k)
+        with torch.no_grad():
+            st, (h_t, c_t) = vs.s_step(state.float(), (h_t, c_t))
+            mean_t, std_t = pol.mean_std(torch.cat((ctx_row, st), 1))
+            act_t = torch.addcmul(mean_t, std_t, noise)
+            h_r, c_r = cell64(state.float().double(), (h_r, c_r))
+            mean_r, std_r = pol64.mean_std(torch.cat((ctx_row.double(), h_r), 1))
+            act_r = mean_r + std_r * noise.double()
+        for name, k_, t_, r_ in (("h", h_k, h_t, h_r), ("c", c_k, c_t, c_r), ("mean", mean_k, mean_t, mean_r), ("action", act_k, act_t, act_r)):
+            err_k[name], err_t[name] = max(err_k[name], worst(k_, r_)), max(err_t[name], worst(t_, r_))
+    print("S %d n %d  kernel %s  torch float32 %s" % (S, n, err_k, err_t))
+    for name in err_k:
+        assert err_k[name] <= min(4.0 * err_t[name], 2e-4), "%s: kernel %.3g, float32 torch path %.3g (vs float64)" % (name, err_k[name], err_t[name])
+
+
+# ------------------------------------------------------------------------------------------------ 3. in place, own rows only
+def test_forecast_step_touches_only_its_slice(cfg_nets):
+    """h / c of 12 rows hold a sentinel (in a buffer with a wider row stride); a call on rows [4:9] changes those rows and
+    leaves every other bit -- the rows outside the slice and the pad columns of all rows -- as it was."""
+    vs, pol, fp = cfg_nets[115]
+    N, Hs, a, b = 12, 128, 4, 9
+    hb, cb = torch.full((N, Hs + 3), 0.375, device=DEV), torch.full((N, Hs + 3), -0.25, device=DEV)
+    h0, c0 = hb.clone(), cb.clone()
+    d = _inputs(b - a, 115, seed=8)
+    act = torch.empty(b - a, 52, dtype=torch.float64, device=DEV)
+    fp(d["ctx"], d["t_idx"], d["state"], hb[a:b, :Hs], cb[a:b, :Hs], act, noise=d["noise"])
+    torch.cuda.synchronize()
+    for buf, ref in ((hb, h0), (cb, c0)):
+        keep = torch.ones(N, Hs + 3, dtype=torch.bool, device=DEV)
+        keep[a:b, :Hs] = False
+        assert torch.equal(buf[keep], ref[keep])
+        assert bool((buf[a:b, :Hs] != ref[a:b, :Hs]).any(dim=1).all())
+    # and the slice got the cell's numbers (same call on a contiguous copy of the rows)
+    h1, c1 = h0[a:b, :Hs].contiguous(), c0[a:b, :Hs].contiguous()
+    act1 = torch.empty_like(act)
+    fp(d["ctx"], d["t_idx"], d["state"], h1, c1, act1, noise=d["noise"])
+    assert torch.equal(hb[a:b, :Hs], h1) and torch.equal(cb[a:b, :Hs], c1) and torch.equal(act, act1)
+
+
+# ------------------------------------------------------------------------------------------------ 4. determinism
+def test_forecast_step_is_deterministic_and_position_independent(cfg_nets):
+    vs, pol, fp = cfg_nets[116]
+    n = 9
+    d = _inputs(n, 116, T=3, seed=21)
+    first = _step(fp, d)
+    again = _step(fp, d)
+    assert all(torch.equal(x, y) for x, y in zip(first, again))
+    perm = torch.tensor([5, 0, 8, 2, 7, 1, 3, 6, 4], device=DEV)
+    moved = _step(fp, {k: v[perm].contiguous() for k, v in d.items()})
+    assert all(torch.equal(x[perm], y) for x, y in zip(first, moved))
+    alone = _step(fp, d, n=1)
+    assert all(torch.equal(x[:1], y) for x, y in zip(first, alone))
+
+
+# ------------------------------------------------------------------------------------------------ 5. graph capture
+def test_forecast_step_replays_from_a_captured_graph(cfg_nets):
+    """One step captured the way the rollout's `_ensure_static` does (warm-up on a side stream, a single-branch graph): three
+    replays from the same h / c == three eager steps, bit for bit, h / c included."""
+    vs, pol, fp = cfg_nets[115]
+    n = 9
+    d = _inputs(n, 115, seed=33)
+    h, c = d["h"].clone(), d["c"].clone()
+    act = torch.empty(n, 52, dtype=torch.float64, device=DEV)
+    body = lambda: fp(d["ctx"], d["t_idx"], d["state"], h, c, act, noise=d["noise"])
+    cur = torch.cuda.current_stream()
+    side = torch.cuda.Stream()
+    side.wait_stream(cur)
+    with torch.cuda.stream(side):
+        for _ in range(3):
+            body()
+    cur.wait_stream(side)
+    gr = torch.cuda.CUDAGraph()
+    with torch.cuda.graph(gr):
+        body()
+
+    def three(run):
+        h.copy_(d["h"]); c.copy_(d["c"])
+        out = []
+        for _ in range(3):
+            run()
+            torch.cuda.synchronize()
+            out.append((h.clone(), c.clone(), act.clone()))
+        return out
+    replayed, eager = three(gr.replay), three(body)
+    for k, (x, y) in enumerate(zip(replayed, eager)):
+        assert all(torch.equal(p, q) for p, q in zip(x, y)), "step %d" % k
+    assert not torch.equal(eager[0][0], eager[2][0])
+
+
+# ------------------------------------------------------------------------------------------------ 6, 7. inside the rollout
+@pytest.fixture(scope="module")
+def workspace(tmp_path_factory):
+    from egopose_amd.bench_support import write_synthetic_dataset
+    root = str(tmp_path_factory.mktemp("egp_ws_fc"))
+    write_synthetic_dataset(root, "subject_03", n_takes=3, n_frames=300, seed=4)
+    return root
+
+
+def _forecast_trainer(workspace, n_env, episode_len, **kw):
+    from egopose_amd.config import ForecastConfig
+    from egopose_amd.train import Trainer
+    os.chdir(workspace)
+    cfg = ForecastConfig("subject_03", create_dirs=False)
+    cfg.env_episode_len = episode_len
+    cfg.num_optim_epoch = 2
+    return Trainer(cfg, torch.device("cuda", 0), torch.float32, num_envs=n_env, **kw), cfg
+
+
+def _train_mode_mean(tr, ro, batch, v_metas=None):
+    """Policy head over VideoForecastNet's TRAIN-mode forward of the batch (the form pinned to the reference's vectors)."""
+    dev = torch.device("cuda", 0)
+    vs, pol = tr.policy_vs_net, tr.policy_net
+    with torch.no_grad():
+        vs.set_mode("train")
+        vs.attach_feature_table(ro.experts.cnn_table(dev, torch.float32), ro.experts.cnn_offset)
+        masks = torch.as_tensor(batch.masks.astype(np.float32), device=dev)
+        vs.initialize((masks, tr.env.cnn_feat, batch.v_metas if v_metas is None else v_metas))
+        mean, _ = pol.mean_std(vs(torch.as_tensor(batch.states, dtype=torch.float32, device=dev)))
+        vs.set_mode("test")
+    return mean.double().cpu().numpy()
+
+
+def test_forecast_rollout_mean_action_runs_the_fused_step(workspace, monkeypatch):
+    """Evaluation rollout (mean action) of ego_forecast: every tick is one call of the fused step, and every recorded action
+    equals the policy head over the train-mode nets on the recorded states -- the per-slot h / c (zeroed at every episode
+    start, several per slot) and the per-slot context row are the right ones."""
+    from egopose_amd import policy_step
+    calls = [0]
+    inner = policy_step.FusedForecastPolicy.__call__
+
+    def counted(self, *a, **k):
+        calls[0] += 1
+        return inner(self, *a, **k)
+    monkeypatch.setattr(policy_step.FusedForecastPolicy, "__call__", counted)
+    tr, cfg = _forecast_trainer(workspace, 16, 12, num_threads=4, num_groups=2)
+    tr.pre_iter_update(0)
+    tr.agent.mean_action = True
+    ro = tr.agent._get_rollout()
+    ro.mean_action = True
+    batch, log = tr.agent.sample(16 * 40)
+    assert isinstance(ro._fused, policy_step.FusedForecastPolicy) and calls[0] > 0
+    ends = np.where(batch.masks == 0)[0]
+    assert len(batch) >= 16 * 40 and len(ends) >= 3 * 16 and batch.exps.max() == 0
+    np.testing.assert_allclose(batch.actions, _train_mode_mean(tr, ro, batch), rtol=2e-4, atol=2e-4)
+    sh = batch.v_metas.copy()
+    sh[:, 1] += 1                       # the check has teeth: another start frame = another context row
+    assert np.abs(_train_mode_mean(tr, ro, batch, sh) - batch.actions).max() > 1e-3
+    tr.close()
+
+
+@pytest.mark.parametrize("use_fused", [True, False])
+def test_forecast_rollout_sampled_actions_are_mean_plus_unit_noise(workspace, use_fused):
+    """Exploration rollout of ego_forecast through the captured fused step (and, `use_fused = False`, through the torch tick):
+    (action - train-mode mean) / std is N(0, 1) noise, independent across steps and action dimensions (the bounds of
+    test_sampled_actions_are_policy_mean_plus_unit_noise; >= 66 k values, standard errors ~0.004)."""
+    from egopose_amd import policy_step
+    tr, cfg = _forecast_trainer(workspace, 32, 12, num_threads=4, num_groups=2)
+    tr.pre_iter_update(0)
+    ro = tr.agent._get_rollout()
+    ro.use_fused = use_fused
+    batch, log = tr.agent.sample(32 * 40)
+    if use_fused:
+        assert isinstance(ro._fused, policy_step.FusedForecastPolicy) and ro.timing["policy_graph"]
+    else:
+        assert ro._fused is None
+    mean = _train_mode_mean(tr, ro, batch)
+    std = float(np.exp(tr.policy_net.action_log_std.detach().cpu().numpy().ravel()[0]))
+    z = (batch.actions - mean) / std
+    assert z.size >= 66000 and batch.exps.min() == 1
+    assert abs(z.mean()) < 0.02 and abs(z.std() - 1.0) < 0.02 and np.abs(z).max() < 6.5
+    assert abs(np.corrcoef(z[:-1, 0], z[1:, 0])[0, 1]) < 0.1 and abs(np.corrcoef(z[:, 0], z[:, 1])[0, 1]) < 0.1
+    tr.close()
