@@ -58,6 +58,28 @@ __device__ long long g_pol_trace[64];
 
 constexpr int POL_MAX_LAYERS = 8;
 constexpr int POL_GC = 5;            // column groups (64 outputs each) a pass accumulates in registers: 320 >= the 300-wide layer
+constexpr int POL_PS = POL_GC * 64 + 4;   // row stride of a wave's partial sums (floats)
+
+// tile of the policy step, both kernels: rows per workgroup x waves x weight blocks in flight per column group.
+// Round-4 sweep on the MI355X (tools/probes/policy_tile_sweep.sh; 512 rows, bench workload): 4x4x2 15.2 us per launch and the
+// lowest / least scattered T_sample; 4x8x2 14.9 us; 8-row tiles 19-21 us (twice the MFMAs per workgroup on half the CUs).
+constexpr int POL_R = 4, POL_NW = 4, POL_PF = 2;
+
+// The dynamic LDS of a workgroup, for the kernels and for the host's byte count (float offsets; cur is at 0):
+//   cur[R][xs] | nxt[R][xs] | part[NW][R][POL_PS] | every layer's bias | exp(log_std) | the rows' noise | the kernel's own tail:
+//   the filter's merged (mean, 1 / std) doubles behind a pad to an even float (the pad float is always reserved), or the cell's c rows
+struct PolCarve {
+    int nxt, part, bias, sd, noise, tail, ms;
+};
+template <int R, int NW>
+__host__ __device__ __forceinline__ PolCarve pol_carve(int xs, int sum_out4, int out_last) {
+    const int out4 = (out_last + 3) & ~3;
+    PolCarve c;
+    c.nxt = R * xs; c.part = 2 * R * xs; c.bias = c.part + NW * R * POL_PS;
+    c.sd = c.bias + sum_out4; c.noise = c.sd + out4; c.tail = c.noise + R * out4;
+    c.ms = c.tail + ((R * out4) & 1);
+    return c;
+}
 
 struct PolLayers {
     const float *wp[POL_MAX_LAYERS];     // packed weights (egp_mlp_pack_f32)
@@ -170,6 +192,175 @@ __device__ __forceinline__ void pol_pass(PolStage<PF> &st, const float *__restri
     }
 }
 
+// a wave's share [kq0, kq1) of a layer's nkq input quads (wave scalar: the k loops' bounds live in SGPRs)
+struct PolSplit {
+    int nkq, kq0, kq1;
+};
+template <int NW>
+__device__ __forceinline__ PolSplit pol_split(int in_dim, int wave) {
+    const int nkq = (in_dim + 3) >> 2;
+    return PolSplit{nkq, wave * nkq / NW, (wave + 1) * nkq / NW};
+}
+
+// the wave's first blocks of the pass over column groups g0 .. of layer l
+template <int NW, int PF>
+__device__ __forceinline__ void pol_preload_pass(PolStage<PF> &st, const PolLayers &L, int l, int g0, int wave, int lane) {
+    const PolSplit k = pol_split<NW>(L.in_dim[l], wave);
+    pol_preload<PF>(st, L.wp[l], k.nkq, g0, min(POL_GC, ((L.out_dim[l] + 63) >> 6) - g0), k.kq0, max(k.kq1, k.kq0 + 1), lane);
+}
+
+// L2 warm-up. A kernel starts with a cold L2 on every XCD (the per-XCD L2s are invalidated at kernel boundaries), so the
+// first touch of a weight line costs a trip to the memory side (~0.7 us) and a wave's PF x POL_GC KiB in flight turn the
+// weight stream into a chain of such trips. The workgroups of one XCD (round-robin dispatch: blockIdx & 7) therefore each
+// touch a DIFFERENT slice of the packed weights right away -- one dword per 128-byte line, all requests in flight at once --
+// while the input rows are gathered; by the time the k loops start, the XCD's L2 holds every layer and the stream runs at
+// L2-hit latency. (Pure prefetch: results are never used; up to POL_WARM x T lines per workgroup; needs the layers' packed
+// buffers back to back in memory -- FusedGaussianPolicy allocates them so -- else warm_lines = 0 and one line is touched.)
+constexpr int POL_WARM = 8;
+template <int T>
+__device__ __forceinline__ void pol_warm_request(const PolLayers &L, int tid, float (&warm)[POL_WARM]) {
+    const int per_xcd = (gridDim.x + 7) >> 3, me = blockIdx.x >> 3;
+    const int lo = (int)((long)L.warm_lines * me / per_xcd), hi = (int)((long)L.warm_lines * (me + 1) / per_xcd);
+#pragma unroll
+    for (int u = 0; u < POL_WARM; ++u) {
+        const int i = min(lo + tid + u * T, max(hi - 1, 0));
+        warm[u] = L.wp[0][(long)i * 32];
+    }
+}
+// (behind the inputs' barrier the warm-up loads have long landed; their registers are free from here on)
+__device__ __forceinline__ void pol_warm_sink(const float (&warm)[POL_WARM]) {
+    float sink = 0.0f;
+#pragma unroll
+    for (int u = 0; u < POL_WARM; ++u) sink += warm[u];
+    asm volatile("" ::"v"(sink));
+}
+
+// What the forecast step's layer 0 -- the state LSTM's gates -- needs in its epilogue (see forecast_body)
+struct PolCell {
+    const float *s_c;                // c rows in LDS [R][hs]
+    float *h_io, *c_io; long hc_stride;
+    int hs, ctx_dim;
+};
+
+// The layers, one pass per chunk of POL_GC x 64 output columns: `cur` holds the workgroup's input rows, `st` the wave's first
+// blocks of layer 0, `split` its share of layer 0's quads. Epilogue of a pass: bias + the waves' partial sums in fixed order
+// (deterministic), then the activation into `nxt` (hidden layer), the Gaussian head (last layer) or, CELL0, layer 0's gates:
+// h' behind the context columns that the prologue has put into `nxt`, h' / c' to the caller's rows.
+template <int R, int NW, int PF, bool CELL0>
+__device__ __forceinline__ void pol_layers(float *cur, float *nxt, float *part, const float *s_bias, const float *s_sd, const float *s_noise,
+                                           PolStage<PF> &st, PolSplit split, const PolLayers &L, int act_kind, int xs, int r0, int n, int wave,
+                                           const float *__restrict__ noise, double *__restrict__ action, float *__restrict__ mean_out,
+                                           const PolCell &C) {
+    constexpr int T = NW * 64, PS = POL_PS;
+    const int tid = threadIdx.x, lane = tid & 63;
+    int bias_off = 0;
+    for (int l = 0; l < L.n; ++l) {
+        const int out = L.out_dim[l];
+        const int ng_all = (out + 63) >> 6;
+        const bool last = l == L.n - 1;
+        const float *wl = L.wp[l];
+        for (int g0 = 0; g0 < ng_all; g0 += POL_GC) {
+            const int ng = min(POL_GC, ng_all - g0);
+            f32x4 acc[POL_GC][R / 4];
+#pragma unroll
+            for (int g = 0; g < POL_GC; ++g)
+#pragma unroll
+                for (int h = 0; h < R / 4; ++h) acc[g][h] = f32x4{0.f, 0.f, 0.f, 0.f};
+            if (split.kq1 > split.kq0) {
+                const int nkq = split.nkq, kq0 = split.kq0, kq1 = split.kq1;
+                switch (ng) {
+                    case 1: pol_pass<1, R, PF>(st, wl, nkq, g0, kq0, kq1, cur, xs, lane, acc); break;
+                    case 2: pol_pass<2, R, PF>(st, wl, nkq, g0, kq0, kq1, cur, xs, lane, acc); break;
+                    case 3: pol_pass<3, R, PF>(st, wl, nkq, g0, kq0, kq1, cur, xs, lane, acc); break;
+                    case 4: pol_pass<4, R, PF>(st, wl, nkq, g0, kq0, kq1, cur, xs, lane, acc); break;
+                    default: pol_pass<5, R, PF>(st, wl, nkq, g0, kq0, kq1, cur, xs, lane, acc); break;
+                }
+            }
+            POL_TR(3 + 4 * l);
+            // the next pass's first blocks: same layer's next column chunk, or the next layer
+            {
+                int nl = l, ng0 = g0 + POL_GC;
+                if (ng0 >= ng_all) { nl = l + 1; ng0 = 0; }
+                if (nl < L.n) pol_preload_pass<NW, PF>(st, L, nl, ng0, wave, lane);
+            }
+            // partial sums -> LDS: register i of lane 4 b + j = out[row 4 h + j][column 64 g + 4 b + i]
+#pragma unroll
+            for (int g = 0; g < POL_GC; ++g)
+                if (g < ng) {
+#pragma unroll
+                    for (int h = 0; h < R / 4; ++h)
+                        *reinterpret_cast<f32x4 *>(part + ((wave * R) + 4 * h + (lane & 3)) * PS + 64 * g + (lane & ~3)) = acc[g][h];
+                }
+            POL_TR(4 + 4 * l);
+            __syncthreads();
+            POL_TR(5 + 4 * l);
+            const int c_base = 64 * g0;
+            const int cw = min(out - c_base, POL_GC * 64);               // real columns of this chunk
+            if (CELL0 && l == 0) {
+                // gate epilogue: one thread per unit, columns 4 u .. 4 u + 3 = (i, f, g, o); fixed summation order
+                for (int j = tid; j < (cw >> 2); j += T) {
+                    const int u = (c_base >> 2) + j;
+                    const f32x4 bv = *reinterpret_cast<const f32x4 *>(s_bias + 4 * u);
+                    f32x4 v[R];
+#pragma unroll
+                    for (int r = 0; r < R; ++r) v[r] = bv;
+#pragma unroll
+                    for (int w = 0; w < NW; ++w)
+#pragma unroll
+                        for (int r = 0; r < R; ++r) v[r] += *reinterpret_cast<const f32x4 *>(part + (w * R + r) * PS + 4 * j);
+#pragma unroll
+                    for (int r = 0; r < R; ++r) {
+                        const float gi = pol_act(v[r][0], 2), gf = pol_act(v[r][1], 2), gg = tanhf(v[r][2]), go = pol_act(v[r][3], 2);
+                        const float cn = gf * C.s_c[r * C.hs + u] + gi * gg;
+                        const float hn = go * tanhf(cn);
+                        nxt[r * xs + C.ctx_dim + u] = hn;
+                        const int row = r0 + r;
+                        if (row < n) {
+                            C.h_io[(long)row * C.hc_stride + u] = hn;
+                            C.c_io[(long)row * C.hc_stride + u] = cn;
+                        }
+                    }
+                }
+            } else {
+                const int cw4 = last ? cw : min((cw + 3) & ~3, ng * 64);      // hidden layers: the pad columns of the last quad become zeros
+                for (int c = tid; c < cw4; c += T) {
+                    const int col = c_base + c;
+                    const bool real = c < cw;
+                    const float bv = real ? s_bias[bias_off + col] : 0.0f;
+                    float v[R];
+#pragma unroll
+                    for (int r = 0; r < R; ++r) v[r] = bv;
+#pragma unroll
+                    for (int w = 0; w < NW; ++w)                         // fixed order: deterministic
+#pragma unroll
+                        for (int r = 0; r < R; ++r) v[r] += part[(w * R + r) * PS + c];
+                    if (!last) {
+#pragma unroll
+                        for (int r = 0; r < R; ++r) nxt[r * xs + col] = real ? pol_act(v[r], act_kind) : 0.0f;
+                    } else {
+                        const float sd = noise ? s_sd[col] : 0.0f;
+#pragma unroll
+                        for (int r = 0; r < R; ++r) {
+                            const int row = r0 + r;
+                            if (row >= n) continue;
+                            const float a = noise ? fmaf(sd, s_noise[r * out + col], v[r]) : v[r];
+                            action[(long)row * out + col] = (double)a;
+                            if (mean_out) mean_out[(long)row * out + col] = v[r];
+                        }
+                    }
+                }
+            }
+            __syncthreads();
+            POL_TR(6 + 4 * l);
+        }
+        bias_off += (out + 3) & ~3;
+        if (!last) {
+            split = pol_split<NW>(L.in_dim[l + 1], wave);
+            float *t = cur; cur = nxt; nxt = t;
+        }
+    }
+}
+
 // `stage_src` / `stage_dst` (optional): the tick's flag slab. The rollout stages the integer flags and context-row indices of a
 // tick in pinned host memory; instead of a copy-engine transfer in front of this kernel (one more dependent operation, ~6 us,
 // on the chain filter -> policy -> env-step of every tick) the workgroups copy the slab to its device copy themselves -- the
@@ -183,15 +374,14 @@ __device__ __forceinline__ void policy_body(const float *__restrict__ ctx_rows, 
                                   const unsigned *__restrict__ stage_src, unsigned *__restrict__ stage_dst, int stage_words,
                                   const PolFilter &F) {
     constexpr int T = NW * 64;
-    constexpr int PS = POL_GC * 64 + 4;              // row stride of a wave's partial sums (floats)
-    extern __shared__ __attribute__((aligned(16))) float s_f[];     // cur[R][xs] | nxt[R][xs] | part[NW][R][PS] [| mean, 1/std: 2 dim doubles]
-    float *cur = s_f, *nxt = s_f + R * xs, *part = s_f + 2 * R * xs;
+    extern __shared__ __attribute__((aligned(16))) float s_f[];     // see PolCarve; the tail: mean, 1 / std of the filter (2 dim doubles)
+    const int out_last = L.out_dim[L.n - 1];
+    const PolCarve lds = pol_carve<R, NW>(xs, L.sum_out4, out_last);
+    float *cur = s_f, *nxt = s_f + lds.nxt, *part = s_f + lds.part;
     // small operands of the epilogues, fetched once in the prologue (a global load in an epilogue is a cold round trip on the chain):
     // every layer's bias | exp(log_std) | the rows' noise
-    float *s_bias = part + NW * R * PS;
-    const int out_last = L.out_dim[L.n - 1];
-    float *s_sd = s_bias + L.sum_out4, *s_noise = s_sd + ((out_last + 3) & ~3);
-    double *s_ms = reinterpret_cast<double *>(s_noise + R * ((out_last + 3) & ~3) + ((R * ((out_last + 3) & ~3)) & 1));
+    float *s_bias = s_f + lds.bias, *s_sd = s_f + lds.sd, *s_noise = s_f + lds.noise;
+    double *s_ms = reinterpret_cast<double *>(s_f + lds.ms);
     const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);      // (scalar: the k loops' bounds live in SGPRs)
     const int r0 = blockIdx.x * R;
     const int in0 = ctx_dim + state_dim;
@@ -221,32 +411,12 @@ __device__ __forceinline__ void policy_body(const float *__restrict__ ctx_rows, 
             pend = F.src.template load_rows<R>(r0, n, c_own);
         }
     }
-    // L2 warm-up. A kernel starts with a cold L2 on every XCD (the per-XCD L2s are invalidated at kernel boundaries), so the
-    // first touch of a weight line costs a trip to the memory side (~0.7 us) and a wave's PF x POL_GC KiB in flight turn the
-    // weight stream into a chain of such trips. The workgroups of one XCD (round-robin dispatch: blockIdx & 7) therefore each
-    // touch a DIFFERENT slice of the packed weights right away -- one dword per 128-byte line, all requests in flight at once --
-    // while the input rows are gathered; by the time the k loops start, the XCD's L2 holds every layer and the stream runs at
-    // L2-hit latency. (Pure prefetch: results are never used; up to POL_WARM x T lines per workgroup; needs the layers' packed
-    // buffers back to back in memory -- FusedGaussianPolicy allocates them so -- else warm_lines = 0 and one line is touched.)
-    constexpr int POL_WARM = 8;
+    // the L2 warm-up (pol_warm_request), while the input rows are gathered
     float warm[POL_WARM];
-    {
-        const int per_xcd = (gridDim.x + 7) >> 3, me = blockIdx.x >> 3;
-        const int lo = (int)((long)L.warm_lines * me / per_xcd), hi = (int)((long)L.warm_lines * (me + 1) / per_xcd);
-#pragma unroll
-        for (int u = 0; u < POL_WARM; ++u) {
-            const int i = min(lo + tid + u * T, max(hi - 1, 0));
-            warm[u] = L.wp[0][(long)i * 32];
-        }
-    }
+    pol_warm_request<T>(L, tid, warm);
     // the first layer's own first blocks
     PolStage<PF> st;
-    int nkq = (L.in_dim[0] + 3) >> 2;
-    int kq0 = wave * nkq / NW, kq1 = (wave + 1) * nkq / NW;
-    {
-        const int ng_all = (L.out_dim[0] + 63) >> 6;
-        pol_preload<PF>(st, L.wp[0], nkq, 0, min(ng_all, POL_GC), kq0, max(kq1, kq0 + 1), lane);
-    }
+    pol_preload_pass<NW, PF>(st, L, 0, 0, wave, lane);
     // the context columns (waiting for the indices requested first; everything above stays in flight)
     long ctx_off[R];                      // every thread resolves its rows' context offsets itself: no LDS hop + barrier between the two dependent loads
 #pragma unroll
@@ -409,117 +579,27 @@ __device__ __forceinline__ void policy_body(const float *__restrict__ ctx_rows, 
     // (the barrier for the staged inputs in LDS only: __syncthreads() would also wait for the acknowledgement of the filtered
     //  rows' global stores above -- a trip to the memory side on the critical path; nothing in this kernel reads them back)
     asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");
-    {   // the warm-up loads have long landed; their registers are free from here on
-        float sink = 0.0f;
-#pragma unroll
-        for (int u = 0; u < POL_WARM; ++u) sink += warm[u];
-        asm volatile("" ::"v"(sink));
-    }
+    pol_warm_sink(warm);
     POL_TR(2);
 
-    int bias_off = 0;
-    for (int l = 0; l < L.n; ++l) {
-        const int out = L.out_dim[l];
-        const int ng_all = (out + 63) >> 6;
-        const bool last = l == L.n - 1;
-        const float *wl = L.wp[l];
-        for (int g0 = 0; g0 < ng_all; g0 += POL_GC) {
-            const int ng = min(POL_GC, ng_all - g0);
-            f32x4 acc[POL_GC][R / 4];
-#pragma unroll
-            for (int g = 0; g < POL_GC; ++g)
-#pragma unroll
-                for (int h = 0; h < R / 4; ++h) acc[g][h] = f32x4{0.f, 0.f, 0.f, 0.f};
-            if (kq1 > kq0) {
-                switch (ng) {
-                    case 1: pol_pass<1, R, PF>(st, wl, nkq, g0, kq0, kq1, cur, xs, lane, acc); break;
-                    case 2: pol_pass<2, R, PF>(st, wl, nkq, g0, kq0, kq1, cur, xs, lane, acc); break;
-                    case 3: pol_pass<3, R, PF>(st, wl, nkq, g0, kq0, kq1, cur, xs, lane, acc); break;
-                    case 4: pol_pass<4, R, PF>(st, wl, nkq, g0, kq0, kq1, cur, xs, lane, acc); break;
-                    default: pol_pass<5, R, PF>(st, wl, nkq, g0, kq0, kq1, cur, xs, lane, acc); break;
-                }
-            }
-            POL_TR(3 + 4 * l);
-            // the next pass's first blocks: same layer's next column chunk, or the next layer
-            {
-                int nl = l, ng0 = g0 + POL_GC;
-                if (ng0 >= ng_all) { nl = l + 1; ng0 = 0; }
-                if (nl < L.n) {
-                    const int nkq_n = (L.in_dim[nl] + 3) >> 2;
-                    const int a = wave * nkq_n / NW, b = (wave + 1) * nkq_n / NW;
-                    const int ng_n = min(POL_GC, ((L.out_dim[nl] + 63) >> 6) - ng0);
-                    pol_preload<PF>(st, L.wp[nl], nkq_n, ng0, ng_n, a, max(b, a + 1), lane);
-                }
-            }
-            // partial sums -> LDS: register i of lane 4 b + j = out[row 4 h + j][column 64 g + 4 b + i]
-#pragma unroll
-            for (int g = 0; g < POL_GC; ++g)
-                if (g < ng) {
-#pragma unroll
-                    for (int h = 0; h < R / 4; ++h)
-                        *reinterpret_cast<f32x4 *>(part + ((wave * R) + 4 * h + (lane & 3)) * PS + 64 * g + (lane & ~3)) = acc[g][h];
-                }
-            POL_TR(4 + 4 * l);
-            __syncthreads();
-            POL_TR(5 + 4 * l);
-            const int c_base = 64 * g0;
-            const int cw = min(out - c_base, POL_GC * 64);               // real columns of this chunk
-            const int cw4 = last ? cw : min((cw + 3) & ~3, ng * 64);      // hidden layers: the pad columns of the last quad become zeros
-            for (int c = tid; c < cw4; c += T) {
-                const int col = c_base + c;
-                const bool real = c < cw;
-                const float bv = real ? s_bias[bias_off + col] : 0.0f;
-                float v[R];
-#pragma unroll
-                for (int r = 0; r < R; ++r) v[r] = bv;
-#pragma unroll
-                for (int w = 0; w < NW; ++w)                         // fixed order: deterministic
-#pragma unroll
-                    for (int r = 0; r < R; ++r) v[r] += part[(w * R + r) * PS + c];
-                if (!last) {
-#pragma unroll
-                    for (int r = 0; r < R; ++r) nxt[r * xs + col] = real ? pol_act(v[r], act_kind) : 0.0f;
-                } else {
-                    const float sd = noise ? s_sd[col] : 0.0f;
-#pragma unroll
-                    for (int r = 0; r < R; ++r) {
-                        const int row = r0 + r;
-                        if (row >= n) continue;
-                        const float a = noise ? fmaf(sd, s_noise[r * out + col], v[r]) : v[r];
-                        action[(long)row * out + col] = (double)a;
-                        if (mean_out) mean_out[(long)row * out + col] = v[r];
-                    }
-                }
-            }
-            __syncthreads();
-            POL_TR(6 + 4 * l);
-        }
-        bias_off += (out + 3) & ~3;
-        if (!last) {
-            nkq = (L.in_dim[l + 1] + 3) >> 2;
-            kq0 = wave * nkq / NW; kq1 = (wave + 1) * nkq / NW;
-            float *t = cur; cur = nxt; nxt = t;
-        }
-    }
+    pol_layers<R, NW, PF, false>(cur, nxt, part, s_bias, s_sd, s_noise, st, pol_split<NW>(L.in_dim[0], wave), L, act_kind, xs, r0, n, wave,
+                                 noise, action, mean_out, PolCell{});
 }
 
 // Registers: no cap. A resident K1 workgroup keeps one 346-register wave on every SIMD of its CU for the length of an env-step
 // (160 left); with 2 groups the OTHER group's K1 occupies half the CUs while this group's policy step runs. A policy workgroup
 // that needs more than 160 registers per SIMD cannot be placed beside a K1 wave and goes to the K1-free CUs -- which is where it
 // runs fastest anyway (no polling waves competing for issue slots), so the prefetch depth is chosen for speed, not for fitting.
-#define POL_KERNEL_ARGS                                                                                                          \
-    const float *__restrict__ ctx_rows, long ctx_row_stride, int ctx_dim, const long long *__restrict__ t_idx,                     \
-        const double *__restrict__ state, int state_dim, int n, PolLayers L, int act_kind, int xs, const float *__restrict__ log_std, \
-        const float *__restrict__ noise, double *__restrict__ action, float *__restrict__ mean_out,                               \
-        const unsigned *__restrict__ stage_src, unsigned *__restrict__ stage_dst, int stage_words, PolFilter F
-#define POL_KERNEL_PASS ctx_rows, ctx_row_stride, ctx_dim, t_idx, state, state_dim, n, L, act_kind, xs, log_std, noise, action, mean_out, stage_src, stage_dst, stage_words, F
 template <int R, int PF, bool FILTER>
-__global__ __launch_bounds__(256) void k_policy_gaussian_w4(POL_KERNEL_ARGS) {
-    policy_body<R, 4, PF, FILTER>(POL_KERNEL_PASS);
-}
-template <int R, int PF, bool FILTER>
-__global__ __launch_bounds__(512) void k_policy_gaussian_w8(POL_KERNEL_ARGS) {
-    policy_body<R, 8, PF, FILTER>(POL_KERNEL_PASS);
+__global__ __launch_bounds__(256) void k_policy_gaussian_w4(const float *__restrict__ ctx_rows, long ctx_row_stride, int ctx_dim,
+                                                            const long long *__restrict__ t_idx, const double *__restrict__ state,
+                                                            int state_dim, int n, PolLayers L, int act_kind, int xs,
+                                                            const float *__restrict__ log_std, const float *__restrict__ noise,
+                                                            double *__restrict__ action, float *__restrict__ mean_out,
+                                                            const unsigned *__restrict__ stage_src, unsigned *__restrict__ stage_dst,
+                                                            int stage_words, PolFilter F) {
+    policy_body<R, 4, PF, FILTER>(ctx_rows, ctx_row_stride, ctx_dim, t_idx, state, state_dim, n, L, act_kind, xs, log_std, noise, action, mean_out,
+                                  stage_src, stage_dst, stage_words, F);
 }
 
 // ---------------------------------------------------------------------------------------------------------------- forecast
@@ -539,13 +619,11 @@ __device__ __forceinline__ void forecast_body(const float *__restrict__ ctx_rows
                                               const PolLayers &L, int act_kind, int xs, const float *__restrict__ log_std,
                                               const float *__restrict__ noise, double *__restrict__ action, float *__restrict__ mean_out) {
     constexpr int T = NW * 64;
-    constexpr int PS = POL_GC * 64 + 4;
-    extern __shared__ __attribute__((aligned(16))) float s_f[];     // cur[R][xs] | nxt[R][xs] | part[NW][R][PS] | small operands | c[R][hs]
-    float *cur = s_f, *nxt = s_f + R * xs, *part = s_f + 2 * R * xs;
-    float *s_bias = part + NW * R * PS;
+    extern __shared__ __attribute__((aligned(16))) float s_f[];     // see PolCarve; the tail: c[R][hs]
     const int out_last = L.out_dim[L.n - 1];
-    const int osd4 = (out_last + 3) & ~3;
-    float *s_sd = s_bias + L.sum_out4, *s_noise = s_sd + osd4, *s_c = s_noise + R * osd4;
+    const PolCarve lds = pol_carve<R, NW>(xs, L.sum_out4, out_last);
+    float *cur = s_f, *nxt = s_f + lds.nxt, *part = s_f + lds.part;
+    float *s_bias = s_f + lds.bias, *s_sd = s_f + lds.sd, *s_noise = s_f + lds.noise, *s_c = s_f + lds.tail;
     const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int r0 = blockIdx.x * R;
     const int in_c = state_dim + hs, in_cp = (in_c + 3) & ~3;        // the cell's input [s | h]
@@ -555,23 +633,12 @@ __device__ __forceinline__ void forecast_body(const float *__restrict__ ctx_rows
     long tix[R];
 #pragma unroll
     for (int r = 0; r < R; ++r) tix[r] = ctx_dim > 0 ? (long)t_idx[min(r0 + r, n - 1)] : 0;
-    // L2 warm-up over the packed weights (cell + MLP in one range), as in policy_body
-    constexpr int POL_WARM = 8;
+    // L2 warm-up over the packed weights (cell + MLP in one range)
     float warm[POL_WARM];
-    {
-        const int per_xcd = (gridDim.x + 7) >> 3, me = blockIdx.x >> 3;
-        const int lo = (int)((long)L.warm_lines * me / per_xcd), hi = (int)((long)L.warm_lines * (me + 1) / per_xcd);
-#pragma unroll
-        for (int u = 0; u < POL_WARM; ++u) {
-            const int i = min(lo + tid + u * T, max(hi - 1, 0));
-            warm[u] = L.wp[0][(long)i * 32];
-        }
-    }
+    pol_warm_request<T>(L, tid, warm);
     // the cell's own first blocks
     PolStage<PF> st;
-    int nkq = (L.in_dim[0] + 3) >> 2;
-    int kq0 = wave * nkq / NW, kq1 = (wave + 1) * nkq / NW;
-    pol_preload<PF>(st, L.wp[0], nkq, 0, min((L.out_dim[0] + 63) >> 6, POL_GC), kq0, max(kq1, kq0 + 1), lane);
+    pol_preload_pass<NW, PF>(st, L, 0, 0, wave, lane);
     // inputs: cur = [s | h | 0], nxt = [ctx | (h' later) | 0], s_c = c; rows >= n are zeros
     for (int k = tid; k < in_cp; k += T) {
 #pragma unroll
@@ -611,120 +678,10 @@ __device__ __forceinline__ void forecast_body(const float *__restrict__ ctx_rows
         }
     }
     __syncthreads();
-    {
-        float sink = 0.0f;
-#pragma unroll
-        for (int u = 0; u < POL_WARM; ++u) sink += warm[u];
-        asm volatile("" ::"v"(sink));
-    }
+    pol_warm_sink(warm);
 
-    int bias_off = 0;
-    for (int l = 0; l < L.n; ++l) {
-        const int out = L.out_dim[l];
-        const int ng_all = (out + 63) >> 6;
-        const bool last = l == L.n - 1, cell = l == 0;
-        const float *wl = L.wp[l];
-        for (int g0 = 0; g0 < ng_all; g0 += POL_GC) {
-            const int ng = min(POL_GC, ng_all - g0);
-            f32x4 acc[POL_GC][R / 4];
-#pragma unroll
-            for (int g = 0; g < POL_GC; ++g)
-#pragma unroll
-                for (int h = 0; h < R / 4; ++h) acc[g][h] = f32x4{0.f, 0.f, 0.f, 0.f};
-            if (kq1 > kq0) {
-                switch (ng) {
-                    case 1: pol_pass<1, R, PF>(st, wl, nkq, g0, kq0, kq1, cur, xs, lane, acc); break;
-                    case 2: pol_pass<2, R, PF>(st, wl, nkq, g0, kq0, kq1, cur, xs, lane, acc); break;
-                    case 3: pol_pass<3, R, PF>(st, wl, nkq, g0, kq0, kq1, cur, xs, lane, acc); break;
-                    case 4: pol_pass<4, R, PF>(st, wl, nkq, g0, kq0, kq1, cur, xs, lane, acc); break;
-                    default: pol_pass<5, R, PF>(st, wl, nkq, g0, kq0, kq1, cur, xs, lane, acc); break;
-                }
-            }
-            // the next pass's first blocks: same layer's next column chunk, or the next layer
-            {
-                int nl = l, ng0 = g0 + POL_GC;
-                if (ng0 >= ng_all) { nl = l + 1; ng0 = 0; }
-                if (nl < L.n) {
-                    const int nkq_n = (L.in_dim[nl] + 3) >> 2;
-                    const int a = wave * nkq_n / NW, b = (wave + 1) * nkq_n / NW;
-                    const int ng_n = min(POL_GC, ((L.out_dim[nl] + 63) >> 6) - ng0);
-                    pol_preload<PF>(st, L.wp[nl], nkq_n, ng0, ng_n, a, max(b, a + 1), lane);
-                }
-            }
-            // partial sums -> LDS: register i of lane 4 b + j = out[row 4 h + j][column 64 g + 4 b + i]
-#pragma unroll
-            for (int g = 0; g < POL_GC; ++g)
-                if (g < ng) {
-#pragma unroll
-                    for (int h = 0; h < R / 4; ++h)
-                        *reinterpret_cast<f32x4 *>(part + ((wave * R) + 4 * h + (lane & 3)) * PS + 64 * g + (lane & ~3)) = acc[g][h];
-                }
-            __syncthreads();
-            const int c_base = 64 * g0;
-            const int cw = min(out - c_base, POL_GC * 64);               // real columns of this chunk
-            if (cell) {
-                // gate epilogue: one thread per unit, columns 4 u .. 4 u + 3 = (i, f, g, o); fixed summation order
-                for (int j = tid; j < (cw >> 2); j += T) {
-                    const int u = (c_base >> 2) + j;
-                    const f32x4 bv = *reinterpret_cast<const f32x4 *>(s_bias + 4 * u);
-                    f32x4 v[R];
-#pragma unroll
-                    for (int r = 0; r < R; ++r) v[r] = bv;
-#pragma unroll
-                    for (int w = 0; w < NW; ++w)
-#pragma unroll
-                        for (int r = 0; r < R; ++r) v[r] += *reinterpret_cast<const f32x4 *>(part + (w * R + r) * PS + 4 * j);
-#pragma unroll
-                    for (int r = 0; r < R; ++r) {
-                        const float gi = pol_act(v[r][0], 2), gf = pol_act(v[r][1], 2), gg = tanhf(v[r][2]), go = pol_act(v[r][3], 2);
-                        const float cn = gf * s_c[r * hs + u] + gi * gg;
-                        const float hn = go * tanhf(cn);
-                        nxt[r * xs + ctx_dim + u] = hn;
-                        const int row = r0 + r;
-                        if (row < n) {
-                            h_io[(long)row * hc_stride + u] = hn;
-                            c_io[(long)row * hc_stride + u] = cn;
-                        }
-                    }
-                }
-            } else {
-                const int cw4 = last ? cw : min((cw + 3) & ~3, ng * 64);      // hidden layers: the pad columns of the last quad become zeros
-                for (int c = tid; c < cw4; c += T) {
-                    const int col = c_base + c;
-                    const bool real = c < cw;
-                    const float bv = real ? s_bias[bias_off + col] : 0.0f;
-                    float v[R];
-#pragma unroll
-                    for (int r = 0; r < R; ++r) v[r] = bv;
-#pragma unroll
-                    for (int w = 0; w < NW; ++w)                         // fixed order: deterministic
-#pragma unroll
-                        for (int r = 0; r < R; ++r) v[r] += part[(w * R + r) * PS + c];
-                    if (!last) {
-#pragma unroll
-                        for (int r = 0; r < R; ++r) nxt[r * xs + col] = real ? pol_act(v[r], act_kind) : 0.0f;
-                    } else {
-                        const float sd = noise ? s_sd[col] : 0.0f;
-#pragma unroll
-                        for (int r = 0; r < R; ++r) {
-                            const int row = r0 + r;
-                            if (row >= n) continue;
-                            const float a = noise ? fmaf(sd, s_noise[r * out + col], v[r]) : v[r];
-                            action[(long)row * out + col] = (double)a;
-                            if (mean_out) mean_out[(long)row * out + col] = v[r];
-                        }
-                    }
-                }
-            }
-            __syncthreads();
-        }
-        bias_off += (out + 3) & ~3;
-        if (!last) {
-            nkq = (L.in_dim[l + 1] + 3) >> 2;
-            kq0 = wave * nkq / NW; kq1 = (wave + 1) * nkq / NW;
-            float *t = cur; cur = nxt; nxt = t;
-        }
-    }
+    pol_layers<R, NW, PF, true>(cur, nxt, part, s_bias, s_sd, s_noise, st, pol_split<NW>(L.in_dim[0], wave), L, act_kind, xs, r0, n, wave,
+                                noise, action, mean_out, PolCell{s_c, h_io, c_io, hc_stride, hs, ctx_dim});
 }
 
 template <int R, int PF>
@@ -763,21 +720,51 @@ extern "C" int egp_mlp_pack_f32(const float *weight, int64_t ldw, int32_t in_dim
     return EGP_OK;
 }
 
-// tile of the policy step: rows per workgroup x waves x weight blocks in flight per column group.
-// Round-4 sweep on the MI355X (tools/probes/policy_tile_sweep.sh; 512 rows, bench workload): 4x4x2 15.2 us per launch and the
-// lowest / least scattered T_sample; 4x8x2 14.9 us; 8-row tiles 19-21 us (twice the MFMAs per workgroup on half the CUs).
-static void policy_tile(int *R, int *NW, int *PF) { *R = 4; *NW = 4; *PF = 2; }
+// The kernels' layer table from `front` (optional: the forecast step's cell) and layers[0 .. n_layers), validated. `in0`: width of
+// the MLP's input, `chain_msg`: the caller's wording for a break in the dims chain. *kmax: the widest activation row.
+static int pol_layer_table(const egp_mlp_layer *front, const egp_mlp_layer *layers, int n_layers, int in0, const char *chain_msg, PolLayers &L,
+                           int *kmax) {
+    L.n = 0; L.sum_out4 = 0;
+    long lines = 0;
+    bool contiguous = true;
+    const float *follow = nullptr;                    // where the next layer's packed weights start if the buffers follow each other
+    auto append = [&](const egp_mlp_layer &y) {
+        L.wp[L.n] = y.wt; L.bias[L.n] = y.bias; L.in_dim[L.n] = y.in_dim; L.out_dim[L.n] = y.out_dim;
+        ++L.n;
+        L.sum_out4 += (y.out_dim + 3) & ~3;
+        const long floats = egp_mlp_pack_floats(y.in_dim, y.out_dim);
+        if (follow && y.wt != follow) contiguous = false;
+        follow = y.wt + floats;
+        lines += floats / 32;
+    };
+    if (front) append(*front);                        // (checked by the caller, with messages of its own)
+    int prev = in0;
+    *kmax = front && front->in_dim > in0 ? front->in_dim : in0;
+    for (int l = 0; l < n_layers; ++l) {
+        EGP_REQUIRE(layers[l].wt && layers[l].bias, "NULL layer");
+        EGP_REQUIRE(((uintptr_t)layers[l].wt & 15) == 0, "packed weights must be 16-byte aligned");
+        EGP_REQUIRE(layers[l].in_dim == prev && layers[l].out_dim > 0, chain_msg);
+        append(layers[l]);
+        prev = layers[l].out_dim;
+        if (prev > *kmax) *kmax = prev;
+    }
+    EGP_REQUIRE(*kmax <= 2048, "layer wider than 2048");
+    L.warm_lines = contiguous && lines < (1l << 30) ? (int)lines : 0;
+    return EGP_OK;
+}
 
-template <int R, int NW, int PF>
-static void policy_launch_t(bool flt, dim3 grid, size_t lds, hipStream_t s, const float *ctx_rows, long ctx_row_stride, int ctx_dim,
-                            const long long *t_idx, const double *state, int state_dim, int n, const PolLayers &L, int act, int xs,
-                            const float *log_std, const float *noise, double *action, float *mean_out, const unsigned *ssrc, unsigned *sdst,
-                            int swords, const PolFilter &F) {
-#define POL_GO(KERN, FLT) KERN<R, PF, FLT><<<grid, dim3(NW * 64), lds, s>>>(ctx_rows, ctx_row_stride, ctx_dim, t_idx, state, state_dim, n, L, act, xs, \
-                                                                            log_std, noise, action, mean_out, ssrc, sdst, swords, F)
-    if constexpr (NW == 4) { if (flt) POL_GO(k_policy_gaussian_w4, true); else POL_GO(k_policy_gaussian_w4, false); }
-    else { if (flt) POL_GO(k_policy_gaussian_w8, true); else POL_GO(k_policy_gaussian_w8, false); }
-#undef POL_GO
+// Activation row stride and dynamic LDS bytes of a launch: PolCarve's ranges + `tail_bytes` of the kernel's own.
+static int pol_lds(const PolLayers &L, int kmax, size_t tail_bytes, int *xs, size_t *lds) {
+    *xs = ((kmax + 31) & ~31) + 4;                    // rows 0..3 of a broadcast read sit on different banks
+    *lds = (size_t)pol_carve<POL_R, POL_NW>(*xs, L.sum_out4, L.out_dim[L.n - 1]).tail * sizeof(float) + tail_bytes;
+    EGP_REQUIRE(*lds <= 150 * 1024, "layers too wide for the LDS tile");
+    return EGP_OK;
+}
+
+static int pol_launched(const char *what) {
+    hipError_t e = hipGetLastError();
+    if (e != hipSuccess) { egp::set_error("%s launch failed: %s", what, hipGetErrorString(e)); return EGP_E_HIP; }
+    return EGP_OK;
 }
 
 static int policy_launch(const float *ctx_rows, int64_t ctx_row_stride, int32_t ctx_dim, const int64_t *t_idx,
@@ -794,51 +781,20 @@ static int policy_launch(const float *ctx_rows, int64_t ctx_row_stride, int32_t 
     EGP_REQUIRE(activation >= 0 && activation <= 2, "activation: 0 tanh, 1 relu, 2 sigmoid");
     EGP_REQUIRE(ctx_dim >= 0 && state_dim >= 0 && ctx_dim + state_dim > 0, "bad input dims");
     PolLayers L;
-    int kmax = ctx_dim + state_dim, prev = ctx_dim + state_dim;
-    for (int l = 0; l < n_layers; ++l) {
-        EGP_REQUIRE(layers[l].wt && layers[l].bias, "NULL layer");
-        EGP_REQUIRE(((uintptr_t)layers[l].wt & 15) == 0, "packed weights must be 16-byte aligned");
-        EGP_REQUIRE(layers[l].in_dim == prev && layers[l].out_dim > 0, "layer dims do not chain");
-        L.wp[l] = layers[l].wt; L.bias[l] = layers[l].bias;
-        L.in_dim[l] = layers[l].in_dim; L.out_dim[l] = layers[l].out_dim;
-        prev = layers[l].out_dim;
-        if (prev > kmax) kmax = prev;
-    }
-    L.n = n_layers;
-    EGP_REQUIRE(kmax <= 2048, "layer wider than 2048");
-    L.sum_out4 = 0;
-    long lines = 0;
-    bool contiguous = true;
-    for (int l = 0; l < n_layers; ++l) {
-        L.sum_out4 += (layers[l].out_dim + 3) & ~3;
-        if (l > 0 && layers[l].wt != layers[l - 1].wt + egp_mlp_pack_floats(layers[l - 1].in_dim, layers[l - 1].out_dim)) contiguous = false;
-        lines += egp_mlp_pack_floats(layers[l].in_dim, layers[l].out_dim) / 32;
-    }
-    L.warm_lines = contiguous && lines < (1l << 30) ? (int)lines : 0;
-    int R, NW, PF;
-    policy_tile(&R, &NW, &PF);
-    const int xs = ((kmax + 31) & ~31) + 4;          // activation row stride: rows 0..3 of a broadcast read sit on different banks
-    size_t small = 0;                                 // biases | exp(log_std) | noise rows (floats, see the kernel's carve-up)
-    for (int l = 0; l < n_layers; ++l) small += (size_t)((layers[l].out_dim + 3) & ~3);
-    const size_t out4 = (size_t)((layers[n_layers - 1].out_dim + 3) & ~3);
-    small += out4 + (size_t)R * out4 + 1;
-    const size_t lds = ((size_t)2 * R * xs + (size_t)NW * R * (POL_GC * 64 + 4) + small) * sizeof(float) + (flt ? (size_t)2 * state_dim * sizeof(double) : 0);
-    EGP_REQUIRE(lds <= 150 * 1024, "layers too wide for the LDS tile");
-    const dim3 grid((n + R - 1) / R);
+    int kmax, xs;
+    size_t lds;
+    if (int rc = pol_layer_table(nullptr, layers, n_layers, ctx_dim + state_dim, "layer dims do not chain", L, &kmax)) return rc;
+    // the tail: the pad float in front of the doubles, and with the filter its merged mean | 1 / std
+    if (int rc = pol_lds(L, kmax, sizeof(float) + (flt ? (size_t)2 * state_dim * sizeof(double) : 0), &xs, &lds)) return rc;
+    const dim3 grid((n + POL_R - 1) / POL_R), block(POL_NW * 64);
     const PolFilter F = flt ? *flt : PolFilter{};
     const unsigned *ssrc = stage_bytes ? (const unsigned *)stage_src : nullptr;
-#define POL_CASE(r, w, p)                                                                                                              \
-    if (R == r && NW == w && PF == p) {                                                                                                \
-        policy_launch_t<r, w, p>(flt != nullptr, grid, lds, (hipStream_t)stream, ctx_rows, (long)ctx_row_stride, ctx_dim, (const long long *)t_idx, \
-                                 state, state_dim, n, L, activation, xs, log_std, noise, action, mean_out, ssrc, (unsigned *)stage_dst,  \
-                                 (int)(stage_bytes / 4), F);                                                                            \
-    } else
-    POL_CASE(4, 4, 2)
-    { egp::set_error("policy tile %dx%dx%d is not built", R, NW, PF); return EGP_E_INVALID; }
-#undef POL_CASE
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) { egp::set_error("k_policy_gaussian launch failed: %s", hipGetErrorString(e)); return EGP_E_HIP; }
-    return EGP_OK;
+#define POL_GO(FLT) k_policy_gaussian_w4<POL_R, POL_PF, FLT><<<grid, block, lds, (hipStream_t)stream>>>(                                          \
+        ctx_rows, (long)ctx_row_stride, ctx_dim, (const long long *)t_idx, state, state_dim, n, L, activation, xs, log_std, noise, action, mean_out, \
+        ssrc, (unsigned *)stage_dst, (int)(stage_bytes / 4), F)
+    if (flt) POL_GO(true); else POL_GO(false);
+#undef POL_GO
+    return pol_launched("k_policy_gaussian");
 }
 
 extern "C" int egp_policy_gaussian_f32(const float *ctx_rows, int64_t ctx_row_stride, int32_t ctx_dim, const int64_t *t_idx,
@@ -870,39 +826,14 @@ extern "C" int egp_policy_forecast_f32(const float *ctx_rows, int64_t ctx_row_st
     EGP_REQUIRE(state_dim >= 1 && cell->in_dim == state_dim + hs && cell->in_dim <= 2048, "cell: in_dim = state_dim + hidden size, at most 2048");
     EGP_REQUIRE(hc_row_stride >= hs, "h / c row stride below the hidden size");
     PolLayers L;
-    L.wp[0] = cell->wt; L.bias[0] = cell->bias; L.in_dim[0] = cell->in_dim; L.out_dim[0] = cell->out_dim;
-    int kmax = cell->in_dim > ctx_dim + hs ? cell->in_dim : ctx_dim + hs, prev = ctx_dim + hs;
-    L.sum_out4 = cell->out_dim;
-    long lines = egp_mlp_pack_floats(cell->in_dim, cell->out_dim) / 32;
-    bool contiguous = true;
-    const float *follow = cell->wt + egp_mlp_pack_floats(cell->in_dim, cell->out_dim);
-    for (int l = 0; l < n_layers; ++l) {
-        EGP_REQUIRE(layers[l].wt && layers[l].bias, "NULL layer");
-        EGP_REQUIRE(((uintptr_t)layers[l].wt & 15) == 0, "packed weights must be 16-byte aligned");
-        EGP_REQUIRE(layers[l].in_dim == prev && layers[l].out_dim > 0, "layer dims do not chain (first layer: ctx_dim + hidden size)");
-        L.wp[l + 1] = layers[l].wt; L.bias[l + 1] = layers[l].bias;
-        L.in_dim[l + 1] = layers[l].in_dim; L.out_dim[l + 1] = layers[l].out_dim;
-        prev = layers[l].out_dim;
-        if (prev > kmax) kmax = prev;
-        L.sum_out4 += (prev + 3) & ~3;
-        if (layers[l].wt != follow) contiguous = false;
-        follow = layers[l].wt + egp_mlp_pack_floats(layers[l].in_dim, layers[l].out_dim);
-        lines += egp_mlp_pack_floats(layers[l].in_dim, layers[l].out_dim) / 32;
-    }
-    L.n = n_layers + 1;
-    EGP_REQUIRE(kmax <= 2048, "layer wider than 2048");
-    L.warm_lines = contiguous && lines < (1l << 30) ? (int)lines : 0;
-    constexpr int R = 4, NW = 4, PF = 2;              // the tile policy_tile() chose for the same passes
-    const int xs = ((kmax + 31) & ~31) + 4;
-    const size_t out4 = (size_t)((prev + 3) & ~3);
-    const size_t lds = ((size_t)2 * R * xs + (size_t)NW * R * (POL_GC * 64 + 4) + (size_t)L.sum_out4 + out4 + R * out4 + (size_t)R * hs) * sizeof(float);
-    EGP_REQUIRE(lds <= 150 * 1024, "layers too wide for the LDS tile");
-    k_policy_forecast_w4<R, PF><<<dim3((n + R - 1) / R), dim3(NW * 64), lds, (hipStream_t)stream>>>(
+    int kmax, xs;
+    size_t lds;
+    if (int rc = pol_layer_table(cell, layers, n_layers, ctx_dim + hs, "layer dims do not chain (first layer: ctx_dim + hidden size)", L, &kmax)) return rc;
+    if (int rc = pol_lds(L, kmax, (size_t)POL_R * hs * sizeof(float), &xs, &lds)) return rc;      // the tail: the cell's c rows
+    k_policy_forecast_w4<POL_R, POL_PF><<<dim3((n + POL_R - 1) / POL_R), dim3(POL_NW * 64), lds, (hipStream_t)stream>>>(
         ctx_rows, (long)ctx_row_stride, ctx_dim, (const long long *)t_idx, state, state_dim, h, c, (long)hc_row_stride, hs, n, L, activation, xs,
         log_std, noise, action, mean_out);
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) { egp::set_error("k_policy_forecast launch failed: %s", hipGetErrorString(e)); return EGP_E_HIP; }
-    return EGP_OK;
+    return pol_launched("k_policy_forecast");
 }
 
 extern "C" int egp_policy_gaussian_staged_f32(const float *ctx_rows, int64_t ctx_row_stride, int32_t ctx_dim, const int64_t *t_idx,

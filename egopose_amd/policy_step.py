@@ -17,6 +17,22 @@ from . import _lib as L
 _ACT_CODE = {torch.tanh: 0, torch.relu: 1, torch.sigmoid: 2}
 
 
+def _ptr(t):
+    return C.c_void_p(t.data_ptr()) if t is not None else C.c_void_p(0)
+
+
+def _check_io(ctx_rows, t_idx, state, action_out, noise, mean_out, nu):
+    """The tensors every policy step takes: dtypes, layouts and the [n][nu] shapes of the outputs."""
+    n, T, H = ctx_rows.shape
+    assert ctx_rows.dtype == torch.float32 and ctx_rows.stride(2) == 1 and ctx_rows.stride(1) == H
+    assert t_idx.dtype == torch.int64 and t_idx.is_contiguous() and state.dtype == torch.float64 and state.is_contiguous()
+    assert action_out.dtype == torch.float64 and action_out.is_contiguous() and action_out.shape == (n, nu)
+    if noise is not None:
+        assert noise.dtype == torch.float32 and noise.is_contiguous() and noise.shape == (n, nu)
+    if mean_out is not None:
+        assert mean_out.dtype == torch.float32 and mean_out.is_contiguous() and mean_out.shape == (n, nu)
+
+
 def supported(policy_net) -> bool:
     """True when `policy_net` is a PolicyGaussian over a plain MLP with an activation the kernel implements."""
     net = getattr(policy_net, "net", None)
@@ -86,16 +102,9 @@ class FusedGaussianPolicy:
         S = state.shape[1]
         if H + S != self.in_dim:
             raise ValueError("context dim %d + state dim %d != policy input %d" % (H, S, self.in_dim))
-        assert ctx_rows.dtype == torch.float32 and ctx_rows.stride(2) == 1 and ctx_rows.stride(1) == H
-        assert t_idx.dtype == torch.int64 and t_idx.is_contiguous() and state.dtype == torch.float64 and state.is_contiguous()
-        assert action_out.dtype == torch.float64 and action_out.is_contiguous() and action_out.shape == (n, self.nu)
-        if noise is not None:
-            assert noise.dtype == torch.float32 and noise.is_contiguous() and noise.shape == (n, self.nu)
-        if mean_out is not None:
-            assert mean_out.dtype == torch.float32 and mean_out.is_contiguous() and mean_out.shape == (n, self.nu)
-        p = lambda t: C.c_void_p(t.data_ptr()) if t is not None else C.c_void_p(0)
-        L.check(self.lib.egp_policy_gaussian_f32(p(ctx_rows), int(ctx_rows.stride(0)), H, p(t_idx), p(state), S, n, self.desc,
-                                                 len(self.layers), self.act, p(self.log_std), p(noise), p(action_out), p(mean_out),
+        _check_io(ctx_rows, t_idx, state, action_out, noise, mean_out, self.nu)
+        L.check(self.lib.egp_policy_gaussian_f32(_ptr(ctx_rows), int(ctx_rows.stride(0)), H, _ptr(t_idx), _ptr(state), S, n, self.desc,
+                                                 len(self.layers), self.act, _ptr(self.log_std), _ptr(noise), _ptr(action_out), _ptr(mean_out),
                                                  L.current_stream()), "egp_policy_gaussian_f32")
         return action_out
 
@@ -105,12 +114,11 @@ class FusedGaussianPolicy:
         observations of (qpos, qvel) normalised with `zf_in` merged with the tile statistics `ctx.obs_zfilter_stats` left in
         `workspace`; y / y2 receive them, `zf_out` the merged statistics. `ctx`: the EgpContext of the model."""
         n, T, H = ctx_rows.shape
-        p = lambda t: C.c_void_p(t.data_ptr()) if t is not None else C.c_void_p(0)
-        L.check(self.lib.egp_policy_gaussian_filter_f32(ctx.handle, p(ctx_rows), int(ctx_rows.stride(0)), H, p(t_idx), p(qpos), p(qvel),
-                                                        p(ctx._phase_t(phase_t, n)), n,
-                                                        p(zf_in), p(zf_out), float(clip or 0.0), p(y), p(y2), p(workspace),
-                                                        C.cast(self.desc, C.c_void_p), len(self.layers), self.act, p(self.log_std), p(noise),
-                                                        p(action_out), p(mean_out), None, None, 0, L.current_stream()),
+        L.check(self.lib.egp_policy_gaussian_filter_f32(ctx.handle, _ptr(ctx_rows), int(ctx_rows.stride(0)), H, _ptr(t_idx), _ptr(qpos), _ptr(qvel),
+                                                        _ptr(ctx._phase_t(phase_t, n)), n,
+                                                        _ptr(zf_in), _ptr(zf_out), float(clip or 0.0), _ptr(y), _ptr(y2), _ptr(workspace),
+                                                        C.cast(self.desc, C.c_void_p), len(self.layers), self.act, _ptr(self.log_std), _ptr(noise),
+                                                        _ptr(action_out), _ptr(mean_out), None, None, 0, L.current_stream()),
                 "egp_policy_gaussian_filter_f32")
         return action_out
 
@@ -149,20 +157,13 @@ class FusedForecastPolicy(FusedGaussianPolicy):
         if state.shape[1] != self.S or H + self.Hs != self.in_dim:
             raise ValueError("state dim %d / context dim %d do not fit the cell (%d -> %d) and the policy input %d"
                              % (state.shape[1], H, self.S, self.Hs, self.in_dim))
-        assert ctx_rows.dtype == torch.float32 and ctx_rows.stride(2) == 1 and ctx_rows.stride(1) == H
-        assert t_idx.dtype == torch.int64 and t_idx.is_contiguous() and state.dtype == torch.float64 and state.is_contiguous()
+        _check_io(ctx_rows, t_idx, state, action_out, noise, mean_out, self.nu)
         for t in (h, c):
             assert t.dtype == torch.float32 and t.shape == (n, self.Hs) and t.stride(1) == 1 and t.stride(0) == h.stride(0) >= self.Hs
         assert h.data_ptr() != c.data_ptr()
-        assert action_out.dtype == torch.float64 and action_out.is_contiguous() and action_out.shape == (n, self.nu)
-        if noise is not None:
-            assert noise.dtype == torch.float32 and noise.is_contiguous() and noise.shape == (n, self.nu)
-        if mean_out is not None:
-            assert mean_out.dtype == torch.float32 and mean_out.is_contiguous() and mean_out.shape == (n, self.nu)
-        p = lambda t: C.c_void_p(t.data_ptr()) if t is not None else C.c_void_p(0)
-        L.check(self.lib.egp_policy_forecast_f32(p(ctx_rows), int(ctx_rows.stride(0)), H, p(t_idx), p(state), self.S, self.cell_desc,
-                                                 p(h), p(c), int(h.stride(0)), n, self.desc, len(self.layers), self.act, p(self.log_std),
-                                                 p(noise), p(action_out), p(mean_out), L.current_stream()), "egp_policy_forecast_f32")
+        L.check(self.lib.egp_policy_forecast_f32(_ptr(ctx_rows), int(ctx_rows.stride(0)), H, _ptr(t_idx), _ptr(state), self.S, self.cell_desc,
+                                                 _ptr(h), _ptr(c), int(h.stride(0)), n, self.desc, len(self.layers), self.act, _ptr(self.log_std),
+                                                 _ptr(noise), _ptr(action_out), _ptr(mean_out), L.current_stream()), "egp_policy_forecast_f32")
         return action_out
 
     def with_filter(self, *args, **kwargs):

@@ -662,10 +662,13 @@ def test_engine_follows_changing_inertia(ctx, skel, mode, monkeypatch):
 
 
 # ------------------------------------------------------------------------------------------------ fused policy step
-@pytest.mark.parametrize("act,hidden,n", [("relu", (300, 200), 517), ("tanh", (64,), 3), ("sigmoid", (130, 70, 33), 64)])
+@pytest.mark.parametrize("act,hidden,n", [("relu", (300, 200), 517), ("tanh", (64,), 3), ("sigmoid", (130, 70, 33), 64),
+                                          ("tanh", (330, 6), 5)])
 def test_fused_policy_step_matches_torch(act, hidden, n):
     """egp_policy_gaussian_f32 == cat(v_out[t], state) -> MLP -> action_mean -> mean + exp(log_std) * noise in torch
-    (float32; tolerance 2e-5 relative to the output scale: different summation order only)."""
+    (float32; tolerance 2e-5 relative to the output scale: different summation order only).
+    (330, 6): a hidden layer of two column chunks (> 5 x 64) whose width is no multiple of 4 -- the zeroed pad columns of its
+    last quad feed the next layer -- on two workgroups, the second ragged."""
     from egopose_amd.nets import MLP, PolicyGaussian
     from egopose_amd import policy_step
     torch.manual_seed(3)

@@ -175,6 +175,27 @@ def test_forecast_step_is_deterministic_and_position_independent(cfg_nets):
     assert all(torch.equal(x[:1], y) for x, y in zip(first, alone))
 
 
+# ------------------------------------------------------------------------------------------------ 4b. the shared MLP
+def test_forecast_step_and_plain_step_agree_bitwise_on_the_shared_mlp():
+    """Both kernels walk the MLP and the head with the same layer loop: the forecast step's h', handed to the plain step as its
+    state (float32 -> float64 -> float32 is exact) with the same context rows and noise, gives the same action and mean bit for
+    bit. 4 x 96 gate columns: two column chunks of the cell; hidden (330, 6): two chunks of a hidden layer and a zeroed pad quad;
+    n = 5: two workgroups, the second ragged."""
+    from egopose_amd import policy_step
+    H, S, Hs, nu, n = 5, 3, 96, 4, 5
+    vs, pol = _nets(S, Hs=Hs, H=H, hidden=(330, 6), nu=nu)
+    assert policy_step.supported_forecast(pol, vs)
+    fc = policy_step.FusedForecastPolicy(pol, vs, torch.device(DEV))
+    plain = policy_step.FusedGaussianPolicy(pol, torch.device(DEV))
+    d = _inputs(n, S, Hs=Hs, H=H, T=3, nu=nu)
+    h, c, act_f, mean_f = _step(fc, d)
+    assert not torch.equal(h, d["h"])
+    act_p, mean_p = torch.empty_like(act_f), torch.empty_like(mean_f)
+    plain(d["ctx"], d["t_idx"], h.double(), act_p, noise=d["noise"], mean_out=mean_p)
+    assert torch.equal(mean_p, mean_f) and torch.equal(act_p, act_f)
+    assert not torch.equal(act_f, mean_f.double())
+
+
 # ------------------------------------------------------------------------------------------------ 5. graph capture
 def test_forecast_step_replays_from_a_captured_graph(cfg_nets):
     """One step captured the way the rollout's `_ensure_static` does (warm-up on a side stream, a single-branch graph): three
