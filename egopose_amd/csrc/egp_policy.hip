@@ -67,17 +67,19 @@ constexpr int POL_R = 4, POL_NW = 4, POL_PF = 2;
 
 // The dynamic LDS of a workgroup, for the kernels and for the host's byte count (float offsets; cur is at 0):
 //   cur[R][xs] | nxt[R][xs] | part[NW][R][POL_PS] | every layer's bias | exp(log_std) | the rows' noise | the kernel's own tail:
-//   the filter's merged (mean, 1 / std) doubles behind a pad to an even float (the pad float is always reserved), or the cell's c rows
+//   the cell's c rows (`cell_floats` = R x hidden size; the forecast step), then the filter's merged (mean, 1 / std) doubles
+//   (`ms_doubles` = 2 x obs dim) behind a pad to an even float -- 8-byte aligned; the pad float is always reserved
 struct PolCarve {
-    int nxt, part, bias, sd, noise, tail, ms;
+    int nxt, part, bias, sd, noise, tail, ms, end;
 };
 template <int R, int NW>
-__host__ __device__ __forceinline__ PolCarve pol_carve(int xs, int sum_out4, int out_last) {
+__host__ __device__ __forceinline__ PolCarve pol_carve(int xs, int sum_out4, int out_last, int cell_floats = 0, int ms_doubles = 0) {
     const int out4 = (out_last + 3) & ~3;
     PolCarve c;
     c.nxt = R * xs; c.part = 2 * R * xs; c.bias = c.part + NW * R * POL_PS;
     c.sd = c.bias + sum_out4; c.noise = c.sd + out4; c.tail = c.noise + R * out4;
-    c.ms = c.tail + ((R * out4) & 1);
+    c.ms = (c.tail + cell_floats + 1) & ~1;
+    c.end = c.tail + cell_floats + 1 + 2 * ms_doubles;
     return c;
 }
 
@@ -612,18 +614,24 @@ __global__ __launch_bounds__(256) void k_policy_gaussian_w4(const float *__restr
 // gathered into `nxt` -- the MLP's input -- and h' / c' back to the caller's rows. Layers 1 .. L.n - 1 are the MLP and the head.
 // In place: a workgroup's h / c rows are read in the prologue (into LDS) and written in layer 0's epilogue, behind barriers;
 // no workgroup touches another's rows, and rows >= n are neither read nor written.
-template <int R, int NW, int PF>
+// FILTER (egp_policy_forecast_filter_f32): the state columns are the observations of (qpos, qvel) pushed through the filter's apply
+// pass on their way into `cur` (see PolFilter) -- k_zf_apply's two phases in its plain form: every workgroup merges the tile
+// partials into the running statistics for itself (F.n_tiles == 0: the statistics as they stand, the frozen filter of an
+// evaluation), one column per thread and round, then normalises its rows element by element. `state` is unused then.
+template <int R, int NW, int PF, bool FILTER>
 __device__ __forceinline__ void forecast_body(const float *__restrict__ ctx_rows, long ctx_row_stride, int ctx_dim,
                                               const long long *__restrict__ t_idx, const double *__restrict__ state, int state_dim,
                                               float *h_io, float *c_io, long hc_stride, int hs, int n,
                                               const PolLayers &L, int act_kind, int xs, const float *__restrict__ log_std,
-                                              const float *__restrict__ noise, double *__restrict__ action, float *__restrict__ mean_out) {
+                                              const float *__restrict__ noise, double *__restrict__ action, float *__restrict__ mean_out,
+                                              const PolFilter &F) {
     constexpr int T = NW * 64;
-    extern __shared__ __attribute__((aligned(16))) float s_f[];     // see PolCarve; the tail: c[R][hs]
+    extern __shared__ __attribute__((aligned(16))) float s_f[];     // see PolCarve; the tail: c[R][hs], then the filter's mean, 1 / std
     const int out_last = L.out_dim[L.n - 1];
-    const PolCarve lds = pol_carve<R, NW>(xs, L.sum_out4, out_last);
+    const PolCarve lds = pol_carve<R, NW>(xs, L.sum_out4, out_last, R * hs, FILTER ? 2 * state_dim : 0);
     float *cur = s_f, *nxt = s_f + lds.nxt, *part = s_f + lds.part;
     float *s_bias = s_f + lds.bias, *s_sd = s_f + lds.sd, *s_noise = s_f + lds.noise, *s_c = s_f + lds.tail;
+    double *s_ms = reinterpret_cast<double *>(s_f + lds.ms);
     const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int r0 = blockIdx.x * R;
     const int in_c = state_dim + hs, in_cp = (in_c + 3) & ~3;        // the cell's input [s | h]
@@ -639,14 +647,42 @@ __device__ __forceinline__ void forecast_body(const float *__restrict__ ctx_rows
     // the cell's own first blocks
     PolStage<PF> st;
     pol_preload_pass<NW, PF>(st, L, 0, 0, wave, lane);
+    if constexpr (FILTER) {         // k_zf_apply's first phase: the merged statistics, every workgroup for itself
+        const int dim = state_dim;
+        for (int c = tid; c < dim; c += T) {
+            double cnt, mean, S;
+            egp::zf_merge_column(dim, F.n_tiles, F.ws, F.st_in, c, cnt, mean, S);
+            if (blockIdx.x == 0 && F.st_out) {
+                F.st_out[1 + c] = mean;
+                F.st_out[1 + dim + c] = S;
+                if (c == 0) F.st_out[0] = cnt;
+            }
+            const double var = cnt > 1.0 ? S / (cnt - 1.0) : mean * mean;
+            s_ms[c] = mean;
+            s_ms[dim + c] = 1.0 / (sqrt(var) + 1e-8);
+        }
+        __syncthreads();
+    }
     // inputs: cur = [s | h | 0], nxt = [ctx | (h' later) | 0], s_c = c; rows >= n are zeros
     for (int k = tid; k < in_cp; k += T) {
 #pragma unroll
         for (int r = 0; r < R; ++r) {
             const int row = r0 + r;
             float v = 0.0f;
-            if (row < n && k < in_c)
-                v = k < state_dim ? (float)state[(long)row * state_dim + k] : h_io[(long)row * hc_stride + (k - state_dim)];
+            if (row < n && k < in_c) {
+                if (k >= state_dim) {
+                    v = h_io[(long)row * hc_stride + (k - state_dim)];
+                } else if constexpr (FILTER) {        // k_zf_apply's second phase for this element
+                    double x = ((double)F.src.at(row, k) - s_ms[k]) * s_ms[state_dim + k];
+                    if (F.clip > 0.0) x = fmin(fmax(x, -F.clip), F.clip);
+                    const long e = (long)row * state_dim + k;
+                    F.y[e] = x;
+                    if (F.y2) F.y2[e] = x;
+                    v = (float)x;
+                } else {
+                    v = (float)state[(long)row * state_dim + k];
+                }
+            }
             cur[r * xs + k] = v;
         }
     }
@@ -684,15 +720,15 @@ __device__ __forceinline__ void forecast_body(const float *__restrict__ ctx_rows
                                 noise, action, mean_out, PolCell{s_c, h_io, c_io, hc_stride, hs, ctx_dim});
 }
 
-template <int R, int PF>
+template <int R, int PF, bool FILTER>
 __global__ __launch_bounds__(256) void k_policy_forecast_w4(const float *__restrict__ ctx_rows, long ctx_row_stride, int ctx_dim,
                                                             const long long *__restrict__ t_idx, const double *__restrict__ state,
                                                             int state_dim, float *h_io, float *c_io, long hc_stride, int hs, int n,
                                                             PolLayers L, int act_kind, int xs, const float *__restrict__ log_std,
                                                             const float *__restrict__ noise, double *__restrict__ action,
-                                                            float *__restrict__ mean_out) {
-    forecast_body<R, 4, PF>(ctx_rows, ctx_row_stride, ctx_dim, t_idx, state, state_dim, h_io, c_io, hc_stride, hs, n, L, act_kind, xs,
-                            log_std, noise, action, mean_out);
+                                                            float *__restrict__ mean_out, PolFilter F) {
+    forecast_body<R, 4, PF, FILTER>(ctx_rows, ctx_row_stride, ctx_dim, t_idx, state, state_dim, h_io, c_io, hc_stride, hs, n, L, act_kind, xs,
+                                    log_std, noise, action, mean_out, F);
 }
 
 }  // namespace
@@ -753,10 +789,10 @@ static int pol_layer_table(const egp_mlp_layer *front, const egp_mlp_layer *laye
     return EGP_OK;
 }
 
-// Activation row stride and dynamic LDS bytes of a launch: PolCarve's ranges + `tail_bytes` of the kernel's own.
-static int pol_lds(const PolLayers &L, int kmax, size_t tail_bytes, int *xs, size_t *lds) {
+// Activation row stride and dynamic LDS bytes of a launch: PolCarve's ranges, the kernel's own tail included (see pol_carve).
+static int pol_lds(const PolLayers &L, int kmax, int cell_floats, int ms_doubles, int *xs, size_t *lds) {
     *xs = ((kmax + 31) & ~31) + 4;                    // rows 0..3 of a broadcast read sit on different banks
-    *lds = (size_t)pol_carve<POL_R, POL_NW>(*xs, L.sum_out4, L.out_dim[L.n - 1]).tail * sizeof(float) + tail_bytes;
+    *lds = (size_t)pol_carve<POL_R, POL_NW>(*xs, L.sum_out4, L.out_dim[L.n - 1], cell_floats, ms_doubles).end * sizeof(float);
     EGP_REQUIRE(*lds <= 150 * 1024, "layers too wide for the LDS tile");
     return EGP_OK;
 }
@@ -785,7 +821,7 @@ static int policy_launch(const float *ctx_rows, int64_t ctx_row_stride, int32_t 
     size_t lds;
     if (int rc = pol_layer_table(nullptr, layers, n_layers, ctx_dim + state_dim, "layer dims do not chain", L, &kmax)) return rc;
     // the tail: the pad float in front of the doubles, and with the filter its merged mean | 1 / std
-    if (int rc = pol_lds(L, kmax, sizeof(float) + (flt ? (size_t)2 * state_dim * sizeof(double) : 0), &xs, &lds)) return rc;
+    if (int rc = pol_lds(L, kmax, 0, flt ? 2 * state_dim : 0, &xs, &lds)) return rc;
     const dim3 grid((n + POL_R - 1) / POL_R), block(POL_NW * 64);
     const PolFilter F = flt ? *flt : PolFilter{};
     const unsigned *ssrc = stage_bytes ? (const unsigned *)stage_src : nullptr;
@@ -808,14 +844,14 @@ extern "C" int egp_policy_gaussian_f32(const float *ctx_rows, int64_t ctx_row_st
 // The ego_forecast policy step: one step of the state LSTM cell (models/rnn.py:29-36, models/video_forecast_net.py:88-93), then
 // [ctx | h'] -> MLP -> Gaussian head as above, h' / c' written back in place. `cell` is the gate layer in egp_mlp_layer form
 // (include/egopose_hip.h gives the column order); see forecast_body.
-extern "C" int egp_policy_forecast_f32(const float *ctx_rows, int64_t ctx_row_stride, int32_t ctx_dim, const int64_t *t_idx,
-                                       const double *state, int32_t state_dim, const egp_mlp_layer *cell, float *h, float *c,
-                                       int64_t hc_row_stride, int32_t n, const egp_mlp_layer *layers, int32_t n_layers,
-                                       int32_t activation, const float *log_std, const float *noise, double *action, float *mean_out,
-                                       void *stream) {
+static int forecast_launch(const float *ctx_rows, int64_t ctx_row_stride, int32_t ctx_dim, const int64_t *t_idx,
+                           const double *state, int32_t state_dim, const egp_mlp_layer *cell, float *h, float *c,
+                           int64_t hc_row_stride, int32_t n, const egp_mlp_layer *layers, int32_t n_layers,
+                           int32_t activation, const float *log_std, const float *noise, double *action, float *mean_out,
+                           void *stream, const PolFilter *flt = nullptr) {
     EGP_REQUIRE(n >= 0, "n < 0");
     if (n == 0) return EGP_OK;
-    EGP_REQUIRE(state && cell && h && c && h != c && layers && action, "NULL pointer (or h == c)");
+    EGP_REQUIRE((state || flt) && cell && h && c && h != c && layers && action, "NULL pointer (or h == c)");
     EGP_REQUIRE(ctx_dim >= 0 && (ctx_dim == 0 || (ctx_rows && t_idx)), "bad context");
     EGP_REQUIRE(!noise || log_std, "noise needs log_std");
     EGP_REQUIRE(n_layers >= 1 && n_layers + 1 <= POL_MAX_LAYERS, "1..7 layers (hidden layers + output layer) behind the cell");
@@ -829,11 +865,51 @@ extern "C" int egp_policy_forecast_f32(const float *ctx_rows, int64_t ctx_row_st
     int kmax, xs;
     size_t lds;
     if (int rc = pol_layer_table(cell, layers, n_layers, ctx_dim + hs, "layer dims do not chain (first layer: ctx_dim + hidden size)", L, &kmax)) return rc;
-    if (int rc = pol_lds(L, kmax, (size_t)POL_R * hs * sizeof(float), &xs, &lds)) return rc;      // the tail: the cell's c rows
-    k_policy_forecast_w4<POL_R, POL_PF><<<dim3((n + POL_R - 1) / POL_R), dim3(POL_NW * 64), lds, (hipStream_t)stream>>>(
-        ctx_rows, (long)ctx_row_stride, ctx_dim, (const long long *)t_idx, state, state_dim, h, c, (long)hc_row_stride, hs, n, L, activation, xs,
-        log_std, noise, action, mean_out);
+    // the tail: the cell's c rows, and with the filter its merged mean | 1 / std
+    if (int rc = pol_lds(L, kmax, POL_R * hs, flt ? 2 * state_dim : 0, &xs, &lds)) return rc;
+    const dim3 grid((n + POL_R - 1) / POL_R), block(POL_NW * 64);
+    const PolFilter F = flt ? *flt : PolFilter{};
+#define POL_GO(FLT) k_policy_forecast_w4<POL_R, POL_PF, FLT><<<grid, block, lds, (hipStream_t)stream>>>(                                         \
+        ctx_rows, (long)ctx_row_stride, ctx_dim, (const long long *)t_idx, state, state_dim, h, c, (long)hc_row_stride, hs, n, L, activation, xs, \
+        log_std, noise, action, mean_out, F)
+    if (flt) POL_GO(true); else POL_GO(false);
+#undef POL_GO
     return pol_launched("k_policy_forecast");
+}
+
+extern "C" int egp_policy_forecast_f32(const float *ctx_rows, int64_t ctx_row_stride, int32_t ctx_dim, const int64_t *t_idx,
+                                       const double *state, int32_t state_dim, const egp_mlp_layer *cell, float *h, float *c,
+                                       int64_t hc_row_stride, int32_t n, const egp_mlp_layer *layers, int32_t n_layers,
+                                       int32_t activation, const float *log_std, const float *noise, double *action, float *mean_out,
+                                       void *stream) {
+    return forecast_launch(ctx_rows, ctx_row_stride, ctx_dim, t_idx, state, state_dim, cell, h, c, hc_row_stride, n, layers, n_layers, activation,
+                           log_std, noise, action, mean_out, stream);
+}
+
+// egp_policy_forecast_f32 with the filter's apply pass in front (see PolFilter and forecast_body): the cell's state input is the
+// observation of (qpos, qvel), normalised with `zf_in` merged with the tile statistics that egp_obs_zfilter_stats_f64 left in
+// `zf_workspace` -- exactly what egp_obs_zfilter_apply_f64 followed by egp_policy_forecast_f32 on y2 computes -- or, with
+// zf_workspace == NULL, with `zf_in` as it stands (the frozen filter of an evaluation: ZFilter.__call__(x, update=False)).
+extern "C" int egp_policy_forecast_filter_f32(egp_ctx *ctx, const float *ctx_rows, int64_t ctx_row_stride, int32_t ctx_dim, const int64_t *t_idx,
+                                              const double *qpos, const double *qvel, const int32_t *phase_t, int32_t n,
+                                              const double *zf_in, double *zf_out, double clip, double *y, double *y2, const void *zf_workspace,
+                                              const egp_mlp_layer *cell, float *h, float *c, int64_t hc_row_stride,
+                                              const egp_mlp_layer *layers, int32_t n_layers, int32_t activation, const float *log_std,
+                                              const float *noise, double *action, float *mean_out, void *stream) {
+    EGP_REQUIRE(n >= 0, "n < 0");
+    if (n == 0) return EGP_OK;
+    EGP_REQUIRE(ctx && qpos && qvel && zf_in && y && zf_in != zf_out, "NULL pointer / zf_out must differ from zf_in");
+    EGP_REQUIRE(!zf_workspace || (zf_out && n <= 64 * egp::ZF_FUSED_TILES),
+                "merged statistics: zf_out is required and at most egp_obs_zfilter_split_max_rows() rows");
+    EGP_REQUIRE(!ctx->dm.obs_phase || phase_t, "the model has obs_phase: phase_t (the rows' cur_t) is required");
+    const int dim = ctx->dm.obs_dim;
+    int rpt, nt = 0;
+    if (zf_workspace) egp::zf_tiling(n, &rpt, &nt);
+    PolFilter f;
+    f.src = egp::ZfSrc<double>{nullptr, qpos, qvel, ctx->dm.nq, ctx->dm.nv, dim, egp::obs_opt_of(ctx->dm), phase_t};
+    f.st_in = zf_in; f.st_out = zf_out; f.ws = (const double *)zf_workspace; f.n_tiles = nt; f.clip = clip; f.y = y; f.y2 = y2;
+    return forecast_launch(ctx_rows, ctx_row_stride, ctx_dim, t_idx, nullptr, dim, cell, h, c, hc_row_stride, n, layers, n_layers, activation,
+                           log_std, noise, action, mean_out, stream, &f);
 }
 
 extern "C" int egp_policy_gaussian_staged_f32(const float *ctx_rows, int64_t ctx_row_stride, int32_t ctx_dim, const int64_t *t_idx,

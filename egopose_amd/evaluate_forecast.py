@@ -1,0 +1,294 @@
+"""Evaluation driver of the ego_forecast policy: every forecast window of every take, batched onto lockstep env slots.
+
+Restates the save mode of ego_pose/ego_forecast_eval.py:95-204 and the `--mode stats` part of ego_pose/eval_forecast.py:29-114.
+The reference evaluates the windows `start = m, 2m, 3m, ... while start + test_len <= take_len` (m = cfg.fr_margin,
+test_len = cfg.env_episode_len) of every take one after another; a window is a fixed-length episode that never breaks on
+`fail`, has no reset inside, no exploration noise and a frozen observation filter (`running_state(x, update=False)`). So the
+windows run here as the slots of `env.batched(N)` in strict lockstep, in passes of N; a tick is
+
+    record qpos -> [observation -> frozen normalisation -> state-LSTM cell -> MLP -> mean action] -> env-step
+
+with the bracket one launch (`FusedForecastPolicy.with_filter(..., workspace=None)`, egp_policy_forecast_filter_f32).
+
+A window starts from the expert's state (`gt_init`) or from the ego_mimic result of the same take (ego_forecast_eval.py:107-120,
+`window_init_state`). The value nets are NOT evaluated: the reference only logs their output, which does not enter the results.
+Rendering (`--render`, `--mode vis`, `--show-noise`), the per-step reward log (`--verbose`) and the `*_wild` scripts are out of
+scope.
+"""
+from __future__ import annotations
+
+import os
+import pickle
+import time
+
+import numpy as np
+
+from . import metrics
+
+
+# ---------------------------------------------------------------------- ego_forecast_eval.py:185-196
+def window_plan(take_lens, fr_margin, test_len):
+    """(take_ind[W], start_ind[W]) of every evaluated window: per take start = m, 2m, ... while start + test_len <= take_len."""
+    m, test_len = int(fr_margin), int(test_len)
+    take_ind, start_ind = [], []
+    for i, take_len in enumerate(take_lens):
+        start = m
+        while start + test_len <= int(take_len):
+            take_ind.append(i)
+            start_ind.append(start)
+            start += m
+    return np.asarray(take_ind, dtype=np.int64), np.asarray(start_ind, dtype=np.int64)
+
+
+# ---------------------------------------------------------------------- ego_forecast_eval.py:107-133
+def window_init_state(expert_qpos, expert_qvel, start, fr_margin, test_len, em_traj=None, em_vel=None, em_off=0):
+    """Seat state and history rows of the window starting at frame `start` of a take -> (qpos, qvel, history[m, nq], miss_len).
+
+    em_traj is None (`gt_init`): the expert's state at `start`, history = the expert's rows [start - m, start).
+    Otherwise em_traj / em_vel are the ego_mimic result of the take (its row i is take frame i + em_off, em_off = the ego_mimic
+    config's fr_margin): the slice [max(0, start - m - em_off), start + test_len - em_off) of it, synced to the expert's pose at
+    frame start - m when it reaches back that far (`sync_traj`); `miss_len` rows are missing from it (at its front for an early
+    window; the reference's arithmetic treats a slice cut short at the take's end the same way, and so does this). The seat
+    state is row m - miss_len, history row t the expert's for t < miss_len and slice row t - miss_len after that."""
+    m, start, test_len = int(fr_margin), int(start), int(test_len)
+    history = np.array(expert_qpos[start - m:start], dtype=np.float64, copy=True)
+    if em_traj is None:
+        return np.array(expert_qpos[start], float, copy=True), np.array(expert_qvel[start], float, copy=True), history, 0
+    lo = start - m - int(em_off)
+    state_pred = np.asarray(em_traj, float)[max(0, lo):start + test_len - int(em_off)]
+    vel_pred = np.asarray(em_vel, float)[max(0, lo):start + test_len - int(em_off)]
+    miss_len = m + test_len - state_pred.shape[0]
+    if lo >= 0:
+        state_pred, vel_pred = metrics.sync_traj(state_pred, vel_pred, expert_qpos[start - m])
+    ind = m - miss_len
+    qpos, qvel = state_pred[ind].copy(), vel_pred[ind].copy()
+    for t in range(m):
+        if not t < miss_len:
+            history[t] = state_pred[t - miss_len]
+    return qpos, qvel, history, miss_len
+
+
+def result_path(cfg, it, data="test", gt_init=False):
+    return "%s/iter_%04d_%s%s.p" % (cfg.result_dir, it, data, "_gt" if gt_init else "")
+
+
+class ForecastEvaluator:
+    """`run()` -> (results, meta) in the reference's pickle layout: results = {'traj_pred': {take: [n_win, m + test_len, nq]},
+    'traj_orig': ...}, meta = {'algo': 'ego_forecast'}. `em_res` (+ `em_off`): the ego_mimic results the windows start from
+    unless `gt_init`. `keep_trace`: `self.trace` keeps per window the actions, the filtered states the policy saw, the qvel that
+    goes with each recorded qpos, and the plan (take_ind, start_ind). `self.timing`: wall seconds of the last run, split into
+    the wait for the host physics and the rest."""
+
+    CTX_BATCH = 1024         # windows per launch of the video net
+
+    def __init__(self, cfg, env, policy_net, policy_vs_net, running_state=None, gt_init=False, em_res=None, em_off=0, num_envs=1024,
+                 device_index=0, n_threads=None, keep_trace=False, logger=None):
+        if not gt_init and em_res is None:
+            raise ValueError("ego_mimic results (em_res) are needed unless gt_init")
+        if running_state is not None and not (running_state.demean and running_state.destd):
+            raise NotImplementedError("running_state without demean / destd")
+        self.cfg, self.env = cfg, env
+        self.policy_net, self.policy_vs_net = policy_net, policy_vs_net
+        self.running_state = running_state
+        self.gt_init, self.em_res, self.em_off = bool(gt_init), em_res, int(em_off)
+        self.num_envs, self.device_index, self.n_threads = int(num_envs), int(device_index), n_threads
+        self.keep_trace, self.logger = bool(keep_trace), logger
+        self.trace, self.timing = None, {}
+        for net in (policy_net, policy_vs_net):
+            net.eval()
+        policy_vs_net.set_mode("test")
+
+    # ------------------------------------------------------------------ host side of a run: plan, seat states, history rows
+    def plan(self, takes=None):
+        cfg, env = self.cfg, self.env
+        m, T = int(cfg.fr_margin), int(cfg.env_episode_len)
+        take_ind, start_ind = window_plan([c.shape[0] if takes is None or env.expert_list[i] in takes else 0 for i, c in enumerate(env.cnn_feat)], m, T)
+        W = len(take_ind)
+        nq, nv = env.skel.nq, env.skel.nv
+        qpos0, qvel0, hist = np.empty((W, nq)), np.empty((W, nv)), np.empty((W, m, nq))
+        miss = np.zeros(W, np.int64)
+        for w, (e, s) in enumerate(zip(take_ind, start_ind)):
+            ex = env.expert_arr[e]
+            if s + T > ex["qpos"].shape[0]:
+                raise ValueError("take %s: the expert has fewer frames than the features" % env.expert_list[e])
+            if self.gt_init:
+                em_t = em_v = None
+            else:
+                take = env.expert_list[e]
+                em_t, em_v = self.em_res["traj_pred"][take], self.em_res["vel_pred"][take]
+            qpos0[w], qvel0[w], hist[w], miss[w] = window_init_state(ex["qpos"], ex["qvel"], s, m, T, em_t, em_v, self.em_off)
+        return take_ind, start_ind, qpos0, qvel0, hist, miss
+
+    # ------------------------------------------------------------------ ego_forecast_eval.py:95-204, batched
+    def run(self, takes=None):
+        """Evaluate every window of every take of the env's expert list (or of `takes`) -> (results, meta)."""
+        import torch
+        from . import policy_step
+        cfg, env = self.cfg, self.env
+        m, T = int(cfg.fr_margin), int(cfg.env_episode_len)
+        t_all = time.time()
+        take_ind, start_ind, qpos0, qvel0, hist, miss = self.plan(takes)
+        W = len(take_ind)
+        N = self.num_envs
+        sim = env.batched(N, self.device_index, self.n_threads, 1)
+        ctx, eng, ex = sim.ctx, sim.engine, sim.experts
+        dev = torch.device("cuda", ctx.device)
+        vs = self.policy_vs_net
+        if not policy_step.supported_forecast(self.policy_net, vs):
+            raise NotImplementedError("the forecast evaluation needs the HIP policy step: a float32 PolicyGaussian over an MLP behind a "
+                                      "VideoForecastNet with an LSTMCell state net")
+        nq, nv, nu, od = ctx.nq, ctx.nv, ctx.nu, ctx.obs_dim
+        f64 = torch.float64
+        pred = np.empty((W, m + T, nq))
+        orig = np.empty((W, m + T, nq))
+        for w, (e, s) in enumerate(zip(take_ind, start_ind)):
+            orig[w] = env.expert_arr[e]["qpos"][s - m:s + T]
+        pred[:, :m] = hist
+        failed = np.zeros(W, bool)
+        tr_act, tr_st, tr_qv = (np.empty((W, T, nu)), np.empty((W, T, od)), np.empty((W, T, nv))) if self.keep_trace else (None, None, None)
+        tm = {"phys_wait": 0.0, "passes": 0, "windows": W, "ticks": 0}
+        with torch.no_grad(), torch.cuda.device(dev):
+            fused = policy_step.FusedForecastPolicy(self.policy_net, vs, dev)
+            vs.attach_feature_table(ex.cnn_table(dev, torch.float32), ex.cnn_offset)
+            vs.check_windows(take_ind, start_ind, 0)
+            zf_in, clip = None, 0.0
+            if self.running_state is not None:
+                zf_in, clip = self.running_state.to_device_state(dev), float(self.running_state.clip or 0.0)
+            traj = torch.zeros(T, N, nq, dtype=f64, device=dev)
+            qv = torch.zeros(T, N, nv, dtype=f64, device=dev) if self.keep_trace else None
+            actions = torch.zeros(T, N, nu, dtype=f64, device=dev)
+            states = torch.zeros(T, N, od, dtype=f64, device=dev)
+            v_out = torch.zeros(N, 1, vs.v_hdim, dtype=torch.float32, device=dev)
+            h = torch.zeros(N, vs.s_hdim, dtype=torch.float32, device=dev)
+            c = torch.zeros_like(h)
+            t_idx = torch.zeros(N, dtype=torch.int64, device=dev)
+            phase = torch.arange(T, dtype=torch.int32, device=dev).unsqueeze(1).expand(T, N).contiguous() if ctx.obs_phase else None
+            lb = ex.head_height_lb
+            # the windows' video contexts, as LockstepRollout._draw_episodes computes them for forecast episodes: in batches whose
+            # size does not follow the slot count (the LSTM kernels' tiling follows the batch size, and a window's forecast must
+            # not depend on how many slots it was evaluated with)
+            ctx_all = torch.empty(W, vs.v_hdim, dtype=torch.float32, device=dev)
+            for w0 in range(0, W, self.CTX_BATCH):
+                sl = slice(w0, min(W, w0 + self.CTX_BATCH))
+                e_d, s_d = torch.as_tensor(take_ind[sl], device=dev), torch.as_tensor(start_ind[sl], device=dev)
+                ctx_all[sl] = vs.context(vs.window_features(e_d, s_d))
+            for w0 in range(0, W, N):
+                k = min(N, W - w0)
+                sl = slice(w0, w0 + k)
+                ids = np.arange(k)
+                q0, v0 = qpos0[sl], qvel0[sl]
+                if w0 == 0 and k < N:             # slots no window ever lands on: a valid state all the same (they are never stepped)
+                    ids = np.arange(N)
+                    q0, v0 = np.concatenate((q0, np.repeat(q0[:1], N - k, 0))), np.concatenate((v0, np.repeat(v0[:1], N - k, 0)))
+                eng.reset(ids, q0, v0)
+                h.zero_(); c.zero_()
+                v_out[:k, 0] = ctx_all[sl]
+                active = np.zeros(N, np.int32)
+                active[:k] = 1
+                for t in range(T):
+                    traj[t, :k].copy_(eng.qpos[:k])
+                    if qv is not None:
+                        qv[t, :k].copy_(eng.qvel[:k])
+                    fused.with_filter(ctx, v_out[:k], t_idx[:k], eng.qpos[:k], eng.qvel[:k], zf_in, None, clip, states[t, :k], None, None,
+                                      h[:k], c[:k], actions[t, :k], phase_t=None if phase is None else phase[t, :k])
+                    ev = torch.cuda.Event()
+                    ev.record()
+                    eng.step_async(0, actions[t], active, ev)
+                    t0 = time.time()
+                    eng.wait(0)
+                    tm["phys_wait"] += time.time() - t0
+                    failed[sl] |= np.asarray(eng.head_z[:k]) < lb[take_ind[sl]] - 0.1          # (logged only: the window runs on)
+                torch.cuda.synchronize(dev)
+                pred[sl, m:] = traj[:, :k].transpose(0, 1).cpu().numpy()
+                if self.keep_trace:
+                    tr_act[sl] = actions[:, :k].transpose(0, 1).cpu().numpy()
+                    tr_st[sl] = states[:, :k].transpose(0, 1).cpu().numpy()
+                    tr_qv[sl] = qv[:, :k].transpose(0, 1).cpu().numpy()
+                tm["passes"] += 1
+                tm["ticks"] += T
+        if self.logger is not None:
+            for w in np.nonzero(failed)[0]:
+                self.logger.info("fail - expert_ind: %d, start_ind %d" % (take_ind[w], start_ind[w]))
+        traj_pred, traj_orig = {}, {}
+        for i, take in enumerate(env.expert_list):
+            sel = take_ind == i
+            if sel.any():                          # (a take too short for one window has no entry)
+                traj_pred[take], traj_orig[take] = pred[sel], orig[sel]
+        self.failed = failed
+        self.miss_len = miss
+        if self.keep_trace:
+            self.trace = dict(actions=tr_act, states=tr_st, qvel=tr_qv, take_ind=take_ind, start_ind=start_ind)
+        tm["total"] = time.time() - t_all
+        tm["rest"] = tm["total"] - tm["phys_wait"]
+        self.timing = tm
+        return {"traj_pred": traj_pred, "traj_orig": traj_orig}, {"algo": "ego_forecast"}
+
+    def save(self, results, meta, it, data="test"):
+        path = result_path(self.cfg, it, data, self.gt_init)
+        os.makedirs(os.path.dirname(path), exist_ok=True)
+        with open(path, "wb") as f:
+            pickle.dump((results, meta), f)
+        return path
+
+
+def build_parser():
+    import argparse
+    ap = argparse.ArgumentParser(prog="python -m egopose_amd.evaluate_forecast")
+    ap.add_argument("--cfg", default="subject_03")
+    ap.add_argument("--iter", type=int, default=0)
+    ap.add_argument("--data", default="test")
+    ap.add_argument("--gt-init", action="store_true")
+    ap.add_argument("--num-envs", type=int, default=1024)
+    ap.add_argument("--gpu-index", type=int, default=0)
+    return ap
+
+
+def main(argv=None):
+    """`python -m egopose_amd.evaluate_forecast --cfg subject_03 --iter N --data test [--gt-init] [--num-envs 1024] [--gpu-index 0]`:
+    ego_forecast_eval.py in save mode (checkpoint loading: :57-79) followed by the statistics of eval_forecast.py (--mode stats)."""
+    import copy
+    import torch
+    from .config import Config as EgoMimicConfig, ForecastConfig
+    from .env import HumanoidEnv
+    from .nets import MLP, PolicyGaussian, VideoForecastNet
+    from .zfilter import load_reference_pickle
+    args = build_parser().parse_args(argv)
+    cfg = ForecastConfig(args.cfg, create_dirs=False)
+    cfg.random_cur_t = False
+    cfg.env_init_noise = 0.0
+    dev = torch.device("cuda", args.gpu_index)
+    env = HumanoidEnv(cfg)
+    env.seed(cfg.seed)
+    env.load_experts(cfg.takes[args.data], cfg.expert_feat_file, cfg.cnn_feat_file)
+    cnn_dim = env.cnn_feat[0].shape[-1]
+    sd, ad = env.observation_space.shape[0], env.action_space.shape[0]
+    policy_vs = VideoForecastNet(cnn_dim, sd, cfg.policy_v_hdim, cfg.fr_margin, cfg.policy_v_net, cfg.policy_v_net_param, cfg.policy_s_hdim,
+                                 cfg.policy_s_net, cfg.policy_dyn_v)
+    policy = PolicyGaussian(MLP(policy_vs.out_dim, cfg.policy_hsize, cfg.policy_htype), ad, log_std=cfg.log_std, fix_std=cfg.fix_std)
+    with open("%s/iter_%04d.p" % (cfg.model_dir, args.iter), "rb") as f:
+        cp = load_reference_pickle(f)
+    policy.load_state_dict(cp["policy_dict"])
+    policy_vs.load_state_dict(cp["policy_vs_dict"])
+    for net in (policy, policy_vs):
+        net.to(dev, torch.float32)
+    em_res, em_off = None, 0
+    if not args.gt_init:
+        em_cfg = EgoMimicConfig(cfg.ego_mimic_cfg, create_dirs=False)
+        with open("%s/iter_%04d_%s.p" % (em_cfg.result_dir, cfg.ego_mimic_iter, args.data), "rb") as f:
+            em_res, _ = pickle.load(f)
+        em_off = em_cfg.fr_margin
+    ev = ForecastEvaluator(cfg, env, policy, policy_vs, running_state=cp["running_state"], gt_init=args.gt_init, em_res=em_res, em_off=em_off,
+                           num_envs=args.num_envs, device_index=args.gpu_index)
+    results, meta = ev.run()
+    path = ev.save(results, meta, args.iter, args.data)
+    print("saved results to %s (%d windows, %.2f s, %.2f s of it waiting for the physics)"
+          % (path, ev.timing["windows"], ev.timing["total"], ev.timing["phys_wait"]))
+    stats = copy.deepcopy(results)
+    metrics.remove_noisy_hands(stats)
+    for horizon in (30, 90):
+        metrics.compute_forecast_metrics(stats, cfg.fr_margin, horizon, verbose=True)
+    env.close()
+
+
+if __name__ == "__main__":
+    main()

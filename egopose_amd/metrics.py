@@ -2,8 +2,9 @@
 
 Mirrors /root/reference/ego_pose/utils/metrics.py:5-36 (get_joint_angles / get_joint_vels / get_joint_accels /
 get_mean_dist / get_mean_abs), the aggregation loop of ego_pose/eval_pose.py:31-69 (compute_metrics) and the two
-trajectory helpers the eval scripts use (utils/tools.py:71-75 align_human_state, ego_pose/utils/tools.py:35-40
-remove_noisy_hands). Quaternions are (w, x, y, z) as everywhere in the reference (utils/transformation.py).
+trajectory helpers the eval scripts use (utils/tools.py:71-75 align_human_state, ego_pose/utils/tools.py:18-32 sync_traj,
+:35-40 remove_noisy_hands), and the forecast statistics of ego_pose/eval_forecast.py:29-98 (compute_forecast_metrics,
+forecast_err_vs_horizon). Quaternions are (w, x, y, z) as everywhere in the reference (utils/transformation.py).
 These run once per evaluated take on a few thousand frames; they are not on the rollout hot path.
 """
 from __future__ import annotations
@@ -136,6 +137,48 @@ def compute_metrics(results, dt=1.0 / 30.0, algo=None, verbose=False):
     return out
 
 
+# ------------------------------------------------------------------ ego_pose/eval_forecast.py:29-98
+def compute_forecast_metrics(results, fr_margin, horizon, dt=1.0 / 30.0, algo="ego forecast", verbose=False):
+    """compute_metrics of eval_forecast.py:29-85 for `results` = {'traj_pred': {take: (n_win, m + T, 59)}, 'traj_orig': ...}:
+    per window the three numbers over frames [m, m + horizon), averaged over a take's windows, then over the takes."""
+    if results is None:
+        return None
+    m = int(fr_margin)
+    if verbose:
+        print("=" * 10 + " %s " % algo + "=" * 10)
+    per_take, acc = {}, np.zeros(3)
+    for take, pred in results["traj_pred"].items():
+        orig = results["traj_orig"][take]
+        row = np.zeros(3)
+        for i in range(orig.shape[0]):
+            traj, gt = pred[i, m:m + horizon, :], orig[i, m:m + horizon, :]
+            angs_gt, vels_gt = get_joint_angles(gt), get_joint_vels(gt, dt)
+            angs, vels = get_joint_angles(traj), get_joint_vels(traj, dt)
+            row += np.array([get_mean_dist(angs, angs_gt), get_mean_dist(vels, vels_gt), get_mean_abs(get_joint_accels(vels, dt))])
+        row /= orig.shape[0]
+        per_take[take] = row
+        if verbose:
+            print("%s - horizon: %d, pose dist: %.4f, vel dist: %.4f, accels: %.4f" % ((take, horizon) + tuple(row)))
+        acc += row
+    acc /= len(per_take)
+    if verbose:
+        print("-" * 60)
+        print("all - horizon: %d, pose dist: %.4f, vel dist: %.4f, accels: %.4f" % ((horizon,) + tuple(acc)))
+        print("-" * 60 + "\n")
+    return {"pose_dist": float(acc[0]), "vel_dist": float(acc[1]), "accels": float(acc[2]), "per_take": per_take}
+
+
+def forecast_err_vs_horizon(results, fr_margin, horizon, step=10, dt=1.0 / 30.0, algo="ego forecast", verbose=False):
+    """compute_err_vs_h (eval_forecast.py:88-98): the pose distance at horizons step, 2 step, ... below `horizon`."""
+    errors = np.array([compute_forecast_metrics(results, fr_margin, h, dt)["pose_dist"] for h in range(step, horizon, step)])
+    if verbose:
+        print("-" * 60)
+        print(algo)
+        print(np.array2string(errors, formatter={"all": lambda x: "%.4f" % x}, separator=", "))
+        print("-" * 60 + "\n")
+    return errors
+
+
 # ------------------------------------------------------------------ trajectory helpers used by the eval drivers
 def align_human_state(qpos, qvel, ref_qpos):
     """utils/tools.py:71-75, in place: put a predicted state at ref's xy position and heading."""
@@ -143,6 +186,21 @@ def align_human_state(qpos, qvel, ref_qpos):
     hq = _heading_q(np.asarray(ref_qpos[3:7], float))
     qpos[3:7] = _qmul(hq, np.asarray(qpos[3:7], float))
     qvel[:3] = _rot_matrix(hq) @ np.asarray(qvel[:3], float)
+
+
+def sync_traj(qpos_traj, qvel_traj, ref_qpos):
+    """ego_pose/utils/tools.py:18-32, all frames at once: turn a predicted trajectory about z so that its first frame has
+    `ref_qpos`'s heading and move it to ref's xy (the root height stays the trajectory's own). Returns new arrays."""
+    qpos_traj, qvel_traj = np.asarray(qpos_traj, float), np.asarray(qvel_traj, float)
+    ref_qpos = np.asarray(ref_qpos, float)
+    rel = _qmul(_heading_q(ref_qpos[3:7]), _qinv(_heading_q(qpos_traj[0, 3:7])))
+    R = _rot_matrix(rel)
+    start = np.array([qpos_traj[0, 0], qpos_traj[0, 1], ref_qpos[2]])
+    qpos, qvel = qpos_traj.copy(), qvel_traj.copy()
+    qpos[:, :2] = ((qpos_traj[:, :3] - start) @ R.T)[:, :2] + ref_qpos[:2]
+    qpos[:, 3:7] = _qmul(rel, qpos_traj[:, 3:7])
+    qvel[:, :3] = qvel_traj[:, :3] @ R.T
+    return qpos, qvel
 
 
 def remove_noisy_hands(results):

@@ -4,7 +4,8 @@ and the Gaussian head of the reference's `policy_net.select_action` (core/agent.
 weights, packed for the kernel's matrix-core tiles, in persistent buffers (`refresh()` re-reads the live parameters,
 addresses stay fixed for hipGraphs). `FusedForecastPolicy` is the ego_forecast form (`egp_policy_forecast_f32`): one step
 of VideoForecastNet's state LSTM cell (models/video_forecast_net.py:88-93, models/rnn.py:29-36) in front of the same MLP,
-the cell's h / c updated in place."""
+the cell's h / c updated in place; its `with_filter` (`egp_policy_forecast_filter_f32`) puts the observation filter's apply
+pass in front of it, merged with a tick's tile statistics or frozen."""
 from __future__ import annotations
 
 import ctypes as C
@@ -166,5 +167,38 @@ class FusedForecastPolicy(FusedGaussianPolicy):
                                                  _ptr(noise), _ptr(action_out), _ptr(mean_out), L.current_stream()), "egp_policy_forecast_f32")
         return action_out
 
-    def with_filter(self, *args, **kwargs):
-        raise NotImplementedError("the forecast step has no filter-fused form")
+    def with_filter(self, ctx, ctx_rows, t_idx, qpos, qvel, zf_in, zf_out, clip, y, y2, workspace, h, c, action_out, noise=None, mean_out=None,
+                    phase_t=None):
+        """The filter's apply pass + the forecast step in one launch (`egp_policy_forecast_filter_f32`): the cell's state input is
+        the observation of (qpos, qvel), normalised with `zf_in` merged with the tile statistics `ctx.obs_zfilter_stats` left in
+        `workspace` (`zf_out` receives the merged statistics), or with `workspace=None` with `zf_in` as it stands -- the frozen
+        filter of an evaluation, `running_state(x, update=False)`; `zf_out` may be None then. y (and y2, optional): float64
+        [n][obs_dim], the normalised rows. `zf_in=None` (a checkpoint without running_state): the raw observations go to y / y2
+        and through the unfiltered step. h / c, noise, action_out, mean_out as in `__call__`. `ctx`: the model's EgpContext."""
+        n, T, H = ctx_rows.shape
+        S = ctx.obs_dim
+        if S != self.S or H + self.Hs != self.in_dim:
+            raise ValueError("observation dim %d / context dim %d do not fit the cell (%d -> %d) and the policy input %d"
+                             % (S, H, self.S, self.Hs, self.in_dim))
+        assert qpos.dtype == torch.float64 and qpos.is_contiguous() and qpos.shape == (n, ctx.nq)
+        assert qvel.dtype == torch.float64 and qvel.is_contiguous() and qvel.shape == (n, ctx.nv)
+        for t in (y, y2):
+            assert t is None or (t.dtype == torch.float64 and t.is_contiguous() and t.shape == (n, S))
+        assert y is not None
+        _check_io(ctx_rows, t_idx, y, action_out, noise, mean_out, self.nu)
+        for t in (h, c):
+            assert t.dtype == torch.float32 and t.shape == (n, self.Hs) and t.stride(1) == 1 and t.stride(0) == h.stride(0) >= self.Hs
+        assert n == 0 or h.data_ptr() != c.data_ptr()
+        if zf_in is None:
+            assert workspace is None
+            ctx.obs_zfilter(qpos, qvel, None, None, clip, y, out2=y2, phase_t=phase_t)
+            return self(ctx_rows, t_idx, y, h, c, action_out, noise=noise, mean_out=mean_out)
+        for t in (zf_in, zf_out):
+            assert t is None or (t.dtype == torch.float64 and t.is_contiguous() and t.shape == (1 + 2 * S,))
+        L.check(self.lib.egp_policy_forecast_filter_f32(ctx.handle, _ptr(ctx_rows), int(ctx_rows.stride(0)), H, _ptr(t_idx), _ptr(qpos), _ptr(qvel),
+                                                        _ptr(ctx._phase_t(phase_t, n)), n, _ptr(zf_in), _ptr(zf_out), float(clip or 0.0),
+                                                        _ptr(y), _ptr(y2), _ptr(workspace), self.cell_desc, _ptr(h), _ptr(c), int(h.stride(0)),
+                                                        self.desc, len(self.layers), self.act, _ptr(self.log_std), _ptr(noise),
+                                                        _ptr(action_out), _ptr(mean_out), L.current_stream()),
+                "egp_policy_forecast_filter_f32")
+        return action_out

@@ -559,6 +559,24 @@ int egp_policy_forecast_f32(const float *ctx_rows, int64_t ctx_row_stride, int32
                             const double *state, int32_t state_dim, const egp_mlp_layer *cell, float *h, float *c,
                             int64_t hc_row_stride, int32_t n, const egp_mlp_layer *layers, int32_t n_layers, int32_t activation,
                             const float *log_std, const float *noise, double *action, float *mean_out, void *stream);
+/* ... with the observation filter's apply pass in front, the forecast counterpart of egp_policy_gaussian_filter_f32: the cell's
+ * state input is the observation of (qpos, qvel) row r (width: the model's obs_dim, the phase column from `phase_t` included
+ * when it has obs_phase; cell->in_dim = obs_dim + Hs), normalised and clipped as egp_obs_zfilter_apply_f64 does, written to y
+ * (and y2 when non-NULL; float64 [n][obs_dim]) and cast to float32 on its way into the cell. Everything from the cell on is
+ * egp_policy_forecast_f32.
+ *   zf_workspace != NULL (merged statistics): `zf_in` is merged with the tile statistics that egp_obs_zfilter_stats_f64 left in
+ *     the workspace (same ordered merge) and the merged state goes to zf_out; needs zf_out != NULL and
+ *     n <= egp_obs_zfilter_split_max_rows(). One launch computes exactly what egp_obs_zfilter_apply_f64 followed by
+ *     egp_policy_forecast_f32 on y2 computes (bit-identical).
+ *   zf_workspace == NULL (frozen statistics): normalises with `zf_in` as it stands -- ZFilter.__call__(x, update=False) of
+ *     utils/zfilter.py, what an evaluation does; zf_out may be NULL and receives a copy of zf_in otherwise; no row limit.
+ * zf_out != zf_in. No allocation, no synchronisation, capturable; n == 0 returns EGP_OK. */
+int egp_policy_forecast_filter_f32(egp_ctx *ctx, const float *ctx_rows, int64_t ctx_row_stride, int32_t ctx_dim, const int64_t *t_idx,
+                                   const double *qpos, const double *qvel, const int32_t *phase_t, int32_t n,
+                                   const double *zf_in, double *zf_out, double clip, double *y, double *y2, const void *zf_workspace,
+                                   const egp_mlp_layer *cell, float *h, float *c, int64_t hc_row_stride,
+                                   const egp_mlp_layer *layers, int32_t n_layers, int32_t activation, const float *log_std,
+                                   const float *noise, double *action, float *mean_out, void *stream);
 
 /* ----------------------------------------------------------------------------------------
  * Host physics boundary (replaces mujoco_py's MjSim inside HumanoidEnv: envs/common/mujoco_env.py:84-105,
