@@ -487,6 +487,125 @@ __device__ __forceinline__ void server_residency_probe(const PdServe &sv) {
     }
 }
 
+// The host handshake of the resident kernels. Thread 0 waits until the slice's go word reaches sequence `want` (or for
+// `timeout_ticks`), hands the word to the workgroup through `s_go_slot` and, where `trace` is given (block 0's substep waits),
+// stamps the start and the end of the wait into trace[0] / trace[1]. The callers alternate between two slots (substep & 1): a wave
+// that is still reading substep k's word cannot be overtaken by thread 0 writing substep k + 1's, which lands in the other slot,
+// and thread 0 cannot reach substep k + 2's wait before every wave has passed the barrier of k + 1 -- so the ONE barrier in here is
+// all a substep needs. A wait that timed out raises sv.err on the host and returns true: the whole workgroup must leave (the
+// caller returns; `s_abort` is workgroup-wide and was cleared before the first wait).
+__device__ __forceinline__ bool server_wait_go(const PdServe &sv, int slice, unsigned long long want, unsigned long long &s_go_slot,
+                                               int &s_abort, long long *trace) {
+    if (threadIdx.x == 0) {
+        const long long t0 = wall_clock64();
+        unsigned long long v;
+        for (;;) {
+            v = scalar_poll_u64(sv.go + slice * 8);
+            if ((v >> 1) >= want) break;
+            for (int z = 0; z < sv.poll_sleep; ++z) __builtin_amdgcn_s_sleep(1);
+            if (wall_clock64() - t0 > sv.timeout_ticks) { s_abort = 1; break; }
+        }
+        s_go_slot = v;
+        if (trace) { trace[0] = t0; trace[1] = wall_clock64(); }
+    }
+    __syncthreads();
+    if (s_abort) {
+        if (threadIdx.x == 0) __hip_atomic_store(sv.err, 1, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);
+        return true;
+    }
+    return false;
+}
+
+// Epilogue of one env, by the wave that served it, after the wait for sequence base + n_sub (the slice's last physics step is
+// drained): prev_qpos <- qpos; qpos | qvel | ee_wpos <- the rows the owner left in pinned memory. `qpos` points at the state
+// rows' qpos column (offset 0 of the row). The kernels run this slice by slice as the physics threads finish, so the env-step
+// ends one PCIe round trip after the last physics call instead of a barrier + a copy launch later.
+__device__ __forceinline__ void server_epilogue_env(const PdServe &sv, const PdLd &ld, const double *qpos, const double *qvel, long env,
+                                                    int lane) {
+    if (lane < sv.nq) {
+        const long d = env * sv.nq + lane;
+        const double q = sys_load_f64(qpos + env * ld.qpos + lane);
+        sv.out_prev_qpos[d] = sv.out_qpos[d];
+        sv.out_qpos[d] = q;
+    }
+    if (lane < sv.nv) sv.out_qvel[env * sv.nv + lane] = sys_load_f64(qvel + env * ld.qvel + lane);
+    if (lane < 15) sv.out_ee[env * 15 + lane] = sys_load_f64(sv.ee_host + env * 15 + lane);
+}
+
+// clip(value, +-lim) into the pinned torque row. System-scope store: straight to the host's row, nothing lingers in a device
+// cache -- the owner steps the env as soon as its row holds no NaN sentinel any more.
+__device__ __forceinline__ void store_torque_clipped(double *torque, long index, double value, double lim) {
+    __hip_atomic_store(reinterpret_cast<unsigned long long *>(torque + index),
+                       (unsigned long long)__double_as_longlong(fmin(fmax(value, -lim), lim)), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+}
+
+// Stable PD (humanoid_v1.py:130-144), per dof: the right-hand side of (M + Kd dt) qacc = -C - Kp eq - Kd qvel, and the torque
+// from the solved acceleration. The expression order is part of the result (bit-identical across the kernels).
+__device__ __forceinline__ double pd_rhs(double r_c, double kp, double eq, double kd, double r_v) { return -r_c - kp * eq - kd * r_v; }
+__device__ __forceinline__ double pd_torque(double kp, double eq, double kd, double r_v, double qacc, double sub_dt) {
+    const double ev = r_v + qacc * sub_dt;
+    return -kp * eq - kd * ev;
+}
+
+// An env's inertia row changed on the host: from the pinned row `src` into the wave's LDS row and the HBM copy `dst` (the LDS
+// row's padding behind nM is zeroed). All loads are issued before the first store.
+__device__ __forceinline__ void refresh_inertia_row(const double *src, double *dst, double *lds_row, int nM, int lane) {
+    constexpr int QM_IT = PD_NM_MAX / 64;
+    double t_qM[QM_IT];
+#pragma unroll
+    for (int k = 0; k < QM_IT; ++k) {
+        const int i = lane + 64 * k;
+        t_qM[k] = i < nM ? sys_load_f64(src + i) : 0.0;
+    }
+#pragma unroll
+    for (int k = 0; k < QM_IT; ++k) {
+        const int i = lane + 64 * k;
+        lds_row[i] = t_qM[k];
+        if (i < nM) dst[i] = t_qM[k];
+    }
+}
+
+// A solve of the multi-env kernels. They keep the factors of M + Kd dt = L^T D L in LDS in place of the env's sparse inertia row F:
+// entry (K, r), r an ancestor of K, holds the multiplier of pivot K in row r, the diagonal entry 1 / D_K. Two sweeps over those
+// 852 + 58 numbers: the lane's column of L for the sweep towards the root (entries (K, row), K a descendant: LDS index up(K)), then
+// its row for the sweep back (entries (row, K), K an ancestor: lo(K)): 58 reads in flight at once each time, the entries that do
+// not exist (and the other sweep's) read a zero slot of the row's padding -- no select, no LDS round trip on the dependent chain
+// readlane -> fma (with the reads and a K > row select inside the sweeps a solve took 13, then 4 us; now as the one-env
+// kernel's: ~2). Where the indices come from is the caller's: registers in k_pd_server_tree58_multi, LDS tables in _multi_dyn.
+template <class UpIndex, class LoIndex>
+__device__ __forceinline__ double tree_solve_two_sweeps(const double *F, int id_diag, double b, UpIndex up, LoIndex lo) {
+    double cf[PD_NV];
+#pragma unroll
+    for (int K = 0; K < PD_NV; ++K) cf[K] = F[up(K)];
+    const double d_own = F[id_diag];
+#pragma unroll
+    for (int K = PD_NV - 1; K >= 0; --K) b = fma(-cf[K], readlane_f64(b, K), b);      // L^T y = b: leaves -> root
+    b *= d_own;
+#pragma unroll
+    for (int K = 0; K < PD_NV; ++K) cf[K] = F[lo(K)];
+#pragma unroll
+    for (int J = 0; J < PD_NV; ++J) b = fma(-cf[J], readlane_f64(b, J), b);           // L x = z: root -> leaves
+    return b;
+}
+
+// The dynamic LDS of the two DYN kernels, in doubles from its start: the kernels address it and the host sizes it from these.
+// k_pd_server_tree58<true>: the tree tables | K8 scratch per wave | per wave qpos[64] | qvel[64] | bias[64]
+namespace dyn_lds {
+constexpr size_t TB = (sizeof(egp_dyn::DynTables) + 7) / 8;
+constexpr size_t SCR = TB, SCR_WAVE = egp_dyn::DY_ENV_DOUBLES;
+constexpr size_t Q = SCR + 4 * SCR_WAVE, Q_ROW = 192;
+constexpr size_t BYTES = (Q + 4 * Q_ROW) * sizeof(double);
+}  // namespace dyn_lds
+// k_pd_server_tree58_multi_dyn<KE>: tables | K8 scratch per wave | factor rows [4][KE][PD_NM_MAX] | state + bias rows [4][KE][192]
+// | the sweeps' index tables, 2 x [PD_NV][64] shorts
+namespace multi_dyn_lds {
+constexpr size_t SCR = dyn_lds::TB, SCR_WAVE = egp_dyn::DY_ENV_DOUBLES;
+constexpr size_t FAC = SCR + 4 * SCR_WAVE, Q_ROW = 192;
+constexpr size_t q(int ke) { return FAC + (size_t)4 * ke * PD_NM_MAX; }
+constexpr size_t idx(int ke) { return q(ke) + (size_t)4 * ke * Q_ROW; }
+constexpr size_t bytes(int ke) { return idx(ke) * sizeof(double) + 2 * PD_NV * 64 * sizeof(short); }
+}  // namespace multi_dyn_lds
+
 // DYN (device_dynamics engines): the wave computes the inertia and the bias force itself from the (qpos, qvel) rows it reads
 // (K8's wave function: FK + CRBA + RNE, egp_dynamics_dev.hpp) instead of taking qM / qfrc_bias from the host -- a backend whose
 // inertia changes with every substep (MuJoCo's does) then sends 117 doubles per env-substep, not 1 085.
@@ -543,10 +662,14 @@ __global__ __launch_bounds__(256) void k_pd_server_tree58(DevModel m, PdLd ld, c
 #pragma unroll
         for (int k = 0; k < QM_IT; ++k) s_qM[wave][lane + 64 * k] = t_qM[k];
     }
-    constexpr int TB_DOUBLES = DYN ? (int)((sizeof(egp_dyn::DynTables) + 7) / 8) : 0;
-    egp_dyn::DynTables *tb = reinterpret_cast<egp_dyn::DynTables *>(s_dynmem);
-    double *s_scr = s_dynmem + TB_DOUBLES + wave * egp_dyn::DY_ENV_DOUBLES;                   // K8 scratch of this wave
-    double *s_q = s_dynmem + TB_DOUBLES + 4 * egp_dyn::DY_ENV_DOUBLES + wave * 192;            // qpos[64] | qvel[64] | bias[64]
+    // the dynamic LDS (dyn_lds) exists for DYN only: the other kernel is launched without any and forms no address in it
+    egp_dyn::DynTables *tb = nullptr;
+    double *s_scr = nullptr, *s_q = nullptr;
+    if constexpr (DYN) {
+        tb = reinterpret_cast<egp_dyn::DynTables *>(s_dynmem);
+        s_scr = s_dynmem + dyn_lds::SCR + wave * dyn_lds::SCR_WAVE;                    // K8 scratch of this wave
+        s_q = s_dynmem + dyn_lds::Q + wave * dyn_lds::Q_ROW;                           // qpos[64] | qvel[64] | bias[64]
+    }
     if constexpr (DYN) {
         const int words = sizeof(egp_dyn::DynTables) / 4;
         const int *src = reinterpret_cast<const int *>(sv.dyn);
@@ -582,30 +705,12 @@ __global__ __launch_bounds__(256) void k_pd_server_tree58(DevModel m, PdLd ld, c
         }
     }
     for (int sub = 0; sub < sv.n_sub; ++sub) {
-        if (threadIdx.x == 0) {
-            const unsigned long long want = sv.base + (unsigned long long)sub;
-            const long long t0 = wall_clock64();
-            unsigned long long v;
-            for (;;) {
-                v = scalar_poll_u64(sv.go + slice * 8);
-                if ((v >> 1) >= want) break;
-                for (int z = 0; z < sv.poll_sleep; ++z) __builtin_amdgcn_s_sleep(1);
-                if (wall_clock64() - t0 > sv.timeout_ticks) { s_abort = 1; break; }
-            }
-            s_go[sub & 1] = v;            // double-buffered: one barrier per substep is enough
-            if (tracer) { sv.trace[sub * 8 + 0] = t0; sv.trace[sub * 8 + 1] = wall_clock64(); }
-        }
-        __syncthreads();
-        if (s_abort) {
-            if (threadIdx.x == 0) __hip_atomic_store(sv.err, 1, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);
+        if (server_wait_go(sv, slice, sv.base + (unsigned long long)sub, s_go[sub & 1], s_abort,
+                           tracer ? sv.trace + sub * 8 : nullptr))
             return;
-        }
         const bool refresh = DYN || (s_go[sub & 1] & 1ull) != 0ull;
         if (live && m.action_torque) {          // action_type 'torque' (humanoid_v1.py:170-172): the clipped control itself
-            if (lane < PD_NV && row >= 6)
-                __hip_atomic_store(reinterpret_cast<unsigned long long *>(torque + env * m.nu + act),
-                                   (unsigned long long)__double_as_longlong(fmin(fmax(target, -c_lim), c_lim)), __ATOMIC_RELAXED,
-                                   __HIP_MEMORY_SCOPE_SYSTEM);
+            if (lane < PD_NV && row >= 6) store_torque_clipped(torque, env * m.nu + act, target, c_lim);
         } else if (live) {
             double r_q, r_v, r_c;
             if constexpr (DYN) {
@@ -640,39 +745,16 @@ __global__ __launch_bounds__(256) void k_pd_server_tree58(DevModel m, PdLd ld, c
                 r_v = sys_load_f64(qvel + env * ld.qvel + row);
                 r_c = sys_load_f64(C + env * ld.bias + row);
             }
-            if (!DYN && refresh) {              // this wave's inertia row changed on the host: LDS and HBM copies
-                const double *src = sv.qM_host + env * ld.qM;
-                double *dst = sv.qM_dev + env * ld.qM;
-                double t_qM[QM_IT];
-#pragma unroll
-                for (int k = 0; k < QM_IT; ++k) {
-                    const int i = lane + 64 * k;
-                    t_qM[k] = i < m.nM ? sys_load_f64(src + i) : 0.0;
-                }
-#pragma unroll
-                for (int k = 0; k < QM_IT; ++k) {
-                    const int i = lane + 64 * k;
-                    s_qM[wave][i] = t_qM[k];
-                    if (i < m.nM) dst[i] = t_qM[k];
-                }
-            }
+            if (!DYN && refresh) refresh_inertia_row(sv.qM_host + env * ld.qM, sv.qM_dev + env * ld.qM, &s_qM[wave][0], m.nM, lane);
             if (!DYN && (sub == 0 || refresh)) factor_from_lds();      // (wave-uniform: the go word is per slice, the wave per env)
-            const double kp = c_kp, kd = c_kd;
             const double eq = row >= 6 ? r_q - target : 0.0;
-            const double qv = r_v;
-            double b = -r_c - kp * eq - kd * qv;
+            double b = pd_rhs(r_c, c_kp, eq, c_kd, r_v);
             if (tracer) sv.trace[sub * 8 + 2] = b != 12345.678 ? wall_clock64() : 0;
             tree_solve<PD_NV - 1>(a, b);
             const double qacc = b * dinv;
             if (tracer) sv.trace[sub * 8 + 3] = qacc != 12345.678 ? wall_clock64() : 0;
-            if (lane < PD_NV && row >= 6) {
-                const double ev = qv + qacc * m.sub_dt;
-                const double tau = -kp * eq - kd * ev;
-                // system-scope store: straight to the pinned row, nothing lingers in a device cache
-                __hip_atomic_store(reinterpret_cast<unsigned long long *>(torque + env * m.nu + act),
-                                   (unsigned long long)__double_as_longlong(fmin(fmax(tau, -c_lim), c_lim)), __ATOMIC_RELAXED,
-                                   __HIP_MEMORY_SCOPE_SYSTEM);
-            }
+            if (lane < PD_NV && row >= 6)
+                store_torque_clipped(torque, env * m.nu + act, pd_torque(c_kp, eq, c_kd, r_v, qacc, m.sub_dt), c_lim);
             if (tracer) sv.trace[sub * 8 + 4] = wall_clock64();
             if constexpr (DYN) {
                 // the torque is on its way and the host steps: now what that mj_step leaves behind for the NEXT compute_torque --
@@ -703,40 +785,9 @@ __global__ __launch_bounds__(256) void k_pd_server_tree58(DevModel m, PdLd ld, c
             }
         }
     }
-    // epilogue: prev_qpos <- qpos; qpos | qvel | ee_wpos <- the rows the owner drained after the last substep.
-    // Runs slice by slice as the physics threads finish, so the env-step ends one PCIe round trip after the last
-    // physics call instead of a barrier + a copy launch later.
-    {
-        const int slot = sv.n_sub & 1;
-        if (threadIdx.x == 0) {
-            const unsigned long long want = sv.base + (unsigned long long)sv.n_sub;
-            const long long t0 = wall_clock64();
-            unsigned long long v;
-            for (;;) {
-                v = scalar_poll_u64(sv.go + slice * 8);
-                if ((v >> 1) >= want) break;
-                for (int z = 0; z < sv.poll_sleep; ++z) __builtin_amdgcn_s_sleep(1);
-                if (wall_clock64() - t0 > sv.timeout_ticks) { s_abort = 1; break; }
-            }
-            s_go[slot] = v;
-        }
-        __syncthreads();
-        if (s_abort) {
-            if (threadIdx.x == 0) __hip_atomic_store(sv.err, 1, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);
-            return;
-        }
-        if (live) {
-            // the row base of qpos: `qpos` points at the state rows' qpos column (offset 0 of the row)
-            if (lane < sv.nq) {
-                const long d = env * sv.nq + lane;
-                const double q = sys_load_f64(qpos + env * ld.qpos + lane);
-                sv.out_prev_qpos[d] = sv.out_qpos[d];
-                sv.out_qpos[d] = q;
-            }
-            if (lane < sv.nv) sv.out_qvel[env * sv.nv + lane] = sys_load_f64(qvel + env * ld.qvel + lane);
-            if (lane < 15) sv.out_ee[env * 15 + lane] = sys_load_f64(sv.ee_host + env * 15 + lane);
-        }
-    }
+    // epilogue: the final state to HBM once the slice's last physics step is drained
+    if (server_wait_go(sv, slice, sv.base + (unsigned long long)sv.n_sub, s_go[sv.n_sub & 1], s_abort, nullptr)) return;
+    if (live) server_epilogue_env(sv, ld, qpos, qvel, env, lane);
 }
 
 // KE envs per wavefront ("multi" form of the resident K1): the grid must fit the chip at once -- one 350-register workgroup per
@@ -757,13 +808,13 @@ __global__ __launch_bounds__(256) void k_pd_server_tree58_multi(DevModel m, PdLd
     __shared__ int s_abort;
     if (sv.probe) { server_residency_probe(sv); return; }
     const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+    const int row = lane < PD_NV ? lane : PD_NV - 1;
+    const int act = row >= 6 ? row - 6 : 0;
+    const int slice = sv.block_slice[blockIdx.x];
     // the workgroup's envs [be0, be1) (at most 4 KE of them, dealt out evenly by the engine: with 4.5 envs per workgroup only every
     // second workgroup has a wave that serves two); wave w takes be0 + w, be0 + w + 4, ...
     const long be0 = sv.block_env0[blockIdx.x], be1 = sv.block_env0[blockIdx.x + 1];
     const long env0 = be0 + wave;
-    const int row = lane < PD_NV ? lane : PD_NV - 1;
-    const int act = row >= 6 ? row - 6 : 0;
-    const int slice = sv.block_slice[blockIdx.x];
     bool live[KE];
     bool any = false;
 #pragma unroll
@@ -803,33 +854,17 @@ __global__ __launch_bounds__(256) void k_pd_server_tree58_multi(DevModel m, PdLd
         idv[K] = id >= 0 ? id : (short)ZERO_SLOT;
     }
     const int id_diag = m.m_map[row * PD_NV + row];
+    auto up_index = [&](int K) { return K > row ? (int)idv[K] : ZERO_SLOT; };           // entry (K, row), K a descendant of the row
+    auto lo_index = [&](int K) { return K < row ? (int)idv[K] : ZERO_SLOT; };           // entry (row, K), K an ancestor
     for (int sub = 0; sub < sv.n_sub; ++sub) {
-        if (threadIdx.x == 0) {
-            const unsigned long long want = sv.base + (unsigned long long)sub;
-            const long long t0 = wall_clock64();
-            unsigned long long v;
-            for (;;) {
-                v = scalar_poll_u64(sv.go + slice * 8);
-                if ((v >> 1) >= want) break;
-                for (int z = 0; z < sv.poll_sleep; ++z) __builtin_amdgcn_s_sleep(1);
-                if (wall_clock64() - t0 > sv.timeout_ticks) { s_abort = 1; break; }
-            }
-            s_go[sub & 1] = v;
-            if (tracer) { sv.trace[sub * 8 + 0] = t0; sv.trace[sub * 8 + 1] = wall_clock64(); }
-        }
-        __syncthreads();
-        if (s_abort) {
-            if (threadIdx.x == 0) __hip_atomic_store(sv.err, 1, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);
+        if (server_wait_go(sv, slice, sv.base + (unsigned long long)sub, s_go[sub & 1], s_abort,
+                           tracer ? sv.trace + sub * 8 : nullptr))
             return;
-        }
         const bool refresh = (s_go[sub & 1] & 1ull) != 0ull;
         if (m.action_torque) {                  // action_type 'torque' (humanoid_v1.py:170-172): the clipped control itself
 #pragma unroll
             for (int e = 0; e < KE; ++e)
-                if (live[e] && lane < PD_NV && row >= 6)
-                    __hip_atomic_store(reinterpret_cast<unsigned long long *>(torque + (env0 + 4 * e) * m.nu + act),
-                                       (unsigned long long)__double_as_longlong(fmin(fmax(target[e], -c_lim), c_lim)), __ATOMIC_RELAXED,
-                                       __HIP_MEMORY_SCOPE_SYSTEM);
+                if (live[e] && lane < PD_NV && row >= 6) store_torque_clipped(torque, (env0 + 4 * e) * m.nu + act, target[e], c_lim);
             continue;
         }
         // every live env's state row first (whole 64-byte lines when the row is contiguous: see k_pd_server_tree58)
@@ -865,21 +900,8 @@ __global__ __launch_bounds__(256) void k_pd_server_tree58_multi(DevModel m, PdLd
                 r_v = pick(sv.nq + row);
                 r_c = pick(sv.nq + sv.nv + row);
             }
-            if (refresh) {                      // this env's inertia row changed on the host: LDS and HBM copies
-                const double *src = sv.qM_host + env * ld.qM;
-                double *dst = sv.qM_dev + env * ld.qM;
-                double t_qM[QM_IT];
-#pragma unroll
-                for (int k = 0; k < QM_IT; ++k) {
-                    const int i = lane + 64 * k;
-                    t_qM[k] = i < m.nM ? sys_load_f64(src + i) : 0.0;
-                }
-#pragma unroll
-                for (int k = 0; k < QM_IT; ++k) {
-                    const int i = lane + 64 * k;
-                    F[i] = t_qM[k];
-                    if (i < m.nM) dst[i] = t_qM[k];
-                }
+            if (refresh) {
+                refresh_inertia_row(sv.qM_host + env * ld.qM, sv.qM_dev + env * ld.qM, F, m.nM, lane);
                 egp_dyn::wave_sync();
             }
             if (sub == 0 || refresh) {
@@ -901,68 +923,20 @@ __global__ __launch_bounds__(256) void k_pd_server_tree58_multi(DevModel m, PdLd
                 egp_dyn::wave_sync();
             }
             const double eq = row >= 6 ? r_q - target[e] : 0.0;
-            double b = -r_c - c_kp * eq - c_kd * r_v;
+            double b = pd_rhs(r_c, c_kp, eq, c_kd, r_v);
             if (tracer && e == 0) sv.trace[sub * 8 + 2] = b != 12345.678 ? wall_clock64() : 0;     // (stamps of block 0: its first env, then its last)
-            // the lane's column of L for the sweep towards the root (entries (K, row), K a descendant), then its row for the sweep back
-            // (entries (row, K), K an ancestor): 58 reads in flight at once each time, the entries that do not exist (and the other
-            // sweep's) read a zero slot of the row's padding -- no select, no LDS round trip on the dependent chain readlane -> fma
-            // (with the reads and a K > row select inside the sweeps a solve took 13, then 4 us; now as the one-env kernel's: ~2)
-            double cf[PD_NV];
-#pragma unroll
-            for (int K = 0; K < PD_NV; ++K) cf[K] = F[K > row ? idv[K] : ZERO_SLOT];
-            const double d_own = F[id_diag];
-#pragma unroll
-            for (int K = PD_NV - 1; K >= 0; --K) b = fma(-cf[K], readlane_f64(b, K), b);      // L^T y = b: leaves -> root
-            b *= d_own;
-#pragma unroll
-            for (int K = 0; K < PD_NV; ++K) cf[K] = F[K < row ? idv[K] : ZERO_SLOT];
-#pragma unroll
-            for (int J = 0; J < PD_NV; ++J) b = fma(-cf[J], readlane_f64(b, J), b);           // L x = z: root -> leaves
+            b = tree_solve_two_sweeps(F, id_diag, b, up_index, lo_index);
             if (tracer && e == 0) sv.trace[sub * 8 + 3] = b != 12345.678 ? wall_clock64() : 0;
-            if (lane < PD_NV && row >= 6) {
-                const double ev = r_v + b * m.sub_dt;
-                const double tau = -c_kp * eq - c_kd * ev;
-                __hip_atomic_store(reinterpret_cast<unsigned long long *>(torque + env * m.nu + act),
-                                   (unsigned long long)__double_as_longlong(fmin(fmax(tau, -c_lim), c_lim)), __ATOMIC_RELAXED,
-                                   __HIP_MEMORY_SCOPE_SYSTEM);
-            }
+            if (lane < PD_NV && row >= 6)
+                store_torque_clipped(torque, env * m.nu + act, pd_torque(c_kp, eq, c_kd, r_v, b, m.sub_dt), c_lim);
             if (tracer) sv.trace[sub * 8 + (e == 0 ? 4 : 5)] = wall_clock64();
         }
     }
-    // epilogue (see k_pd_server_tree58): the final state of the wave's envs to HBM once the slice's last step is drained
-    {
-        const int slot = sv.n_sub & 1;
-        if (threadIdx.x == 0) {
-            const unsigned long long want = sv.base + (unsigned long long)sv.n_sub;
-            const long long t0 = wall_clock64();
-            unsigned long long v;
-            for (;;) {
-                v = scalar_poll_u64(sv.go + slice * 8);
-                if ((v >> 1) >= want) break;
-                for (int z = 0; z < sv.poll_sleep; ++z) __builtin_amdgcn_s_sleep(1);
-                if (wall_clock64() - t0 > sv.timeout_ticks) { s_abort = 1; break; }
-            }
-            s_go[slot] = v;
-        }
-        __syncthreads();
-        if (s_abort) {
-            if (threadIdx.x == 0) __hip_atomic_store(sv.err, 1, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);
-            return;
-        }
+    // epilogue: the final state of the wave's envs to HBM once the slice's last physics step is drained
+    if (server_wait_go(sv, slice, sv.base + (unsigned long long)sv.n_sub, s_go[sv.n_sub & 1], s_abort, nullptr)) return;
 #pragma unroll
-        for (int e = 0; e < KE; ++e) {
-            if (!live[e]) continue;
-            const long env = env0 + 4 * e;
-            if (lane < sv.nq) {
-                const long d = env * sv.nq + lane;
-                const double q = sys_load_f64(qpos + env * ld.qpos + lane);
-                sv.out_prev_qpos[d] = sv.out_qpos[d];
-                sv.out_qpos[d] = q;
-            }
-            if (lane < sv.nv) sv.out_qvel[env * sv.nv + lane] = sys_load_f64(qvel + env * ld.qvel + lane);
-            if (lane < 15) sv.out_ee[env * 15 + lane] = sys_load_f64(sv.ee_host + env * 15 + lane);
-        }
-    }
+    for (int e = 0; e < KE; ++e)
+        if (live[e]) server_epilogue_env(sv, ld, qpos, qvel, env0 + 4 * e, lane);
 }
 
 // DYN form of the multi-env resident K1 (device_dynamics engines beyond one env per wave): K8 inside, as k_pd_server_tree58<true>
@@ -992,11 +966,11 @@ __global__ __launch_bounds__(256) void k_pd_server_tree58_multi_dyn(DevModel m, 
     __shared__ int s_abort;
     if (sv.probe) { server_residency_probe(sv); return; }
     const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
-    const long be0 = sv.block_env0[blockIdx.x], be1 = sv.block_env0[blockIdx.x + 1];
-    const long env0 = be0 + wave;                      // wave w takes be0 + w, be0 + w + 4, ... (see k_pd_server_tree58_multi)
     const int row = lane < PD_NV ? lane : PD_NV - 1;
     const int act = row >= 6 ? row - 6 : 0;
     const int slice = sv.block_slice[blockIdx.x];
+    const long be0 = sv.block_env0[blockIdx.x], be1 = sv.block_env0[blockIdx.x + 1];
+    const long env0 = be0 + wave;                      // wave w takes be0 + w, be0 + w + 4, ... (see k_pd_server_tree58_multi)
     bool live[KE];
     unsigned live_mask = 0u;            // (the same as bits, for the loops over the envs that are kept rolled)
 #pragma unroll
@@ -1012,17 +986,16 @@ __global__ __launch_bounds__(256) void k_pd_server_tree58_multi_dyn(DevModel m, 
 #pragma unroll
     for (int e = 0; e < KE; ++e) target[e] = c_ref + (live[e] ? action[(env0 + 4 * e) * ld.action + act] : 0.0) * c_scale;
     constexpr int QM_IT = PD_NM_MAX / 64;
-    constexpr int TB_DOUBLES = (int)((sizeof(egp_dyn::DynTables) + 7) / 8);
-    egp_dyn::DynTables *tb = reinterpret_cast<egp_dyn::DynTables *>(s_dynmem);
-    double *s_scr = s_dynmem + TB_DOUBLES + wave * egp_dyn::DY_ENV_DOUBLES;                             // K8 scratch of this wave
-    double *s_fac = s_dynmem + TB_DOUBLES + 4 * egp_dyn::DY_ENV_DOUBLES;                                // [4 waves][KE][PD_NM_MAX]
-    double *s_q = s_fac + (size_t)4 * KE * PD_NM_MAX + (size_t)wave * KE * 192;                         // per env: qpos[64] | qvel[64] | bias[64]
+    egp_dyn::DynTables *tb = reinterpret_cast<egp_dyn::DynTables *>(s_dynmem);                         // (multi_dyn_lds)
+    double *s_scr = s_dynmem + multi_dyn_lds::SCR + wave * multi_dyn_lds::SCR_WAVE;                    // K8 scratch of this wave
+    double *s_fac = s_dynmem + multi_dyn_lds::FAC;                                                     // [4 waves][KE][PD_NM_MAX]
+    double *s_q = s_dynmem + multi_dyn_lds::q(KE) + (size_t)wave * KE * multi_dyn_lds::Q_ROW;          // per env: qpos[64] | qvel[64] | bias[64]
     // sparse index of entry (K, lane's row) for the sweep towards the root (K a descendant: s_up) and of (row, K) for the sweep back
     // (K an ancestor: s_lo) -- the same for every env -- or, where the tree has no such entry, a slot of the row's padding that
     // stays zero (nM = 910 of PD_NM_MAX = 960 doubles). [K][lane], in the dynamic LDS on purpose: k_pd_server_tree58_multi keeps them
     // in registers, here the 116 addresses made from them would be carried across K8 and the elimination
     constexpr int ZERO_SLOT = PD_NM_MAX - 1;
-    short *s_up = reinterpret_cast<short *>(s_fac + (size_t)4 * KE * (PD_NM_MAX + 192));
+    short *s_up = reinterpret_cast<short *>(s_dynmem + multi_dyn_lds::idx(KE));
     short *s_lo = s_up + PD_NV * 64;
     for (int i = threadIdx.x; i < PD_NV * 64; i += 256) {
         const int K = i >> 6, r = (i & 63) < PD_NV ? (i & 63) : PD_NV - 1;
@@ -1051,6 +1024,8 @@ __global__ __launch_bounds__(256) void k_pd_server_tree58_multi_dyn(DevModel m, 
     const bool tracer = sv.trace && blockIdx.x == 0 && threadIdx.x == 0;
     const int id_diag = m.m_map[row * PD_NV + row];
     const short *up_l = s_up + lane, *lo_l = s_lo + lane;       // (entry K of the lane: a constant offset from these)
+    auto up_index = [&](int K) { return up_l[K * 64]; };
+    auto lo_index = [&](int K) { return lo_l[K * 64]; };
     // the env's inertia row in F -> the factors of M + Kd dt in its place (k_pd_server_tree58_multi's layout)
     auto factor_in_place = [&](double *F) {
         double a[PD_NV];
@@ -1081,31 +1056,13 @@ __global__ __launch_bounds__(256) void k_pd_server_tree58_multi_dyn(DevModel m, 
         factor_in_place(s_fac + (size_t)(wave * KE + e) * PD_NM_MAX);       // (its wave_syncs order the held row too)
     }
     for (int sub = 0; sub < sv.n_sub; ++sub) {
-        if (threadIdx.x == 0) {
-            const unsigned long long want = sv.base + (unsigned long long)sub;
-            const long long t0 = wall_clock64();
-            unsigned long long v;
-            for (;;) {
-                v = scalar_poll_u64(sv.go + slice * 8);
-                if ((v >> 1) >= want) break;
-                for (int z = 0; z < sv.poll_sleep; ++z) __builtin_amdgcn_s_sleep(1);
-                if (wall_clock64() - t0 > sv.timeout_ticks) { s_abort = 1; break; }
-            }
-            s_go[sub & 1] = v;
-            if (tracer) { sv.trace[sub * 8 + 0] = t0; sv.trace[sub * 8 + 1] = wall_clock64(); }
-        }
-        __syncthreads();
-        if (s_abort) {
-            if (threadIdx.x == 0) __hip_atomic_store(sv.err, 1, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);
+        if (server_wait_go(sv, slice, sv.base + (unsigned long long)sub, s_go[sub & 1], s_abort,
+                           tracer ? sv.trace + sub * 8 : nullptr))
             return;
-        }
         if (m.action_torque) {                  // action_type 'torque' (humanoid_v1.py:170-172): the clipped control itself
 #pragma unroll
             for (int e = 0; e < KE; ++e)
-                if (live[e] && lane < PD_NV && row >= 6)
-                    __hip_atomic_store(reinterpret_cast<unsigned long long *>(torque + (env0 + 4 * e) * m.nu + act),
-                                       (unsigned long long)__double_as_longlong(fmin(fmax(target[e], -c_lim), c_lim)), __ATOMIC_RELAXED,
-                                       __HIP_MEMORY_SCOPE_SYSTEM);
+                if (live[e] && lane < PD_NV && row >= 6) store_torque_clipped(torque, (env0 + 4 * e) * m.nu + act, target[e], c_lim);
             continue;
         }
         // every live env's qpos | qvel row first, lane = index (the bias is not in the host row), into the env's LDS row
@@ -1134,27 +1091,12 @@ __global__ __launch_bounds__(256) void k_pd_server_tree58_multi_dyn(DevModel m, 
             const double *F = s_fac + (size_t)(wave * KE + e) * PD_NM_MAX;
             const double r_q = s_q[e * 192 + 7 + act], r_v = s_q[e * 192 + 64 + row], r_c = s_q[e * 192 + 128 + row];
             const double eq = row >= 6 ? r_q - target[e] : 0.0;
-            double b = -r_c - c_kp * eq - c_kd * r_v;
+            double b = pd_rhs(r_c, c_kp, eq, c_kd, r_v);
             if (tracer && e == 0) sv.trace[sub * 8 + 2] = b != 12345.678 ? wall_clock64() : 0;     // (stamps of block 0: its first env, then its last)
-            double cf[PD_NV];                   // the two sweeps of k_pd_server_tree58_multi
-#pragma unroll
-            for (int K = 0; K < PD_NV; ++K) cf[K] = F[up_l[K * 64]];
-            const double d_own = F[id_diag];
-#pragma unroll
-            for (int K = PD_NV - 1; K >= 0; --K) b = fma(-cf[K], readlane_f64(b, K), b);      // L^T y = b: leaves -> root
-            b *= d_own;
-#pragma unroll
-            for (int K = 0; K < PD_NV; ++K) cf[K] = F[lo_l[K * 64]];
-#pragma unroll
-            for (int J = 0; J < PD_NV; ++J) b = fma(-cf[J], readlane_f64(b, J), b);           // L x = z: root -> leaves
+            b = tree_solve_two_sweeps(F, id_diag, b, up_index, lo_index);
             if (tracer && e == 0) sv.trace[sub * 8 + 3] = b != 12345.678 ? wall_clock64() : 0;
-            if (lane < PD_NV && row >= 6) {
-                const double ev = r_v + b * m.sub_dt;
-                const double tau = -c_kp * eq - c_kd * ev;
-                __hip_atomic_store(reinterpret_cast<unsigned long long *>(torque + env * m.nu + act),
-                                   (unsigned long long)__double_as_longlong(fmin(fmax(tau, -c_lim), c_lim)), __ATOMIC_RELAXED,
-                                   __HIP_MEMORY_SCOPE_SYSTEM);
-            }
+            if (lane < PD_NV && row >= 6)
+                store_torque_clipped(torque, env * m.nu + act, pd_torque(c_kp, eq, c_kd, r_v, b, m.sub_dt), c_lim);
             if (tracer) sv.trace[sub * 8 + (e == 0 ? 4 : 5)] = wall_clock64();
         }
         // ... and then, while the host steps, what that mj_step leaves behind for the NEXT compute_torque of every env: M and C at
@@ -1181,40 +1123,11 @@ __global__ __launch_bounds__(256) void k_pd_server_tree58_multi_dyn(DevModel m, 
         }
         if (tracer) sv.trace[sub * 8 + 6] = wall_clock64();
     }
-    // epilogue (see k_pd_server_tree58): the final state of the wave's envs to HBM once the slice's last step is drained
-    {
-        const int slot = sv.n_sub & 1;
-        if (threadIdx.x == 0) {
-            const unsigned long long want = sv.base + (unsigned long long)sv.n_sub;
-            const long long t0 = wall_clock64();
-            unsigned long long v;
-            for (;;) {
-                v = scalar_poll_u64(sv.go + slice * 8);
-                if ((v >> 1) >= want) break;
-                for (int z = 0; z < sv.poll_sleep; ++z) __builtin_amdgcn_s_sleep(1);
-                if (wall_clock64() - t0 > sv.timeout_ticks) { s_abort = 1; break; }
-            }
-            s_go[slot] = v;
-        }
-        __syncthreads();
-        if (s_abort) {
-            if (threadIdx.x == 0) __hip_atomic_store(sv.err, 1, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);
-            return;
-        }
+    // epilogue: the final state of the wave's envs to HBM once the slice's last physics step is drained
+    if (server_wait_go(sv, slice, sv.base + (unsigned long long)sv.n_sub, s_go[sv.n_sub & 1], s_abort, nullptr)) return;
 #pragma unroll
-        for (int e = 0; e < KE; ++e) {
-            if (!live[e]) continue;
-            const long env = env0 + 4 * e;
-            if (lane < sv.nq) {
-                const long d = env * sv.nq + lane;
-                const double q = sys_load_f64(qpos + env * ld.qpos + lane);
-                sv.out_prev_qpos[d] = sv.out_qpos[d];
-                sv.out_qpos[d] = q;
-            }
-            if (lane < sv.nv) sv.out_qvel[env * sv.nv + lane] = sys_load_f64(qvel + env * ld.qvel + lane);
-            if (lane < 15) sv.out_ee[env * 15 + lane] = sys_load_f64(sv.ee_host + env * 15 + lane);
-        }
-    }
+    for (int e = 0; e < KE; ++e)
+        if (live[e]) server_epilogue_env(sv, ld, qpos, qvel, env0 + 4 * e, lane);
 }
 
 // Generic path (any nv <= 64): one wavefront per env, system in LDS.
@@ -2426,15 +2339,9 @@ int egp_launch_pd_torque_strided(egp_ctx *ctx, const double *qpos, long ld_qpos,
     return launch_pd<double>(ctx, ld, qpos, qvel, action, qM, bias, n, torque, nullptr, stream, done);
 }
 
-size_t egp_pd_server_dyn_lds_bytes() {
-    return ((sizeof(egp_dyn::DynTables) + 7) / 8 + 4 * (size_t)egp_dyn::DY_ENV_DOUBLES + 4 * 192) * sizeof(double);
-}
-
-// k_pd_server_tree58_multi_dyn<KE>: tables | K8 scratch per wave | factor rows per env | state + bias row per env | index tables
-constexpr size_t pd_server_multi_dyn_lds_bytes(int ke) {
-    return ((sizeof(egp_dyn::DynTables) + 7) / 8 + 4 * (size_t)egp_dyn::DY_ENV_DOUBLES + (size_t)4 * ke * (PD_NM_MAX + 192)) * sizeof(double) +
-           2 * PD_NV * 64 * sizeof(short);
-}
+// the dynamic LDS of the DYN kernels: the layouts the kernels address (dyn_lds, multi_dyn_lds)
+size_t egp_pd_server_dyn_lds_bytes() { return dyn_lds::BYTES; }
+constexpr size_t pd_server_multi_dyn_lds_bytes(int ke) { return multi_dyn_lds::bytes(ke); }
 // the static part: s_go, s_abort (rounded up). 160 KiB is what a gfx950 workgroup may declare; two envs per wave fit, three
 // (~186 kB) and four (~223 kB) do not with float64 factors
 constexpr size_t PD_SERVER_STATIC_LDS = 64;
@@ -2559,17 +2466,9 @@ int egp_launch_pd_server(egp_ctx *ctx, const double *qpos, long ld_qpos, const d
                device_dynamics ? const_cast<double *>(bias) : nullptr, nullptr, block_env0, row_contig};
     EGP_REQUIRE(envs_per_wave == 1 || (block_env0 && n_blocks > 0), "the multi-env K1 needs the workgroups' env ranges");
     const dim3 grid(envs_per_wave == 1 ? (n + 3) / 4 : n_blocks);
-    if (device_dynamics && envs_per_wave == 2) {
-        k_pd_server_tree58_multi_dyn<2><<<grid, dim3(256), k.lds, stream>>>(ctx->dm, ld, qpos, qvel, action, qM, bias, n, torque, sv);
-    } else if (device_dynamics) {
-        k_pd_server_tree58<true><<<grid, dim3(256), k.lds, stream>>>(ctx->dm, ld, qpos, qvel, action, qM, bias, n, torque, sv);
-    } else if (envs_per_wave == 1) {
-        k_pd_server_tree58<false><<<grid, dim3(256), 0, stream>>>(ctx->dm, ld, qpos, qvel, action, qM, bias, n, torque, sv);
-    } else if (envs_per_wave == 2) {
-        k_pd_server_tree58_multi<2><<<grid, dim3(256), k.lds, stream>>>(ctx->dm, ld, qpos, qvel, action, qM, bias, n, torque, sv);
-    } else {
-        k_pd_server_tree58_multi<4><<<grid, dim3(256), k.lds, stream>>>(ctx->dm, ld, qpos, qvel, action, qM, bias, n, torque, sv);
-    }
+    int n_envs = n;
+    void *args[] = {&ctx->dm, &ld, &qpos, &qvel, &action, &qM, &bias, &n_envs, &torque, &sv};       // (the kernels' common signature)
+    EGP_HIP_CHECK(hipLaunchKernel(k.fn, grid, dim3(256), args, k.lds, stream));
     return after_launch("k_pd_server_tree58");
 }
 

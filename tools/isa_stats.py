@@ -18,7 +18,8 @@ def regs(tok):
 
 def main():
     text, pat = open(sys.argv[1]).read(), sys.argv[2]
-    m = re.search(r'^(\w*%s\w*):[^\n]*\n(.*?)\n\s*s_endpgm' % re.escape(pat), text, re.S | re.M)
+    # the whole function, up to its .Lfunc_end label (or .size directive): a kernel may hold several s_endpgm (early returns)
+    m = re.search(r'^(\w*%s\w*):[^\n]*\n(.*?)\n\s*(?:\.Lfunc_end\d+:|\.size\s)' % re.escape(pat), text, re.S | re.M)
     if not m:
         sys.exit("kernel %s not found" % pat)
     name, body = m.group(1), m.group(2)
