@@ -249,6 +249,8 @@ SIGNATURES = {
                                           C.POINTER(MlpLayer), _i32, _i32, vp, vp, vp, vp, vp]),
     "egp_policy_forecast_filter_f32": (C.c_int, [vp, vp, C.c_int64, _i32, vp, vp, vp, vp, _i32, vp, vp, C.c_double, vp, vp, vp,
                                                  C.POINTER(MlpLayer), vp, vp, C.c_int64, C.POINTER(MlpLayer), _i32, _i32, vp, vp, vp, vp, vp]),
+    "egp_policy_value_filter_f32": (C.c_int, [vp, vp, C.c_int64, _i32, vp, C.c_int64, _i32, vp, vp, vp, vp, _i32, vp, vp, C.c_double, vp, vp,
+                                              C.POINTER(MlpLayer), _i32, _i32, vp, vp, vp, vp, C.POINTER(MlpLayer), _i32, _i32, vp, vp]),
     "egp_policy_gaussian_staged_f32": (C.c_int, [vp, C.c_int64, _i32, vp, vp, _i32, _i32, C.POINTER(MlpLayer), _i32, _i32, vp, vp, vp, vp, vp, vp,
                                                  C.c_int64, vp]),
     "egp_physics_register": (C.c_int, [C.POINTER(PhysicsVtable), _i32, C.POINTER(vp)]),

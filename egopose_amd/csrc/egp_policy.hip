@@ -247,13 +247,16 @@ struct PolCell {
 // The layers, one pass per chunk of POL_GC x 64 output columns: `cur` holds the workgroup's input rows, `st` the wave's first
 // blocks of layer 0, `split` its share of layer 0's quads. Epilogue of a pass: bias + the waves' partial sums in fixed order
 // (deterministic), then the activation into `nxt` (hidden layer), the Gaussian head (last layer) or, CELL0, layer 0's gates:
-// h' behind the context columns that the prologue has put into `nxt`, h' / c' to the caller's rows.
-template <int R, int NW, int PF, bool CELL0>
+// h' behind the context columns that the prologue has put into `nxt`, h' / c' to the caller's rows. `critic` (BOTH kernels only, a
+// workgroup-uniform flag; constant false elsewhere): the last layer is a value head -- no Gaussian head, no float64 action; its
+// float32 output goes where the actor's goes with `mean_out`.
+template <int R, int NW, int PF, bool CELL0, bool BOTH = false>
 __device__ __forceinline__ void pol_layers(float *cur, float *nxt, float *part, const float *s_bias, const float *s_sd, const float *s_noise,
                                            PolStage<PF> &st, PolSplit split, const PolLayers &L, int act_kind, int xs, int r0, int n, int wave,
                                            const float *__restrict__ noise, double *__restrict__ action, float *__restrict__ mean_out,
-                                           const PolCell &C) {
+                                           const PolCell &C, bool critic_flag = false) {
     constexpr int T = NW * 64, PS = POL_PS;
+    const bool critic = BOTH && critic_flag;
     const int tid = threadIdx.x, lane = tid & 63;
     int bias_off = 0;
     for (int l = 0; l < L.n; ++l) {
@@ -339,6 +342,10 @@ __device__ __forceinline__ void pol_layers(float *cur, float *nxt, float *part, 
                     if (!last) {
 #pragma unroll
                         for (int r = 0; r < R; ++r) nxt[r * xs + col] = real ? pol_act(v[r], act_kind) : 0.0f;
+                    } else if (critic) {
+#pragma unroll
+                        for (int r = 0; r < R; ++r)
+                            if (r0 + r < n) mean_out[(long)(r0 + r) * out + col] = v[r];
                     } else {
                         const float sd = noise ? s_sd[col] : 0.0f;
 #pragma unroll
@@ -368,7 +375,9 @@ __device__ __forceinline__ void pol_layers(float *cur, float *nxt, float *part, 
 // on the chain filter -> policy -> env-step of every tick) the workgroups copy the slab to its device copy themselves -- the
 // kernels that run after the env-step (reward, filter) read it there -- and take their own rows' indices (`t_idx`, which then
 // points into the pinned slab) with ONE load per row.
-template <int R, int NW, int PF, bool FILTER>
+// BOTH (k_policy_value_w4): the workgroups with blockIdx.y != 0 take the same rows through a value stack (`critic`); the filter's
+// outputs (y / y2, st_out) are left to the actor's workgroups.
+template <int R, int NW, int PF, bool FILTER, bool BOTH = false>
 __device__ __forceinline__ void policy_body(const float *__restrict__ ctx_rows, long ctx_row_stride, int ctx_dim,
                                   const long long *__restrict__ t_idx, const double *__restrict__ state, int state_dim, int n,
                                   const PolLayers &L, int act_kind, int xs, const float *__restrict__ log_std,
@@ -376,6 +385,7 @@ __device__ __forceinline__ void policy_body(const float *__restrict__ ctx_rows, 
                                   const unsigned *__restrict__ stage_src, unsigned *__restrict__ stage_dst, int stage_words,
                                   const PolFilter &F) {
     constexpr int T = NW * 64;
+    const bool critic = BOTH && blockIdx.y != 0;
     extern __shared__ __attribute__((aligned(16))) float s_f[];     // see PolCarve; the tail: mean, 1 / std of the filter (2 dim doubles)
     const int out_last = L.out_dim[L.n - 1];
     const PolCarve lds = pol_carve<R, NW>(xs, L.sum_out4, out_last);
@@ -478,7 +488,7 @@ __device__ __forceinline__ void policy_body(const float *__restrict__ ctx_rows, 
         for (int c = tid; c < dim; c += T) {
             double cnt, mean, S;
             egp::zf_merge_column(dim, F.n_tiles, F.ws, F.st_in, c, cnt, mean, S);
-            if (blockIdx.x == 0) {
+            if (!critic && blockIdx.x == 0) {
                 F.st_out[1 + c] = mean;
                 F.st_out[1 + dim + c] = S;
                 if (c == 0) F.st_out[0] = cnt;
@@ -505,7 +515,7 @@ __device__ __forceinline__ void policy_body(const float *__restrict__ ctx_rows, 
                     M.merge(F.n_tiles, q0);
                 }
                 const double cnt = M.cnt, mean = M.mean, S = M.S;
-                if (blockIdx.x == 0 && mine) {
+                if (!critic && blockIdx.x == 0 && mine) {
                     F.st_out[1 + c] = mean;
                     F.st_out[1 + state_dim + c] = S;
                     if (c == 0) F.st_out[0] = cnt;
@@ -523,9 +533,11 @@ __device__ __forceinline__ void policy_body(const float *__restrict__ ctx_rows, 
                         if (row < n) {
                             double x = (raw[r] - mean) * istd;
                             if (F.clip > 0.0) x = fmin(fmax(x, -F.clip), F.clip);
-                            const long e = (long)row * state_dim + c;
-                            F.y[e] = x;
-                            if (F.y2) F.y2[e] = x;
+                            if (!critic) {
+                                const long e = (long)row * state_dim + c;
+                                F.y[e] = x;
+                                if (F.y2) F.y2[e] = x;
+                            }
                             v[r] = (float)x;
                         }
                     }
@@ -556,9 +568,11 @@ __device__ __forceinline__ void policy_body(const float *__restrict__ ctx_rows, 
                     const int c = k - ctx_dim;
                     double x = ((double)F.src.at(row, c) - s_ms[c]) * s_ms[state_dim + c];
                     if (F.clip > 0.0) x = fmin(fmax(x, -F.clip), F.clip);
-                    const long e = (long)row * state_dim + c;
-                    F.y[e] = x;
-                    if (F.y2) F.y2[e] = x;
+                    if (!critic) {
+                        const long e = (long)row * state_dim + c;
+                        F.y[e] = x;
+                        if (F.y2) F.y2[e] = x;
+                    }
                     v = (float)x;
                 } else {
                     v = (float)state[(long)row * state_dim + (k - ctx_dim)];
@@ -584,8 +598,8 @@ __device__ __forceinline__ void policy_body(const float *__restrict__ ctx_rows, 
     pol_warm_sink(warm);
     POL_TR(2);
 
-    pol_layers<R, NW, PF, false>(cur, nxt, part, s_bias, s_sd, s_noise, st, pol_split<NW>(L.in_dim[0], wave), L, act_kind, xs, r0, n, wave,
-                                 noise, action, mean_out, PolCell{});
+    pol_layers<R, NW, PF, false, BOTH>(cur, nxt, part, s_bias, s_sd, s_noise, st, pol_split<NW>(L.in_dim[0], wave), L, act_kind, xs, r0, n, wave,
+                                       noise, action, mean_out, PolCell{}, critic);
 }
 
 // Registers: no cap. A resident K1 workgroup keeps one 346-register wave on every SIMD of its CU for the length of an env-step
@@ -602,6 +616,31 @@ __global__ __launch_bounds__(256) void k_policy_gaussian_w4(const float *__restr
                                                             int stage_words, PolFilter F) {
     policy_body<R, 4, PF, FILTER>(ctx_rows, ctx_row_stride, ctx_dim, t_idx, state, state_dim, n, L, act_kind, xs, log_std, noise, action, mean_out,
                                   stage_src, stage_dst, stage_words, F);
+}
+
+// Actor and critic of a tick in one launch (egp_policy_value_filter_f32): a second grid dimension selects the net. Workgroup
+// (x, 0) is k_policy_gaussian_w4 for rows x R ..: observation -> filter (frozen statistics) -> [policy ctx row | state] -> MLP ->
+// Gaussian head, and it alone writes y / y2 / st_out. Workgroup (x, 1) takes the same rows through the value stack --
+// [value ctx row | state] -> MLP -> value_head, one float32 per row -- and repeats the cheap frozen normalisation for itself, so
+// no workgroup waits for another. Each net has its own layers, context slab, row stride, context width, activation and row
+// stride in LDS (the launch's dynamic LDS is the larger of the two carve-ups); `t_idx` is shared. One copy of policy_body serves
+// both kinds of workgroup (a workgroup-uniform flag skips the filter's stores and picks the last layer's epilogue); the actor's
+// workgroups do the arithmetic of k_policy_gaussian_w4<R, PF, FILTER> on the same values: bit-identical actions.
+struct PolNet {
+    const float *ctx_rows; long ctx_row_stride; int ctx_dim;
+    int act_kind, xs;
+    PolLayers L;
+};
+struct PolNets { PolNet net[2]; };          // actor, critic: indexed with blockIdx.y where it lies, in the kernel's argument segment
+template <int R, int PF, bool FILTER>
+__global__ __launch_bounds__(256) void k_policy_value_w4(PolNets P, const long long *__restrict__ t_idx, const double *__restrict__ state,
+                                                         int state_dim, int n, const float *__restrict__ log_std, const float *__restrict__ noise,
+                                                         double *__restrict__ action, float *__restrict__ mean_out, float *__restrict__ value_out,
+                                                         PolFilter F) {
+    const bool critic = blockIdx.y != 0;
+    const PolNet &N = P.net[blockIdx.y];
+    policy_body<R, 4, PF, FILTER, true>(N.ctx_rows, N.ctx_row_stride, N.ctx_dim, t_idx, state, state_dim, n, N.L, N.act_kind, N.xs,
+                                        critic ? nullptr : log_std, critic ? nullptr : noise, action, critic ? value_out : mean_out, nullptr, nullptr, 0, F);
 }
 
 // ---------------------------------------------------------------------------------------------------------------- forecast
@@ -925,21 +964,72 @@ extern "C" int egp_policy_gaussian_staged_f32(const float *ctx_rows, int64_t ctx
 // filtered observations of (qpos, qvel) -- the group's n rows -- normalised with `zf_in` merged with the tile statistics that
 // egp_obs_zfilter_stats_f64 left in `zf_workspace`; they are also written to y (and y2), and the merged statistics to zf_out:
 // together exactly what egp_obs_zfilter_apply_f64 followed by egp_policy_gaussian_staged_f32 on y2 computes, in one launch.
+// the PolFilter of a *_filter_f32 entry point. zf_workspace == NULL: frozen statistics (no tiles; the wave merge's unconditional
+// tile-0 loads read `zf_in` itself, which has a tile partial's layout, and are discarded)
+static int pol_filter_of(egp_ctx *ctx, const double *qpos, const double *qvel, const int32_t *phase_t, int32_t n, const double *zf_in, double *zf_out,
+                         double clip, double *y, double *y2, const void *zf_workspace, PolFilter &f) {
+    EGP_REQUIRE(ctx && qpos && qvel && zf_in && zf_out && zf_in != zf_out && y, "NULL pointer / zf_out must differ from zf_in");
+    EGP_REQUIRE(n > 0 && (!zf_workspace || n <= 64 * egp::ZF_FUSED_TILES), "merged statistics: 1 .. egp_obs_zfilter_split_max_rows() rows");
+    EGP_REQUIRE(!ctx->dm.obs_phase || phase_t, "the model has obs_phase: phase_t (the rows' cur_t) is required");
+    int rpt, nt = 0;
+    if (zf_workspace) egp::zf_tiling(n, &rpt, &nt);
+    f.src = egp::ZfSrc<double>{nullptr, qpos, qvel, ctx->dm.nq, ctx->dm.nv, ctx->dm.obs_dim, egp::obs_opt_of(ctx->dm), phase_t};
+    f.st_in = zf_in; f.st_out = zf_out; f.ws = zf_workspace ? (const double *)zf_workspace : zf_in; f.n_tiles = nt; f.clip = clip; f.y = y; f.y2 = y2;
+    return EGP_OK;
+}
+
+// egp_policy_gaussian_staged_f32 with the filter's apply pass in front (see PolFilter): the policy input's state columns are the
+// filtered observations of (qpos, qvel) -- the group's n rows -- normalised with `zf_in` merged with the tile statistics that
+// egp_obs_zfilter_stats_f64 left in `zf_workspace`; they are also written to y (and y2), and the merged statistics to zf_out:
+// together exactly what egp_obs_zfilter_apply_f64 followed by egp_policy_gaussian_staged_f32 on y2 computes, in one launch.
+// zf_workspace == NULL: `zf_in` as it stands (the frozen filter of an evaluation); zf_out receives a copy of it.
 extern "C" int egp_policy_gaussian_filter_f32(egp_ctx *ctx, const float *ctx_rows, int64_t ctx_row_stride, int32_t ctx_dim, const int64_t *t_idx,
                                               const double *qpos, const double *qvel, const int32_t *phase_t, int32_t n, const double *zf_in, double *zf_out,
                                               double clip, double *y, double *y2, const void *zf_workspace,
                                               const egp_mlp_layer *layers, int32_t n_layers, int32_t activation, const float *log_std,
                                               const float *noise, double *action, float *mean_out, const void *stage_src, void *stage_dst,
                                               int64_t stage_bytes, void *stream) {
-    EGP_REQUIRE(ctx && qpos && qvel && zf_in && zf_out && zf_in != zf_out && y && zf_workspace, "NULL pointer / zf_out must differ from zf_in");
-    EGP_REQUIRE(n > 0 && n <= 64 * egp::ZF_FUSED_TILES, "1 .. egp_obs_zfilter_split_max_rows() rows");
-    const int dim = ctx->dm.obs_dim;
-    int rpt, nt;
-    egp::zf_tiling(n, &rpt, &nt);
     PolFilter f;
-    EGP_REQUIRE(!ctx->dm.obs_phase || phase_t, "the model has obs_phase: phase_t (the rows' cur_t) is required");
-    f.src = egp::ZfSrc<double>{nullptr, qpos, qvel, ctx->dm.nq, ctx->dm.nv, dim, egp::obs_opt_of(ctx->dm), phase_t};
-    f.st_in = zf_in; f.st_out = zf_out; f.ws = (const double *)zf_workspace; f.n_tiles = nt; f.clip = clip; f.y = y; f.y2 = y2;
-    return policy_launch(ctx_rows, ctx_row_stride, ctx_dim, t_idx, nullptr, dim, n, layers, n_layers, activation, log_std, noise, action, mean_out,
-                         stage_src, stage_dst, stage_bytes, stream, &f);
+    if (int rc = pol_filter_of(ctx, qpos, qvel, phase_t, n, zf_in, zf_out, clip, y, y2, zf_workspace, f)) return rc;
+    return policy_launch(ctx_rows, ctx_row_stride, ctx_dim, t_idx, nullptr, ctx->dm.obs_dim, n, layers, n_layers, activation, log_std, noise, action,
+                         mean_out, stage_src, stage_dst, stage_bytes, stream, &f);
+}
+
+// Actor and critic of an evaluation tick in one launch (k_policy_value_w4): per row the observation of (qpos, qvel), the frozen
+// filter, [policy ctx row | state] -> `layers` -> Gaussian head -> action (as egp_policy_gaussian_filter_f32 with zf_workspace ==
+// NULL, bit for bit) and [value ctx row | state] -> `vlayers` -> value_out[row] (float32; the last of vlayers is the value head,
+// out_dim 1). zf_in == NULL: no filter -- `y` must hold the rows' states already and is read, not written.
+extern "C" int egp_policy_value_filter_f32(egp_ctx *ctx, const float *ctx_rows, int64_t ctx_row_stride, int32_t ctx_dim, const float *vctx_rows,
+                                           int64_t vctx_row_stride, int32_t vctx_dim, const int64_t *t_idx, const double *qpos, const double *qvel,
+                                           const int32_t *phase_t, int32_t n, const double *zf_in, double *zf_out, double clip, double *y, double *y2,
+                                           const egp_mlp_layer *layers, int32_t n_layers, int32_t activation, const float *log_std,
+                                           const float *noise, double *action, float *mean_out, const egp_mlp_layer *vlayers, int32_t n_vlayers,
+                                           int32_t vactivation, float *value_out, void *stream) {
+    EGP_REQUIRE(n >= 0, "n < 0");
+    if (n == 0) return EGP_OK;
+    EGP_REQUIRE(ctx && ctx_rows && vctx_rows && t_idx && y && layers && vlayers && action && value_out, "NULL pointer");
+    EGP_REQUIRE(!noise || log_std, "noise needs log_std");
+    EGP_REQUIRE(n_layers >= 1 && n_layers <= POL_MAX_LAYERS && n_vlayers >= 1 && n_vlayers <= POL_MAX_LAYERS, "1..8 layers per net (hidden layers + output layer)");
+    EGP_REQUIRE(activation >= 0 && activation <= 2 && vactivation >= 0 && vactivation <= 2, "activation: 0 tanh, 1 relu, 2 sigmoid");
+    EGP_REQUIRE(ctx_dim >= 0 && vctx_dim >= 0 && ctx_row_stride >= 0 && vctx_row_stride >= 0, "bad context dims");
+    const int dim = ctx->dm.obs_dim;
+    PolFilter f{};
+    if (zf_in)
+        if (int rc = pol_filter_of(ctx, qpos, qvel, phase_t, n, zf_in, zf_out, clip, y, y2, nullptr, f)) return rc;
+    PolNets P{{{ctx_rows, (long)ctx_row_stride, ctx_dim, activation, 0, {}}, {vctx_rows, (long)vctx_row_stride, vctx_dim, vactivation, 0, {}}}};
+    PolNet &A = P.net[0], &V = P.net[1];
+    int kmax;
+    size_t lds_a, lds_v;
+    if (int rc = pol_layer_table(nullptr, layers, n_layers, ctx_dim + dim, "policy layer dims do not chain", A.L, &kmax)) return rc;
+    if (int rc = pol_lds(A.L, kmax, 0, zf_in ? 2 * dim : 0, &A.xs, &lds_a)) return rc;
+    if (int rc = pol_layer_table(nullptr, vlayers, n_vlayers, vctx_dim + dim, "value layer dims do not chain", V.L, &kmax)) return rc;
+    if (int rc = pol_lds(V.L, kmax, 0, zf_in ? 2 * dim : 0, &V.xs, &lds_v)) return rc;
+    EGP_REQUIRE(vlayers[n_vlayers - 1].out_dim == 1, "the value net's last layer is the value head (out_dim 1)");
+    const size_t lds = lds_a > lds_v ? lds_a : lds_v;
+    const dim3 grid((n + POL_R - 1) / POL_R, 2), block(POL_NW * 64);
+#define POL_GO(FLT) k_policy_value_w4<POL_R, POL_PF, FLT><<<grid, block, lds, (hipStream_t)stream>>>(                                       \
+        P, (const long long *)t_idx, y, dim, n, log_std, noise, action, mean_out, value_out, f)
+    if (zf_in) POL_GO(true); else POL_GO(false);
+#undef POL_GO
+    return pol_launched("k_policy_value");
 }

@@ -8,11 +8,26 @@ Per take: roll the policy over the whole clip (`fix_len = len - 2*fr_margin`) wi
 fail-safe fires -- 'valuefs': the value estimate drops below 0.6 x its running mean, 'naivefs': the env reports a
 fall -- re-seat the humanoid on the state regressor's prediction for the next frame, aligned to where the
 character stands (utils/tools.py:71-75). Rendering (`env_vis`, `--render`) is out of scope.
+
+`BatchedEvaluator` is the same evaluation with the takes side by side: every take is a slot of `env.batched(N)`, all slots advance
+in lockstep, in passes of N takes in take order, and a tick is
+
+    record qpos / qvel -> [observation -> frozen filter -> policy MLP -> mean action | value MLP -> value] -> env-step
+    -> host: fail-safe decision per slot -> re-seat the flagged slots on their take's state_pred[t + 1]
+
+with the bracket one launch (`FusedActorCritic.with_filter`, egp_policy_value_filter_f32) and the values' copy to pinned memory
+queued behind it. The video contexts and the state regressor's predictions of a take are computed once per take, at batch 1 as
+above (a take's result does not depend on the slot count). 'valuefs' compares against a running mean over ALL values in take
+order; `egopose_amd.failsafe` makes that exact for takes that run side by side (speculative runs, checked against the true
+statistic afterwards, re-run where a decision differs). The reward (which nothing reads) is not evaluated; `causal` and
+`show_noise` stay with `Evaluator`.
 """
 from __future__ import annotations
 
+import copy
 import os
 import pickle
+import time
 
 import numpy as np
 import torch
@@ -141,12 +156,235 @@ class Evaluator:
         return path
 
 
+class BatchedEvaluator:
+    """`Evaluator` with the takes on `num_envs` lockstep slots (module docstring). `run()` -> the same (results, meta), `save()`
+    the same pickle. `keep_trace`: `self.trace[take]` = dict(actions [T][nu], values [T], resets, state_pred, states [T][obs]) of
+    the accepted run. `self.timing`: wall seconds of the last run, split into the wait for the host physics and the rest, and the
+    fail-safe scheduler's passes."""
+
+    def __init__(self, cfg, env, policy_net, policy_vs_net, value_net, value_vs_net, state_net, state_net_mean, state_net_std,
+                 running_state=None, fail_safe="valuefs", causal=False, show_noise=False, sync=False, logger=None,
+                 keep_trace=False, num_envs=8, device_index=0, n_threads=None):
+        from . import policy_step
+        from .failsafe import SpeculativeValueFailSafe
+        if fail_safe not in ("valuefs", "naivefs", "none"):
+            raise ValueError("fail_safe must be 'valuefs', 'naivefs' or 'none'")
+        if causal or show_noise:
+            raise NotImplementedError("causal / show_noise evaluation runs take by take: use Evaluator")
+        if running_state is not None and not (running_state.demean and running_state.destd):
+            raise NotImplementedError("running_state without demean / destd: use Evaluator")
+        if not (policy_step.supported(policy_net) and policy_step.supported_value(value_net)):
+            raise NotImplementedError("the batched evaluation needs the HIP actor + critic step (float32 PolicyGaussian and Value "
+                                      "over plain MLPs): use Evaluator")
+        self.cfg, self.env = cfg, env
+        self.policy_net, self.policy_vs_net = policy_net, policy_vs_net
+        self.value_net, self.value_vs_net = value_net, value_vs_net
+        self.state_net = state_net
+        self.state_net_mean, self.state_net_std = np.asarray(state_net_mean, float), np.asarray(state_net_std, float)
+        self.running_state = running_state
+        self.fail_safe, self.causal, self.show_noise, self.sync = fail_safe, False, False, sync
+        self.num_envs, self.device_index, self.n_threads = int(num_envs), int(device_index), n_threads
+        self._fs = SpeculativeValueFailSafe()
+        self.logger = logger
+        self.trace = {} if keep_trace else None
+        self.timing = {}
+        for net in (policy_net, policy_vs_net, value_net, value_vs_net, state_net):
+            net.eval()
+        for net in (policy_vs_net, value_vs_net):
+            net.set_mode("test")
+
+    value_stat = property(lambda self: self._fs.stat)      # the running statistic of every accepted value, across run() calls
+
+    # ------------------------------------------------------------------ per take, once: contexts and regressor states (batch 1)
+    @torch.no_grad()
+    def _take_tables(self, i):
+        env, m = self.env, self.cfg.fr_margin
+        p = next(self.policy_net.parameters())
+        cnn_feat = torch.as_tensor(env.cnn_feat[i], dtype=p.dtype, device=p.device)
+        test_len = cnn_feat.shape[0] - 2 * m
+        ex = env.expert_arr[i]
+        if test_len < 1 or ex["qpos"].shape[0] < m + test_len:
+            raise ValueError("take %s: no frames between the margins, or fewer expert frames than features" % env.expert_list[i])
+        self.policy_vs_net.initialize(cnn_feat)
+        self.value_vs_net.initialize(cnn_feat)
+        sp = next(self.state_net.parameters())
+        state_pred = self.state_net(cnn_feat.to(device=sp.device, dtype=sp.dtype).unsqueeze(1))[m:-m].double().cpu().numpy()
+        state_pred = state_pred * self.state_net_std[None, :] + self.state_net_mean[None, :]
+        return dict(len=test_len, pol=self.policy_vs_net.v_out.float().contiguous(), val=self.value_vs_net.v_out.float().contiguous(),
+                    state_pred=state_pred, orig=np.array(ex["qpos"][m:m + test_len], float))
+
+    # ------------------------------------------------------------------ ego_mimic_eval.py:93-100 for a set of slots
+    @staticmethod
+    def _seat_rows(states, ref_qpos):
+        nq = ref_qpos.shape[1]
+        qpos = np.array(ref_qpos, float, copy=True)
+        qpos[:, 2:] = states[:, :nq - 2]
+        qvel = np.array(states[:, nq - 2:], float, copy=True)
+        for k in range(qpos.shape[0]):
+            metrics.align_human_state(qpos[k], qvel[k], ref_qpos[k])
+        return qpos, qvel
+
+    def _reseat_below(self, i):
+        """naivefs: the head height below which take i counts as fallen (env.py: HumanoidEnv.step)."""
+        env = self.env
+        return env.fix_head_lb if env.fix_head_lb is not None else float(env.expert_arr[i]["head_height_lb"]) - 0.1
+
+    # ------------------------------------------------------------------ ego_mimic_eval.py:103-175 for N takes at a time
+    @torch.no_grad()
+    def _run_pass(self, take_inds, prefixes):
+        """Run the takes `take_inds` (indices into the expert list), each from a copy of its prefix statistic, in passes of N
+        slots -> [(values, taken re-seat decisions)]; the full records go to self._latest."""
+        from .failsafe import below
+        env, R, tm = self.env, self._run, self.timing
+        sim, ctx, eng, fused, N = R["sim"], R["ctx"], R["eng"], R["fused"], self.num_envs
+        out = []
+        for c0 in range(0, len(take_inds), N):
+            chunk = take_inds[c0:c0 + N]
+            k = len(chunk)
+            tabs = [R["tables"][i] for i in chunk]
+            lens = np.array([tb["len"] for tb in tabs])
+            stats = [copy.deepcopy(st) for st in prefixes[c0:c0 + N]]
+            for j, tb in enumerate(tabs):
+                R["pol_slab"][j, :tb["len"]] = tb["pol"]
+                R["val_slab"][j, :tb["len"]] = tb["val"]
+            ref0 = np.stack([env.expert_arr[i]["qpos"][self.cfg.fr_margin] for i in chunk])
+            q0, v0 = self._seat_rows(np.stack([tb["state_pred"][0] for tb in tabs]), ref0)
+            ids = np.arange(k)
+            if not R["seated"] and k < N:         # slots no take ever lands on: a valid state all the same (they are never stepped)
+                ids = np.arange(N)
+                q0, v0 = np.concatenate((q0, np.repeat(q0[:1], N - k, 0))), np.concatenate((v0, np.repeat(v0[:1], N - k, 0)))
+            R["seated"] = True
+            eng.reset(ids, q0, v0)
+            active = np.zeros(N, np.int32)
+            active[:k] = 1
+            resets = [[] for _ in range(k)]
+            below_lb = np.array([self._reseat_below(i) for i in chunk]) if self.fail_safe == "naivefs" else None
+            traj, qv, actions, states, v_dev, v_host = R["traj"], R["qv"], R["actions"], R["states"], R["v_dev"], R["v_host"]
+            for t in range(int(lens.max())):
+                traj[t, :k].copy_(eng.qpos[:k])
+                qv[t, :k].copy_(eng.qvel[:k])
+                fused.with_filter(ctx, R["pol_slab"][:k], R["t_all"][t, :k], eng.qpos[:k], eng.qvel[:k], R["zf_in"], None, R["clip"], states[t, :k], None,
+                                  None, actions[t, :k], R["val_slab"][:k], v_dev[t, :k], phase_t=None if R["phase"] is None else R["phase"][t, :k])
+                ev = torch.cuda.Event()
+                ev.record()
+                v_host[t].copy_(v_dev[t], non_blocking=True)
+                ev_v = torch.cuda.Event()
+                ev_v.record()
+                eng.step_async(0, actions[t], active, ev)
+                t0 = time.time()
+                eng.wait(0)
+                tm["phys_wait"] += time.time() - t0
+                ev_v.synchronize()
+                flagged = []
+                for j in range(k):
+                    if not active[j]:
+                        continue
+                    value = float(v_host[t, j])
+                    if stats[j] is not None:
+                        stats[j].push(np.array([value]))
+                    if t + 1 >= lens[j]:                       # info['end']: no decision, the take is over
+                        active[j] = 0
+                        continue
+                    if self.fail_safe == "valuefs":
+                        hit = below(value, stats[j])
+                    elif self.fail_safe == "naivefs":
+                        hit = bool(eng.head_z[j] < below_lb[j])
+                    else:
+                        hit = False
+                    if hit:
+                        flagged.append(j)
+                        resets[j].append(t)
+                if flagged:
+                    fl = np.array(flagged)
+                    q1, v1 = self._seat_rows(np.stack([tabs[j]["state_pred"][t + 1] for j in flagged]), np.array(eng.qpos_host[fl], float))
+                    eng.reset(fl, q1, v1)
+                tm["ticks"] += 1
+            torch.cuda.synchronize(R["dev"])
+            T = int(lens.max())
+            h_traj, h_qv, h_act, h_st = (x[:T, :k].transpose(0, 1).cpu().numpy() for x in (traj, qv, actions, states))
+            h_val = v_host[:T, :k].t().double().numpy().copy()
+            for j, i in enumerate(chunk):
+                L = int(lens[j])
+                taken = np.zeros(L, bool)
+                taken[resets[j]] = True
+                self._latest[i] = dict(traj_pred=h_traj[j, :L].copy(), vel_pred=h_qv[j, :L].copy(), actions=h_act[j, :L].copy(),
+                                       states=h_st[j, :L].copy(), values=h_val[j, :L].copy(), resets=list(resets[j]))
+                out.append((h_val[j, :L], taken))
+            tm["passes"] += 1
+        return out
+
+    def run(self, takes=None):
+        """Evaluate every take of the env's expert list (or of `takes`) -> (results, meta) in the reference's pickle layout."""
+        from . import policy_step
+        env, N = self.env, self.num_envs
+        t_all = time.time()
+        sel = [i for i, take in enumerate(env.expert_list) if takes is None or take in takes]
+        self.timing = tm = {"phys_wait": 0.0, "passes": 0, "takes": len(sel), "ticks": 0, "fs_passes": 0, "fs_pass_takes": []}
+        self._latest = {}
+        if sel:
+            sim = env.batched(N, self.device_index, self.n_threads, 1)
+            ctx, eng = sim.ctx, sim.engine
+            dev = torch.device("cuda", ctx.device)
+            with torch.no_grad(), torch.cuda.device(dev):
+                tables = {i: self._take_tables(i) for i in sel}
+                Tm = max(tb["len"] for tb in tables.values())
+                f64, f32 = torch.float64, torch.float32
+                z = lambda *shape, dtype=f64: torch.zeros(*shape, dtype=dtype, device=dev)
+                zf_in, clip = None, 0.0
+                if self.running_state is not None:
+                    zf_in, clip = self.running_state.to_device_state(dev), float(self.running_state.clip or 0.0)
+                self._run = dict(sim=sim, ctx=ctx, eng=eng, dev=dev, tables=tables, seated=False, zf_in=zf_in, clip=clip,
+                                 fused=policy_step.FusedActorCritic(self.policy_net, self.value_net, dev),
+                                 pol_slab=z(N, Tm, self.policy_vs_net.v_hdim, dtype=f32), val_slab=z(N, Tm, self.value_vs_net.v_hdim, dtype=f32),
+                                 traj=z(Tm, N, ctx.nq), qv=z(Tm, N, ctx.nv), actions=z(Tm, N, ctx.nu), states=z(Tm, N, ctx.obs_dim),
+                                 v_dev=z(Tm, N, dtype=f32), v_host=torch.zeros(Tm, N, dtype=f32).pin_memory(),
+                                 t_all=torch.arange(Tm, dtype=torch.int64, device=dev).unsqueeze(1).expand(Tm, N).contiguous(),
+                                 phase=torch.arange(Tm, dtype=torch.int32, device=dev).unsqueeze(1).expand(Tm, N).contiguous() if ctx.obs_phase else None)
+                if self.fail_safe == "valuefs":
+                    self._fs.run(sel, self._run_pass)
+                    tm["fs_passes"], tm["fs_pass_takes"] = self._fs.passes, list(self._fs.pass_takes)
+                else:
+                    self._run_pass(sel, [None] * len(sel))
+                    tm["fs_passes"], tm["fs_pass_takes"] = 1, [len(sel)]
+            self._run = None
+        traj_pred, traj_orig, vel_pred, num_reset = {}, {}, {}, 0
+        for i in sel:
+            take, rec = env.expert_list[i], self._latest[i]
+            traj_pred[take], traj_orig[take], vel_pred[take] = rec["traj_pred"], tables[i]["orig"], rec["vel_pred"]
+            num_reset += len(rec["resets"])
+            if self.logger is not None:
+                for _ in rec["resets"]:
+                    self.logger.info("reset state!")
+            if self.trace is not None:
+                self.trace[take] = dict(actions=rec["actions"], values=rec["values"], resets=rec["resets"], state_pred=tables[i]["state_pred"],
+                                        states=rec["states"])
+        self._latest = None
+        tm["total"] = time.time() - t_all
+        tm["rest"] = tm["total"] - tm["phys_wait"]
+        return {"traj_pred": traj_pred, "traj_orig": traj_orig, "vel_pred": vel_pred}, {"algo": "ego_mimic", "num_reset": num_reset}
+
+    save = Evaluator.save
+
+
+def select_evaluator(policy_net, value_net, num_envs=1, sequential=False, causal=False, show_noise=False):
+    """Which evaluator `main()` uses -> (class, reason or None): BatchedEvaluator for num_envs > 1 unless something needs the
+    take-by-take path (then Evaluator, with the reason to print)."""
+    from . import policy_step
+    if sequential or int(num_envs) <= 1:
+        return Evaluator, None
+    if causal or show_noise:
+        return Evaluator, "--causal / --show-noise run take by take"
+    if not (policy_step.supported(policy_net) and policy_step.supported_value(value_net)):
+        return Evaluator, "the nets are outside the fused actor + critic step (float32 PolicyGaussian and Value over plain MLPs)"
+    return BatchedEvaluator, None
+
+
 def compute_metrics(results, dt=1.0 / 30.0, algo="ego_mimic", verbose=False):
     return metrics.compute_metrics(results, dt, algo, verbose)
 
 
 def main(argv=None):
-    """`python -m egopose_amd.evaluate --cfg subject_03 --iter 3000 --data test [--fail-safe naivefs] [--causal]`:
+    """`python -m egopose_amd.evaluate --cfg subject_03 --iter 3000 --data test [--fail-safe naivefs] [--causal] [--num-envs N] [--sequential]`:
     the non-rendering part of ego_pose/ego_mimic_eval.py (checkpoint + state-net loading: :60-80) followed by the
     statistics of ego_pose/eval_pose.py (--mode stats)."""
     import argparse
@@ -161,6 +399,8 @@ def main(argv=None):
     ap.add_argument("--causal", action="store_true")
     ap.add_argument("--show-noise", action="store_true")
     ap.add_argument("--gpu-index", type=int, default=0)
+    ap.add_argument("--num-envs", type=int, default=1, help="> 1: takes side by side on that many env slots (BatchedEvaluator)")
+    ap.add_argument("--sequential", action="store_true", help="take by take (Evaluator) whatever --num-envs says")
     args = ap.parse_args(argv)
     cfg = Config(args.cfg, create_dirs=False)
     dev, dtype = torch.device("cuda", args.gpu_index), torch.float32
@@ -185,8 +425,17 @@ def main(argv=None):
     state_net.load_state_dict(sn_cp["state_net_dict"])
     for net in (policy, policy_vs, value, value_vs, state_net):
         net.to(dev, dtype)
-    ev = Evaluator(cfg, env, policy, policy_vs, value, value_vs, state_net, meta["mean"], meta["std"], running_state=cp["running_state"],
-                   fail_safe=args.fail_safe, causal=args.causal, show_noise=args.show_noise)
+    cls, why = select_evaluator(policy, value, args.num_envs, args.sequential, args.causal, args.show_noise)
+    if why is not None:
+        print("falling back to the sequential Evaluator: %s" % why)
+    if cls is BatchedEvaluator:
+        if args.fail_safe == "naivefs":
+            env.set_fix_head_lb(0.3)                   # ego_mimic_eval.py:51-52 (the sequential path keeps the take's own bound)
+        ev = BatchedEvaluator(cfg, env, policy, policy_vs, value, value_vs, state_net, meta["mean"], meta["std"], running_state=cp["running_state"],
+                              fail_safe=args.fail_safe, num_envs=args.num_envs, device_index=args.gpu_index)
+    else:
+        ev = Evaluator(cfg, env, policy, policy_vs, value, value_vs, state_net, meta["mean"], meta["std"], running_state=cp["running_state"],
+                       fail_safe=args.fail_safe, causal=args.causal, show_noise=args.show_noise)
     results, rmeta = ev.run()
     path = ev.save(results, rmeta, args.iter, args.data)
     print("num reset: %d, saved results to %s" % (rmeta["num_reset"], path))

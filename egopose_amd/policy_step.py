@@ -5,7 +5,8 @@ weights, packed for the kernel's matrix-core tiles, in persistent buffers (`refr
 addresses stay fixed for hipGraphs). `FusedForecastPolicy` is the ego_forecast form (`egp_policy_forecast_f32`): one step
 of VideoForecastNet's state LSTM cell (models/video_forecast_net.py:88-93, models/rnn.py:29-36) in front of the same MLP,
 the cell's h / c updated in place; its `with_filter` (`egp_policy_forecast_filter_f32`) puts the observation filter's apply
-pass in front of it, merged with a tick's tile statistics or frozen."""
+pass in front of it, merged with a tick's tile statistics or frozen. `FusedActorCritic` is the ego_mimic evaluation's tick
+(`egp_policy_value_filter_f32`): the frozen filter, the policy step and the value net of the same rows in one launch."""
 from __future__ import annotations
 
 import ctypes as C
@@ -43,6 +44,16 @@ def supported(policy_net) -> bool:
             and max(l.out_features for l in net.affine_layers) <= 2048)
 
 
+def supported_value(value_net) -> bool:
+    """True when `value_net` is a Value over a plain float32 MLP with an activation the kernel implements, inside its limits."""
+    net, head = getattr(value_net, "net", None), getattr(value_net, "value_head", None)
+    return (isinstance(head, nn.Linear) and head.out_features == 1 and hasattr(net, "affine_layers") and len(net.affine_layers) >= 1
+            and getattr(net, "activation", None) in _ACT_CODE and len(net.affine_layers) + 1 <= 8
+            and head.weight.dtype == torch.float32 and all(l.weight.dtype == torch.float32 for l in net.affine_layers)
+            and head.in_features == net.affine_layers[-1].out_features
+            and max(max(l.in_features, l.out_features) for l in net.affine_layers) <= 2048)
+
+
 def supported_forecast(policy_net, vs_net) -> bool:
     """True when `supported(policy_net)` and `vs_net` is a VideoForecastNet whose state net is one float32 nn.LSTMCell
     (with biases, one direction) inside the kernel's limits. (`s_net_type == 'id'` passes the state through unchanged:
@@ -59,7 +70,7 @@ def supported_forecast(policy_net, vs_net) -> bool:
 
 class FusedGaussianPolicy:
 
-    def __init__(self, policy_net, device, _front=()):
+    def __init__(self, policy_net, device, _front=(), _back=()):
         if not supported(policy_net):
             raise ValueError("policy net is not a float32 PolicyGaussian over an MLP")
         self.lib = L.load()
@@ -68,12 +79,12 @@ class FusedGaussianPolicy:
         self.act = _ACT_CODE[policy_net.net.activation]
         # the kernel's packed weight form (include/egopose_hip.h: egp_mlp_layer): one 64-column x 4-feature block per wave load
         # (ONE buffer, layer after layer: the kernel's L2 warm-up walks it as a single range)
-        # (`_front`: (in, out) of packed layers a subclass keeps in front of the MLP's, in the same allocation)
-        dims = list(_front) + [(l.in_features, l.out_features) for l in self.layers]
+        # (`_front` / `_back`: (in, out) of packed layers a subclass keeps in front of / behind the MLP's, in the same allocation)
+        dims = list(_front) + [(l.in_features, l.out_features) for l in self.layers] + list(_back)
         sizes = [int(self.lib.egp_mlp_pack_floats(i, o)) for i, o in dims]
         self.wt_all = torch.zeros(sum(sizes), dtype=torch.float32, device=device)
         parts = list(torch.split(self.wt_all, sizes))
-        self.front_wt, self.wt = parts[:len(_front)], parts[len(_front):]
+        self.front_wt, self.wt, self.back_wt = parts[:len(_front)], parts[len(_front):len(parts) - len(_back)], parts[len(parts) - len(_back):]
         self.bias = [torch.empty(l.out_features, dtype=torch.float32, device=device) for l in self.layers]
         self.log_std = torch.empty(self.layers[-1].out_features, dtype=torch.float32, device=device)
         self.desc = (L.MlpLayer * len(self.layers))()
@@ -109,12 +120,20 @@ class FusedGaussianPolicy:
                                                  L.current_stream()), "egp_policy_gaussian_f32")
         return action_out
 
+    def _zf_scratch(self, zf_in):
+        if getattr(self, "_zf_copy", None) is None or self._zf_copy.shape != zf_in.shape or self._zf_copy.device != zf_in.device:
+            self._zf_copy = torch.empty_like(zf_in)
+        return self._zf_copy
+
     def with_filter(self, ctx, ctx_rows, t_idx, qpos, qvel, zf_in, zf_out, clip, y, y2, workspace, action_out, noise=None, mean_out=None,
                     phase_t=None):
         """The filter's apply pass + the policy step in one launch (`egp_policy_gaussian_filter_f32`): the state columns are the
         observations of (qpos, qvel) normalised with `zf_in` merged with the tile statistics `ctx.obs_zfilter_stats` left in
-        `workspace`; y / y2 receive them, `zf_out` the merged statistics. `ctx`: the EgpContext of the model."""
+        `workspace`; y / y2 receive them, `zf_out` the merged statistics. `workspace=None`: `zf_in` as it stands -- the frozen
+        filter of an evaluation, `running_state(x, update=False)`; `zf_out` may be None then. `ctx`: the EgpContext of the model."""
         n, T, H = ctx_rows.shape
+        if workspace is None and zf_out is None:      # the frozen filter (`zf_in` as it stands): the kernel still writes its copy of the statistics
+            zf_out = self._zf_scratch(zf_in)
         L.check(self.lib.egp_policy_gaussian_filter_f32(ctx.handle, _ptr(ctx_rows), int(ctx_rows.stride(0)), H, _ptr(t_idx), _ptr(qpos), _ptr(qvel),
                                                         _ptr(ctx._phase_t(phase_t, n)), n,
                                                         _ptr(zf_in), _ptr(zf_out), float(clip or 0.0), _ptr(y), _ptr(y2), _ptr(workspace),
@@ -201,4 +220,73 @@ class FusedForecastPolicy(FusedGaussianPolicy):
                                                         self.desc, len(self.layers), self.act, _ptr(self.log_std), _ptr(noise),
                                                         _ptr(action_out), _ptr(mean_out), L.current_stream()),
                 "egp_policy_forecast_filter_f32")
+        return action_out
+
+
+class FusedActorCritic(FusedGaussianPolicy):
+    """The ego_mimic evaluation's tick in one launch (`egp_policy_value_filter_f32`): observation -> frozen filter ->
+    [policy context row | state] -> policy MLP -> Gaussian head, and [value context row | state] -> value MLP -> value_head for
+    the same rows. The value net's packed layers sit behind the policy's in `wt_all`."""
+
+    def __init__(self, policy_net, value_net, device):
+        if not supported_value(value_net):
+            raise ValueError("value net is not a float32 Value over an MLP")
+        self.value_net = value_net
+        self.vlayers = list(value_net.net.affine_layers) + [value_net.value_head]
+        self.vact = _ACT_CODE[value_net.net.activation]
+        self.vbias = [torch.empty(l.out_features, dtype=torch.float32, device=device) for l in self.vlayers]
+        super().__init__(policy_net, device, _back=[(l.in_features, l.out_features) for l in self.vlayers])
+        self.vdesc = (L.MlpLayer * len(self.vlayers))()
+        for i, l in enumerate(self.vlayers):
+            self.vdesc[i].wt = self.back_wt[i].data_ptr()
+            self.vdesc[i].bias = self.vbias[i].data_ptr()
+            self.vdesc[i].in_dim, self.vdesc[i].out_dim = l.in_features, l.out_features
+        self.v_in_dim = self.vlayers[0].in_features
+
+    @torch.no_grad()
+    def refresh(self):
+        """Pack the live parameters of both nets into the kernel's buffers."""
+        super().refresh()
+        stream = L.current_stream()
+        for l, wt, b in zip(self.vlayers, self.back_wt, self.vbias):
+            w = l.weight if l.weight.stride(1) == 1 else l.weight.contiguous()
+            L.check(self.lib.egp_mlp_pack_f32(C.c_void_p(w.data_ptr()), int(w.stride(0)), l.in_features, l.out_features,
+                                              C.c_void_p(wt.data_ptr()), stream), "egp_mlp_pack_f32")
+            b.copy_(l.bias)
+
+    def with_filter(self, ctx, ctx_rows, t_idx, qpos, qvel, zf_in, zf_out, clip, y, y2, workspace, action_out, value_ctx_rows, value_out,
+                    noise=None, mean_out=None, phase_t=None):
+        """As `FusedGaussianPolicy.with_filter(..., workspace=None)` (the frozen filter -- `workspace` must be None; actions, y, y2
+        bit-identical to it) plus the critic: value_ctx_rows float32 [n][T][Hv] (the value net's context tables, indexed by the same
+        `t_idx`), value_out float32 [n]. `zf_in=None` (a checkpoint without running_state): the raw observations go to y / y2 and
+        into both nets."""
+        if workspace is not None:
+            raise ValueError("the actor + critic step normalises with frozen statistics only (workspace=None)")
+        n, T, H = ctx_rows.shape
+        S = ctx.obs_dim
+        nv_, Tv, Hv = value_ctx_rows.shape
+        if H + S != self.in_dim or Hv + S != self.v_in_dim or nv_ != n:
+            raise ValueError("context dims %d / %d + observation dim %d do not fit the policy input %d / the value input %d"
+                             % (H, Hv, S, self.in_dim, self.v_in_dim))
+        assert qpos.dtype == torch.float64 and qpos.is_contiguous() and qpos.shape == (n, ctx.nq)
+        assert qvel.dtype == torch.float64 and qvel.is_contiguous() and qvel.shape == (n, ctx.nv)
+        for t in (y, y2):
+            assert t is None or (t.dtype == torch.float64 and t.is_contiguous() and t.shape == (n, S))
+        assert y is not None
+        _check_io(ctx_rows, t_idx, y, action_out, noise, mean_out, self.nu)
+        assert value_ctx_rows.dtype == torch.float32 and value_ctx_rows.stride(2) == 1 and value_ctx_rows.stride(1) == Hv
+        assert value_out.dtype == torch.float32 and value_out.is_contiguous() and value_out.numel() == n
+        if zf_in is None:
+            ctx.obs_zfilter(qpos, qvel, None, None, clip, y, out2=y2, phase_t=phase_t)
+        else:
+            for t in (zf_in, zf_out):
+                assert t is None or (t.dtype == torch.float64 and t.is_contiguous() and t.shape == (1 + 2 * S,))
+            if zf_out is None:
+                zf_out = self._zf_scratch(zf_in)
+        L.check(self.lib.egp_policy_value_filter_f32(ctx.handle, _ptr(ctx_rows), int(ctx_rows.stride(0)), H, _ptr(value_ctx_rows),
+                                                     int(value_ctx_rows.stride(0)), Hv, _ptr(t_idx), _ptr(qpos), _ptr(qvel),
+                                                     _ptr(ctx._phase_t(phase_t, n)), n, _ptr(zf_in), _ptr(zf_out), float(clip or 0.0), _ptr(y), _ptr(y2),
+                                                     self.desc, len(self.layers), self.act, _ptr(self.log_std), _ptr(noise), _ptr(action_out),
+                                                     _ptr(mean_out), self.vdesc, len(self.vlayers), self.vact, _ptr(value_out), L.current_stream()),
+                "egp_policy_value_filter_f32")
         return action_out

@@ -540,6 +540,26 @@ int egp_policy_gaussian_filter_f32(egp_ctx *ctx, const float *ctx_rows, int64_t 
                                    const egp_mlp_layer *layers, int32_t n_layers, int32_t activation, const float *log_std,
                                    const float *noise, double *action, float *mean_out, const void *stage_src, void *stage_dst,
                                    int64_t stage_bytes, void *stream);
+/* zf_workspace == NULL in egp_policy_gaussian_filter_f32 (frozen statistics): normalises with `zf_in` as it stands --
+ * ZFilter.__call__(x, update=False) of utils/zfilter.py, what an evaluation does; zf_out receives a copy of zf_in; no row limit.
+ *
+ * Actor and critic of an evaluation tick in one launch (ego_mimic_eval.py:147-161 for all takes of a pass at once): per row r the
+ * observation of (qpos, qvel), the frozen filter (`zf_in` as it stands; y, and y2 when non-NULL, receive the normalised rows,
+ * zf_out a copy of zf_in), then
+ *   [ctx_rows [r*ctx_row_stride  + t_idx[r]*ctx_dim  ...] | state] -> layers  -> Gaussian head -> action[r] (and mean_out[r])
+ *   [vctx_rows[r*vctx_row_stride + t_idx[r]*vctx_dim ...] | state] -> vlayers -> value_out[r]   (float32)
+ * `vlayers` are the value net's MLP and, last, its value_head (out_dim 1; hidden layers with `vactivation`). The launch's grid has a
+ * second dimension that selects the net: the actor's workgroups run the code of egp_policy_gaussian_filter_f32 with zf_workspace ==
+ * NULL (action, mean_out, y, y2 bit-identical to it), the critic's repeat the normalisation for themselves; no workgroup depends on
+ * another. zf_in == NULL (a checkpoint without running_state): no filter -- `y` must already hold the rows' states ([n][obs_dim],
+ * e.g. from egp_obs_f64) and is only read; qpos, qvel, zf_out, y2 are unused. Rows >= n of every output are untouched. No
+ * allocation, no synchronisation, capturable; n == 0 returns EGP_OK. */
+int egp_policy_value_filter_f32(egp_ctx *ctx, const float *ctx_rows, int64_t ctx_row_stride, int32_t ctx_dim, const float *vctx_rows,
+                                int64_t vctx_row_stride, int32_t vctx_dim, const int64_t *t_idx, const double *qpos, const double *qvel,
+                                const int32_t *phase_t, int32_t n, const double *zf_in, double *zf_out, double clip, double *y, double *y2,
+                                const egp_mlp_layer *layers, int32_t n_layers, int32_t activation, const float *log_std,
+                                const float *noise, double *action, float *mean_out, const egp_mlp_layer *vlayers, int32_t n_vlayers,
+                                int32_t vactivation, float *value_out, void *stream);
 /* The ego_forecast policy step in one launch: the state goes through ONE STEP of the state LSTM before it joins the video
  * context (VideoForecastNet in test mode, models/video_forecast_net.py:88-93, over the step-mode cell of models/rnn.py:29-36;
  * torch's nn.LSTMCell, gate order i, f, g, o), then the MLP and the Gaussian head exactly as egp_policy_gaussian_f32:
