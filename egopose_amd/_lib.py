@@ -242,6 +242,8 @@ SIGNATURES = {
     "egp_lstm_group_bwd_rows_f32": (C.c_int, [C.POINTER(C.c_void_p), _i32, vp, vp, vp, _i32, _i32, _i32, _i32, _i32, vp, vp, vp, vp, _i32, vp]),
     "egp_set_dynamics_model": (C.c_int, [vp, C.POINTER(DynamicsDesc)]),
     "egp_dynamics_f64": (C.c_int, [vp, vp, vp, _i32, vp, C.c_int64, vp, vp, vp]),
+    "egp_set_pose2d_bodies": (C.c_int, [vp, c_int_p, c_int_p]),
+    "egp_pose2d_f64": (C.c_int, [vp, vp, vp, vp, vp, vp, vp, C.c_int64, vp]),
     "egp_mlp_pack_floats": (C.c_int64, [_i32, _i32]),
     "egp_mlp_pack_f32": (C.c_int, [vp, C.c_int64, _i32, _i32, vp, vp]),
     "egp_policy_gaussian_f32": (C.c_int, [vp, C.c_int64, _i32, vp, vp, _i32, _i32, C.POINTER(MlpLayer), _i32, _i32, vp, vp, vp, vp, vp]),

@@ -124,33 +124,18 @@ __device__ __forceinline__ void st_m3(double *p, const M3 &R) {
 __device__ __forceinline__ V3 ld_v3(const double *p) { return {p[0], p[1], p[2]}; }
 __device__ __forceinline__ void st_v3(double *p, V3 v) { p[0] = v.x; p[1] = v.y; p[2] = v.z; }
 
-// No level-by-level sweep: every lane walks its own (short) ancestor chain, so the tree costs four wave-local
-// synchronisations instead of two per depth level, and no lane waits for lanes of other levels.
-//   A  lane = body : chain of the body's own hinges in the PARENT frame -> local transform (Rl, tl) and the hinges' local
-//                    axis / anchor (parent-frame coordinates)
-//   B  lane = body : world frame = root frame o local transforms along the ancestor path (walked upwards)
-//   C  lane = dof  : joint motion vector S_d in world coordinates, and S_d * qvel_d
-//   D  lane = body : spatial velocity and bias acceleration from the dof chain (walked upwards with suffix sums), own
-//                    spatial inertia, body force
-//   E  lane = body : composite inertia / subtree force = sum over the body's contiguous (depth-first) subtree range
-//   F  lane = dof  : column of M up the ancestor chain, bias entry
-// `tb`: the tree tables (LDS copy); `base`: DY_ENV_DOUBLES doubles of wave-private LDS; q / qd: the env's qpos / qvel (any
-// memory the wave can read); outputs may be NULL: qM_out = the env's sparse inertia row (MuJoCo order), bias_out [nv],
-// xpos_out [nb][3]. `valid` = false makes the wave compute on its inputs and write nothing.
-__device__ __forceinline__ void dynamics_wave(const DynTables &tb, double *base, const double *q, const double *qd, int lane, bool valid,
-                                              double *qM_out, double *bias_out, double *xpos_out) {
-    const int nb = tb.nb, nv = tb.nv, nj = tb.nj;
-    double *sLoc = base;                                 // [nb][12]  local transform in the parent frame: Rl (9), tl (3)       (A, B)
-    double *sJl = sLoc + nb * DY_LW;                        // [nj][6]   hinge axis (3) and anchor (3) in the parent frame of its body (A, C)
-    double *sIb = base;                                  // [nb][10]  own spatial inertia about the world origin        (D, F: over sLoc / sJl)
-    double *sF = sIb + nb * DY_LI;                          // [nb][6]   body force                                        (D, F)
-    const int r1 = dy_env_doubles(nb, nj, nv) - (nb * DY_LW + nv * DY_LS + nv);
-    double *sW = base + r1;                              // [nb][12]  world frame: R (9), p (3)
-    double *sS = sW + nb * DY_LW;                           // [nv][6]   joint motion vectors (world)
-    double *sQ = sS + nv * DY_LS;                            // [nv]      qvel
+// Per-frame LDS of the forward-kinematics phases alone (A0, A, B): local transforms, hinge axes / anchors, world frames and the
+// hinges' (sin, 1 - cos) pairs. K8 carves the same arrays out of its larger per-env block.
+__host__ __device__ inline int dy_fk_doubles(int nb, int nj) { return nb * DY_LW + nj * DY_LJ + nb * DY_LW + 2 * nj; }
+
+// Phases A0, A and B of the pass described below: the world frame of every body (sW: R (9), p (3) per body, rows of DY_LW doubles)
+// from the pose `q`, without the inertia / bias phases. sLoc [nb][DY_LW], sJl [nj][DY_LJ] and sW [nb][DY_LW] are wave-private LDS;
+// `sSC` holds 2 * nj doubles (sin, 1 - cos of every hinge angle). Ends on a wave_sync: every lane may read sW afterwards.
+__device__ __forceinline__ void fk_wave(const DynTables &tb, double *sLoc, double *sJl, double *sW, double *sSC, const double *q, int lane,
+                                        bool valid, double *xpos_out) {
+    const int nb = tb.nb, nj = tb.nj;
     const int b = lane;
-    DY_TR(0);
-    if (lane < nv) sQ[lane] = qd[lane];
+    double *sS = sSC;
     // ---- A0: lane = hinge: sin and 1 - cos of every hinge angle at once (a body's up to three hinges used to take their
     //          double-precision sincos one after the other); parked in sS, which phase C fills later
     if (lane < nj) {
@@ -211,6 +196,36 @@ __device__ __forceinline__ void dynamics_wave(const DynTables &tb, double *base,
     }
     wave_sync();
     DY_TR(2);
+}
+
+// No level-by-level sweep: every lane walks its own (short) ancestor chain, so the tree costs four wave-local
+// synchronisations instead of two per depth level, and no lane waits for lanes of other levels.
+//   A  lane = body : chain of the body's own hinges in the PARENT frame -> local transform (Rl, tl) and the hinges' local
+//                    axis / anchor (parent-frame coordinates)
+//   B  lane = body : world frame = root frame o local transforms along the ancestor path (walked upwards)
+//   C  lane = dof  : joint motion vector S_d in world coordinates, and S_d * qvel_d
+//   D  lane = body : spatial velocity and bias acceleration from the dof chain (walked upwards with suffix sums), own
+//                    spatial inertia, body force
+//   E  lane = body : composite inertia / subtree force = sum over the body's contiguous (depth-first) subtree range
+//   F  lane = dof  : column of M up the ancestor chain, bias entry
+// `tb`: the tree tables (LDS copy); `base`: DY_ENV_DOUBLES doubles of wave-private LDS; q / qd: the env's qpos / qvel (any
+// memory the wave can read); outputs may be NULL: qM_out = the env's sparse inertia row (MuJoCo order), bias_out [nv],
+// xpos_out [nb][3]. `valid` = false makes the wave compute on its inputs and write nothing.
+__device__ __forceinline__ void dynamics_wave(const DynTables &tb, double *base, const double *q, const double *qd, int lane, bool valid,
+                                              double *qM_out, double *bias_out, double *xpos_out) {
+    const int nb = tb.nb, nv = tb.nv, nj = tb.nj;
+    double *sLoc = base;                                 // [nb][12]  local transform in the parent frame: Rl (9), tl (3)       (A, B)
+    double *sJl = sLoc + nb * DY_LW;                        // [nj][6]   hinge axis (3) and anchor (3) in the parent frame of its body (A, C)
+    double *sIb = base;                                  // [nb][10]  own spatial inertia about the world origin        (D, F: over sLoc / sJl)
+    double *sF = sIb + nb * DY_LI;                          // [nb][6]   body force                                        (D, F)
+    const int r1 = dy_env_doubles(nb, nj, nv) - (nb * DY_LW + nv * DY_LS + nv);
+    double *sW = base + r1;                              // [nb][12]  world frame: R (9), p (3)
+    double *sS = sW + nb * DY_LW;                           // [nv][6]   joint motion vectors (world)
+    double *sQ = sS + nv * DY_LS;                            // [nv]      qvel
+    const int b = lane;
+    DY_TR(0);
+    if (lane < nv) sQ[lane] = qd[lane];
+    fk_wave(tb, sLoc, sJl, sW, sS, q, lane, valid, xpos_out);
     // ---- C: joint motion vectors
     if (lane < nv) {
         const int d = lane;

@@ -73,6 +73,8 @@ struct egp_ctx {
     bool pd_grid = false;              // variant 0, one substep per launch: the lane-grid kernel (variant 3: the row kernel)
     const unsigned short *pd_grid_off = nullptr;   // its [register][lane] gather table (device)
     void *dyn_tables = nullptr;        // device copy of the dynamics tree (egp_set_dynamics_model), owned through allocs
+    int pose2d_body[EGP_POSE2D_NKP] = {}, pose2d_role[6] = {};   // egp_set_pose2d_bodies: body of every keypoint row, rows with a role
+    bool pose2d_set = false;
 };
 
 // launches used by the engine (same TU as the kernels)

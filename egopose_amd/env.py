@@ -241,6 +241,11 @@ class HumanoidEnv:
         sim = self._one()
         if self.fix_start_state is not None:
             qpos, qvel = self.fix_start_state[:self.skel.nq], self.fix_start_state[self.skel.nq:]
+        elif self.expert_list is None:
+            # no experts (feature-only takes), humanoid_v1.py:227-230 after sim.reset(): the model's rest pose one metre up, at rest
+            qpos, qvel = self.rest_qpos(), np.zeros(self.skel.nv)
+            qpos[2] += 1.0
+            self.cur_t = 0
         else:
             e_ind, s_ind = self.sample_reset(1)
             self.set_expert(int(e_ind[0]))
@@ -261,6 +266,13 @@ class HumanoidEnv:
         self.prev_qpos = None
         self.bquat = self.get_body_quat()
         return self.get_obs()
+
+    def rest_qpos(self):
+        """The compiled model's initial qpos (what sim.reset() restores): the root at its MJCF position, unit quaternion, hinges at 0."""
+        qpos = np.zeros(self.skel.nq)
+        qpos[:3] = self.skel.body_pos[0]
+        qpos[3] = 1.0
+        return qpos
 
     def set_state(self, qpos, qvel):
         """MujocoEnv.set_state (envs/common/mujoco_env.py:95-101): overwrite the single env's state + forward."""

@@ -21,6 +21,8 @@ above (a take's result does not depend on the slot count). 'valuefs' compares ag
 order; `egopose_amd.failsafe` makes that exact for takes that run side by side (speculative runs, checked against the true
 statistic afterwards, re-run where a decision differs). The reward (which nothing reads) is not evaluated; `causal` and
 `show_noise` stay with `Evaluator`.
+
+Takes that have video features only (no MoCap, no expert): `egopose_amd.evaluate_wild` (`--test-feat NAME`), on the same pass.
 """
 from __future__ import annotations
 
@@ -184,7 +186,7 @@ class BatchedEvaluator:
         self.running_state = running_state
         self.fail_safe, self.causal, self.show_noise, self.sync = fail_safe, False, False, sync
         self.num_envs, self.device_index, self.n_threads = int(num_envs), int(device_index), n_threads
-        self._fs = SpeculativeValueFailSafe()
+        self._fs = SpeculativeValueFailSafe(decide_on_end=self.DECIDE_ON_END)
         self.logger = logger
         self.trace = {} if keep_trace else None
         self.timing = {}
@@ -195,23 +197,39 @@ class BatchedEvaluator:
 
     value_stat = property(lambda self: self._fs.stat)      # the running statistic of every accepted value, across run() calls
 
+    # What a subclass over another kind of take changes (evaluate_wild.BatchedWildEvaluator): whether the tick that ends a take still
+    # takes the fail-safe decision (it never re-seats), the takes' names, a take's tables, the pose its first seat is aligned to, and
+    # how the records become results.
+    DECIDE_ON_END = False
+
+    def _take_names(self):
+        return self.env.expert_list
+
+    def _seat_ref(self, i):
+        return self.env.expert_arr[i]["qpos"][self.cfg.fr_margin]
+
     # ------------------------------------------------------------------ per take, once: contexts and regressor states (batch 1)
     @torch.no_grad()
-    def _take_tables(self, i):
-        env, m = self.env, self.cfg.fr_margin
+    def _feature_tables(self, cnn_feat_np):
+        """Contexts of both video nets and the de-normalised regressor states of one take's features (batch 1)."""
+        m = self.cfg.fr_margin
         p = next(self.policy_net.parameters())
-        cnn_feat = torch.as_tensor(env.cnn_feat[i], dtype=p.dtype, device=p.device)
-        test_len = cnn_feat.shape[0] - 2 * m
-        ex = env.expert_arr[i]
-        if test_len < 1 or ex["qpos"].shape[0] < m + test_len:
-            raise ValueError("take %s: no frames between the margins, or fewer expert frames than features" % env.expert_list[i])
+        cnn_feat = torch.as_tensor(cnn_feat_np, dtype=p.dtype, device=p.device)
         self.policy_vs_net.initialize(cnn_feat)
         self.value_vs_net.initialize(cnn_feat)
         sp = next(self.state_net.parameters())
         state_pred = self.state_net(cnn_feat.to(device=sp.device, dtype=sp.dtype).unsqueeze(1))[m:-m].double().cpu().numpy()
         state_pred = state_pred * self.state_net_std[None, :] + self.state_net_mean[None, :]
-        return dict(len=test_len, pol=self.policy_vs_net.v_out.float().contiguous(), val=self.value_vs_net.v_out.float().contiguous(),
-                    state_pred=state_pred, orig=np.array(ex["qpos"][m:m + test_len], float))
+        return dict(len=cnn_feat.shape[0] - 2 * m, pol=self.policy_vs_net.v_out.float().contiguous(),
+                    val=self.value_vs_net.v_out.float().contiguous(), state_pred=state_pred)
+
+    def _take_tables(self, i):
+        env, m = self.env, self.cfg.fr_margin
+        test_len = env.cnn_feat[i].shape[0] - 2 * m
+        ex = env.expert_arr[i]
+        if test_len < 1 or ex["qpos"].shape[0] < m + test_len:
+            raise ValueError("take %s: no frames between the margins, or fewer expert frames than features" % env.expert_list[i])
+        return dict(self._feature_tables(env.cnn_feat[i]), orig=np.array(ex["qpos"][m:m + test_len], float))
 
     # ------------------------------------------------------------------ ego_mimic_eval.py:93-100 for a set of slots
     @staticmethod
@@ -247,7 +265,7 @@ class BatchedEvaluator:
             for j, tb in enumerate(tabs):
                 R["pol_slab"][j, :tb["len"]] = tb["pol"]
                 R["val_slab"][j, :tb["len"]] = tb["val"]
-            ref0 = np.stack([env.expert_arr[i]["qpos"][self.cfg.fr_margin] for i in chunk])
+            ref0 = np.stack([self._seat_ref(i) for i in chunk])
             q0, v0 = self._seat_rows(np.stack([tb["state_pred"][0] for tb in tabs]), ref0)
             ids = np.arange(k)
             if not R["seated"] and k < N:         # slots no take ever lands on: a valid state all the same (they are never stepped)
@@ -282,7 +300,8 @@ class BatchedEvaluator:
                     value = float(v_host[t, j])
                     if stats[j] is not None:
                         stats[j].push(np.array([value]))
-                    if t + 1 >= lens[j]:                       # info['end']: no decision, the take is over
+                    last = t + 1 >= lens[j]
+                    if last and not self.DECIDE_ON_END:        # info['end']: no decision, the take is over
                         active[j] = 0
                         continue
                     if self.fail_safe == "valuefs":
@@ -292,8 +311,11 @@ class BatchedEvaluator:
                     else:
                         hit = False
                     if hit:
-                        flagged.append(j)
+                        if not last:                           # (a decision on the take's last tick has no next frame to re-seat on)
+                            flagged.append(j)
                         resets[j].append(t)
+                    if last:
+                        active[j] = 0
                 if flagged:
                     fl = np.array(flagged)
                     q1, v1 = self._seat_rows(np.stack([tabs[j]["state_pred"][t + 1] for j in flagged]), np.array(eng.qpos_host[fl], float))
@@ -318,7 +340,7 @@ class BatchedEvaluator:
         from . import policy_step
         env, N = self.env, self.num_envs
         t_all = time.time()
-        sel = [i for i, take in enumerate(env.expert_list) if takes is None or take in takes]
+        sel = [i for i, take in enumerate(self._take_names()) if takes is None or take in takes]
         self.timing = tm = {"phys_wait": 0.0, "passes": 0, "takes": len(sel), "ticks": 0, "fs_passes": 0, "fs_pass_takes": []}
         self._latest = {}
         if sel:
@@ -347,10 +369,20 @@ class BatchedEvaluator:
                     self._run_pass(sel, [None] * len(sel))
                     tm["fs_passes"], tm["fs_pass_takes"] = 1, [len(sel)]
             self._run = None
+        out = self._results(sel, tables if sel else {})
+        self._latest = None
+        tm["total"] = time.time() - t_all
+        tm["rest"] = tm["total"] - tm["phys_wait"]
+        return out
+
+    def _results(self, sel, tables):
         traj_pred, traj_orig, vel_pred, num_reset = {}, {}, {}, 0
+        names = self._take_names()
         for i in sel:
-            take, rec = env.expert_list[i], self._latest[i]
-            traj_pred[take], traj_orig[take], vel_pred[take] = rec["traj_pred"], tables[i]["orig"], rec["vel_pred"]
+            take, rec = names[i], self._latest[i]
+            traj_pred[take], vel_pred[take] = rec["traj_pred"], rec["vel_pred"]
+            if "orig" in tables[i]:
+                traj_orig[take] = tables[i]["orig"]
             num_reset += len(rec["resets"])
             if self.logger is not None:
                 for _ in rec["resets"]:
@@ -358,9 +390,6 @@ class BatchedEvaluator:
             if self.trace is not None:
                 self.trace[take] = dict(actions=rec["actions"], values=rec["values"], resets=rec["resets"], state_pred=tables[i]["state_pred"],
                                         states=rec["states"])
-        self._latest = None
-        tm["total"] = time.time() - t_all
-        tm["rest"] = tm["total"] - tm["phys_wait"]
         return {"traj_pred": traj_pred, "traj_orig": traj_orig, "vel_pred": vel_pred}, {"algo": "ego_mimic", "num_reset": num_reset}
 
     save = Evaluator.save
@@ -401,13 +430,26 @@ def main(argv=None):
     ap.add_argument("--gpu-index", type=int, default=0)
     ap.add_argument("--num-envs", type=int, default=1, help="> 1: takes side by side on that many env slots (BatchedEvaluator)")
     ap.add_argument("--sequential", action="store_true", help="take by take (Evaluator) whatever --num-envs says")
+    ap.add_argument("--test-feat", default=None, help="evaluate the feature-only takes of datasets/features/cnn_feat_<NAME>.p (no MoCap)")
+    ap.add_argument("--mode", default="eval", choices=["eval", "wild-stats"], help="wild-stats: 2D keypoint statistics of saved --test-feat results")
+    ap.add_argument("--statereg-cfg", default=None, help="wild-stats: also score the state regressor's results of this config")
+    ap.add_argument("--statereg-iter", type=int, default=100)
+    ap.add_argument("--host", action="store_true", help="wild-stats: the per-frame numpy loop instead of the GPU kernel")
     args = ap.parse_args(argv)
     cfg = Config(args.cfg, create_dirs=False)
+    if args.mode == "wild-stats":
+        return _wild_stats(cfg, args)
     dev, dtype = torch.device("cuda", args.gpu_index), torch.float32
     env = HumanoidEnv(cfg)
     env.seed(cfg.seed)
-    env.load_experts(cfg.takes[args.data], cfg.expert_feat_file, cfg.cnn_feat_file)
-    cnn_dim = env.cnn_feat[0].shape[-1]
+    cnn_feat_dict = None
+    if args.test_feat is not None:                 # ego_mimic_eval_wild.py:36-39: no experts
+        from .evaluate_wild import BatchedWildEvaluator, WildEvaluator, load_features
+        cnn_feat_dict = load_features(cfg, args.test_feat)
+        cnn_dim = next(iter(cnn_feat_dict.values())).shape[-1]
+    else:
+        env.load_experts(cfg.takes[args.data], cfg.expert_feat_file, cfg.cnn_feat_file)
+        cnn_dim = env.cnn_feat[0].shape[-1]
     sd, ad = env.observation_space.shape[0], env.action_space.shape[0]
     mk = lambda hdim, kind, param: VideoStateNet(cnn_dim, hdim, cfg.fr_margin, kind, param, cfg.causal)
     policy_vs, value_vs = mk(cfg.policy_v_hdim, cfg.policy_v_net, cfg.policy_v_net_param), mk(cfg.value_v_hdim, cfg.value_v_net, cfg.value_v_net_param)
@@ -428,6 +470,18 @@ def main(argv=None):
     cls, why = select_evaluator(policy, value, args.num_envs, args.sequential, args.causal, args.show_noise)
     if why is not None:
         print("falling back to the sequential Evaluator: %s" % why)
+    if cnn_feat_dict is not None:
+        nets = (policy, policy_vs, value, value_vs, state_net, meta["mean"], meta["std"])
+        if cls is BatchedEvaluator:
+            ev = BatchedWildEvaluator(cfg, env, cnn_feat_dict, *nets, running_state=cp["running_state"], num_envs=args.num_envs,
+                                      device_index=args.gpu_index)
+        else:
+            ev = WildEvaluator(cfg, env, cnn_feat_dict, *nets, running_state=cp["running_state"], show_noise=args.show_noise)
+        results, rmeta = ev.run()
+        path = ev.save(results, rmeta, args.iter, args.test_feat)
+        print("num reset: %d, saved results to %s" % (ev.num_reset, path))
+        env.close()
+        return
     if cls is BatchedEvaluator:
         if args.fail_safe == "naivefs":
             env.set_fix_head_lb(0.3)                   # ego_mimic_eval.py:51-52 (the sequential path keeps the take's own bound)
@@ -441,6 +495,28 @@ def main(argv=None):
     print("num reset: %d, saved results to %s" % (rmeta["num_reset"], path))
     compute_metrics(results, verbose=True)
     env.close()
+
+
+def _wild_stats(cfg, args):
+    """eval_pose_wild.py --mode stats: the 2D keypoint distance and the smoothness of the saved wild results."""
+    import yaml
+    from . import pose2d
+    from .statereg import StateRegConfig
+    with open("%s/meta/meta_%s.yml" % (cfg.data_dir, args.test_feat)) as f:
+        meta = yaml.safe_load(f)
+    pose_ctx = pose2d.Pose2DContext()
+    loader = pose2d.file_keypoint_loader(cfg.data_dir, pose_ctx)
+    jobs = [("ego mimic", "%s/iter_%04d_%s.p" % (cfg.result_dir, args.iter, args.test_feat))]
+    if args.statereg_cfg is not None:
+        sr_cfg = StateRegConfig(args.statereg_cfg, create_dirs=False)
+        jobs.append(("state reg", "%s/iter_%04d_%s.p" % (sr_cfg.result_dir, args.statereg_iter, args.test_feat)))
+    out = {}
+    for algo, path in jobs:
+        with open(path, "rb") as f:
+            res, _ = pickle.load(f)
+        out[algo] = pose2d.eval_pose_wild_stats(res, meta, loader, cfg, backend="host" if args.host else "hip", pose_ctx=pose_ctx,
+                                                algo=algo, verbose=True, device_index=args.gpu_index)
+    return out
 
 
 if __name__ == "__main__":

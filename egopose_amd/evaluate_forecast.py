@@ -12,8 +12,13 @@ with the bracket one launch (`FusedForecastPolicy.with_filter(..., workspace=Non
 
 A window starts from the expert's state (`gt_init`) or from the ego_mimic result of the same take (ego_forecast_eval.py:107-120,
 `window_init_state`). The value nets are NOT evaluated: the reference only logs their output, which does not enter the results.
-Rendering (`--render`, `--mode vis`, `--show-noise`), the per-step reward log (`--verbose`) and the `*_wild` scripts are out of
-scope.
+Rendering (`--render`, `--mode vis`, `--show-noise`) and the per-step reward log (`--verbose`) are out of scope.
+
+Feature-only takes (ego_forecast_eval_wild.py): the window plan and the seat / history rows are here (`wild_window_plan`,
+`wild_window_init_state`), `ForecastEvaluator(..., cnn_feat_dict=...)` runs them -- the feature table comes from the pickle, seat and
+history from the wild ego_mimic result, there is no expert, no `sync_traj`, no `traj_orig` and no per-take head bound (`failed` is
+only logged against the env's `fix_head_lb`, if set) -- and `--mode wild-stats` scores the saved results with the 2D keypoint
+metric (`egopose_amd.pose2d`). `--test-feat NAME` selects this path.
 """
 from __future__ import annotations
 
@@ -68,6 +73,37 @@ def window_init_state(expert_qpos, expert_qvel, start, fr_margin, test_len, em_t
     return qpos, qvel, history, miss_len
 
 
+# ---------------------------------------------------------------------- ego_forecast_eval_wild.py:160-170
+def wild_window_plan(take_lens, fr_margin, em_margin, test_len):
+    """(take_ind[W], start_ind[W]) of the windows of feature-only takes: per take start = m + em_m, m + em_m + m, ... while
+    start + test_len <= take_len (take_len = rows of the take's feature array, em_m = the ego_mimic config's fr_margin)."""
+    m, em_m, test_len = int(fr_margin), int(em_margin), int(test_len)
+    take_ind, start_ind = [], []
+    for i, take_len in enumerate(take_lens):
+        start = m + em_m
+        while start + test_len <= int(take_len):
+            take_ind.append(i)
+            start_ind.append(start)
+            start += m
+    return np.asarray(take_ind, dtype=np.int64), np.asarray(start_ind, dtype=np.int64)
+
+
+# ---------------------------------------------------------------------- ego_forecast_eval_wild.py:102-120
+def wild_window_init_state(em_traj, em_vel, start, fr_margin, em_margin, test_len):
+    """Seat state and history rows of the window starting at feature row `start` of a feature-only take, from the take's wild
+    ego_mimic result (its row i is feature row i + em_m) -> (qpos, qvel, history[m, nq]): the slice
+    [start - m - em_m, start + test_len - em_m) of it, seat = its row m, history = its rows 0..m-1. No expert, no sync_traj. (The result has take_len - 2 em_m rows, so the slice of a window at
+    the take's end comes up short, as the reference's does; only its first m + 1 rows are read.)"""
+    m, em_m, start, test_len = int(fr_margin), int(em_margin), int(start), int(test_len)
+    if start < m + em_m:
+        raise ValueError("window start %d before fr_margin + the ego_mimic margin" % start)        # the reference's assert
+    lo, hi = start - m - em_m, start + test_len - em_m
+    state_pred, vel_pred = np.asarray(em_traj, float)[lo:hi], np.asarray(em_vel, float)[lo:hi]
+    if state_pred.shape[0] <= m:      # the mimic result ends em_m rows before the features do: a window at the take's end needs test_len > em_m
+        raise ValueError("window at %d: the ego_mimic result has no row for its start (%d rows from %d)" % (start, state_pred.shape[0], lo))
+    return state_pred[m].copy(), vel_pred[m].copy(), state_pred[:m].copy()
+
+
 def result_path(cfg, it, data="test", gt_init=False):
     return "%s/iter_%04d_%s%s.p" % (cfg.result_dir, it, data, "_gt" if gt_init else "")
 
@@ -77,12 +113,16 @@ class ForecastEvaluator:
     'traj_orig': ...}, meta = {'algo': 'ego_forecast'}. `em_res` (+ `em_off`): the ego_mimic results the windows start from
     unless `gt_init`. `keep_trace`: `self.trace` keeps per window the actions, the filtered states the policy saw, the qvel that
     goes with each recorded qpos, and the plan (take_ind, start_ind). `self.timing`: wall seconds of the last run, split into
-    the wait for the host physics and the rest."""
+    the wait for the host physics and the rest.
+    `cnn_feat_dict` = {take: features} (ego_forecast_eval_wild.py): feature-only takes on an env without experts; `em_res` is then the
+    wild ego_mimic result, and results = {'traj_pred': {take: [n_win, m + test_len, nq]}} alone."""
 
     CTX_BATCH = 1024         # windows per launch of the video net
 
     def __init__(self, cfg, env, policy_net, policy_vs_net, running_state=None, gt_init=False, em_res=None, em_off=0, num_envs=1024,
-                 device_index=0, n_threads=None, keep_trace=False, logger=None):
+                 device_index=0, n_threads=None, keep_trace=False, logger=None, cnn_feat_dict=None):
+        if cnn_feat_dict is not None and (gt_init or env.expert_list is not None):
+            raise ValueError("feature-only takes have no expert: no gt_init, and an env without experts")
         if not gt_init and em_res is None:
             raise ValueError("ego_mimic results (em_res) are needed unless gt_init")
         if running_state is not None and not (running_state.demean and running_state.destd):
@@ -94,6 +134,9 @@ class ForecastEvaluator:
         self.num_envs, self.device_index, self.n_threads = int(num_envs), int(device_index), n_threads
         self.keep_trace, self.logger = bool(keep_trace), logger
         self.trace, self.timing = None, {}
+        self.wild = cnn_feat_dict is not None
+        self.take_names = list(cnn_feat_dict.keys()) if self.wild else None
+        self.cnn_feat = [np.asarray(cnn_feat_dict[take]) for take in self.take_names] if self.wild else None
         for net in (policy_net, policy_vs_net):
             net.eval()
         policy_vs_net.set_mode("test")
@@ -102,6 +145,8 @@ class ForecastEvaluator:
     def plan(self, takes=None):
         cfg, env = self.cfg, self.env
         m, T = int(cfg.fr_margin), int(cfg.env_episode_len)
+        if self.wild:
+            return self._wild_plan(takes, m, T)
         take_ind, start_ind = window_plan([c.shape[0] if takes is None or env.expert_list[i] in takes else 0 for i, c in enumerate(env.cnn_feat)], m, T)
         W = len(take_ind)
         nq, nv = env.skel.nq, env.skel.nv
@@ -119,6 +164,17 @@ class ForecastEvaluator:
             qpos0[w], qvel0[w], hist[w], miss[w] = window_init_state(ex["qpos"], ex["qvel"], s, m, T, em_t, em_v, self.em_off)
         return take_ind, start_ind, qpos0, qvel0, hist, miss
 
+    def _wild_plan(self, takes, m, T):
+        names, nq, nv = self.take_names, self.env.skel.nq, self.env.skel.nv
+        take_ind, start_ind = wild_window_plan([c.shape[0] if takes is None or names[i] in takes else 0 for i, c in enumerate(self.cnn_feat)],
+                                               m, self.em_off, T)
+        W = len(take_ind)
+        qpos0, qvel0, hist = np.empty((W, nq)), np.empty((W, nv)), np.empty((W, m, nq))
+        for w, (e, s) in enumerate(zip(take_ind, start_ind)):
+            em_t, em_v = self.em_res["traj_pred"][names[e]], self.em_res["vel_pred"][names[e]]
+            qpos0[w], qvel0[w], hist[w] = wild_window_init_state(em_t, em_v, s, m, self.em_off, T)
+        return take_ind, start_ind, qpos0, qvel0, hist, np.zeros(W, np.int64)
+
     # ------------------------------------------------------------------ ego_forecast_eval.py:95-204, batched
     def run(self, takes=None):
         """Evaluate every window of every take of the env's expert list (or of `takes`) -> (results, meta)."""
@@ -132,6 +188,10 @@ class ForecastEvaluator:
         N = self.num_envs
         sim = env.batched(N, self.device_index, self.n_threads, 1)
         ctx, eng, ex = sim.ctx, sim.engine, sim.experts
+        if self.wild:
+            from .expert import ExpertSet
+            ex = ExpertSet.features_only(self.cnn_feat)
+        names = self.take_names if self.wild else env.expert_list
         dev = torch.device("cuda", ctx.device)
         vs = self.policy_vs_net
         if not policy_step.supported_forecast(self.policy_net, vs):
@@ -140,9 +200,10 @@ class ForecastEvaluator:
         nq, nv, nu, od = ctx.nq, ctx.nv, ctx.nu, ctx.obs_dim
         f64 = torch.float64
         pred = np.empty((W, m + T, nq))
-        orig = np.empty((W, m + T, nq))
+        orig = None if self.wild else np.empty((W, m + T, nq))
         for w, (e, s) in enumerate(zip(take_ind, start_ind)):
-            orig[w] = env.expert_arr[e]["qpos"][s - m:s + T]
+            if orig is not None:
+                orig[w] = env.expert_arr[e]["qpos"][s - m:s + T]
         pred[:, :m] = hist
         failed = np.zeros(W, bool)
         tr_act, tr_st, tr_qv = (np.empty((W, T, nu)), np.empty((W, T, od)), np.empty((W, T, nv))) if self.keep_trace else (None, None, None)
@@ -163,7 +224,8 @@ class ForecastEvaluator:
             c = torch.zeros_like(h)
             t_idx = torch.zeros(N, dtype=torch.int64, device=dev)
             phase = torch.arange(T, dtype=torch.int32, device=dev).unsqueeze(1).expand(T, N).contiguous() if ctx.obs_phase else None
-            lb = ex.head_height_lb
+            lb = ex.head_height_lb            # (feature-only takes: None)
+            fix_lb = getattr(env, "fix_head_lb", None) if self.wild else None
             # the windows' video contexts, as LockstepRollout._draw_episodes computes them for forecast episodes: in batches whose
             # size does not follow the slot count (the LSTM kernels' tiling follows the batch size, and a window's forecast must
             # not depend on how many slots it was evaluated with)
@@ -197,7 +259,10 @@ class ForecastEvaluator:
                     t0 = time.time()
                     eng.wait(0)
                     tm["phys_wait"] += time.time() - t0
-                    failed[sl] |= np.asarray(eng.head_z[:k]) < lb[take_ind[sl]] - 0.1          # (logged only: the window runs on)
+                    if lb is not None:
+                        failed[sl] |= np.asarray(eng.head_z[:k]) < lb[take_ind[sl]] - 0.1      # (logged only: the window runs on)
+                    elif fix_lb is not None:
+                        failed[sl] |= np.asarray(eng.head_z[:k]) < fix_lb
                 torch.cuda.synchronize(dev)
                 pred[sl, m:] = traj[:, :k].transpose(0, 1).cpu().numpy()
                 if self.keep_trace:
@@ -210,10 +275,12 @@ class ForecastEvaluator:
             for w in np.nonzero(failed)[0]:
                 self.logger.info("fail - expert_ind: %d, start_ind %d" % (take_ind[w], start_ind[w]))
         traj_pred, traj_orig = {}, {}
-        for i, take in enumerate(env.expert_list):
+        for i, take in enumerate(names):
             sel = take_ind == i
             if sel.any():                          # (a take too short for one window has no entry)
-                traj_pred[take], traj_orig[take] = pred[sel], orig[sel]
+                traj_pred[take] = pred[sel]
+                if orig is not None:
+                    traj_orig[take] = orig[sel]
         self.failed = failed
         self.miss_len = miss
         if self.keep_trace:
@@ -221,6 +288,8 @@ class ForecastEvaluator:
         tm["total"] = time.time() - t_all
         tm["rest"] = tm["total"] - tm["phys_wait"]
         self.timing = tm
+        if self.wild:
+            return {"traj_pred": traj_pred}, {"algo": "ego_forecast"}
         return {"traj_pred": traj_pred, "traj_orig": traj_orig}, {"algo": "ego_forecast"}
 
     def save(self, results, meta, it, data="test"):
@@ -240,7 +309,24 @@ def build_parser():
     ap.add_argument("--gt-init", action="store_true")
     ap.add_argument("--num-envs", type=int, default=1024)
     ap.add_argument("--gpu-index", type=int, default=0)
+    ap.add_argument("--mode", default="eval", choices=["eval", "wild-stats"], help="wild-stats: 2D keypoint statistics of saved --test-feat results")
+    ap.add_argument("--test-feat", default=None, help="forecast on the feature-only takes of features/cnn_feat_<NAME>.p, from the wild ego_mimic result iter_<N>_<NAME>.p")
+    ap.add_argument("--horizon", type=int, default=30)
+    ap.add_argument("--host", action="store_true", help="wild-stats: the per-frame numpy loop instead of the GPU kernel")
     return ap
+
+
+def _wild_stats(cfg, args):
+    """eval_forecast_wild.py --mode stats on the saved forecast results of feature-only takes."""
+    import yaml
+    from . import pose2d
+    with open("%s/meta/meta_%s.yml" % (cfg.data_dir, args.test_feat)) as f:
+        meta = yaml.safe_load(f)
+    pose_ctx = pose2d.Pose2DContext()
+    with open("%s/iter_%04d_%s.p" % (cfg.result_dir, args.iter, args.test_feat), "rb") as f:
+        res, _ = pickle.load(f)
+    return pose2d.eval_forecast_wild_stats(res, meta, pose2d.file_keypoint_loader(cfg.data_dir, pose_ctx), cfg, horizon=args.horizon,
+                                           backend="host" if args.host else "hip", pose_ctx=pose_ctx, verbose=True, device_index=args.gpu_index)
 
 
 def main(argv=None):
@@ -254,13 +340,23 @@ def main(argv=None):
     from .zfilter import load_reference_pickle
     args = build_parser().parse_args(argv)
     cfg = ForecastConfig(args.cfg, create_dirs=False)
+    if args.mode == "wild-stats":
+        return _wild_stats(cfg, args)
+    if args.gt_init and args.test_feat is not None:
+        raise SystemExit("--gt-init needs MoCap: not with --test-feat")
     cfg.random_cur_t = False
     cfg.env_init_noise = 0.0
     dev = torch.device("cuda", args.gpu_index)
     env = HumanoidEnv(cfg)
     env.seed(cfg.seed)
-    env.load_experts(cfg.takes[args.data], cfg.expert_feat_file, cfg.cnn_feat_file)
-    cnn_dim = env.cnn_feat[0].shape[-1]
+    cnn_feat_dict, data = None, args.data
+    if args.test_feat is not None:                 # ego_forecast_eval_wild.py:40-43: no experts
+        from .evaluate_wild import load_features
+        cnn_feat_dict, data = load_features(cfg, args.test_feat), args.test_feat
+        cnn_dim = next(iter(cnn_feat_dict.values())).shape[-1]
+    else:
+        env.load_experts(cfg.takes[args.data], cfg.expert_feat_file, cfg.cnn_feat_file)
+        cnn_dim = env.cnn_feat[0].shape[-1]
     sd, ad = env.observation_space.shape[0], env.action_space.shape[0]
     policy_vs = VideoForecastNet(cnn_dim, sd, cfg.policy_v_hdim, cfg.fr_margin, cfg.policy_v_net, cfg.policy_v_net_param, cfg.policy_s_hdim,
                                  cfg.policy_s_net, cfg.policy_dyn_v)
@@ -274,15 +370,18 @@ def main(argv=None):
     em_res, em_off = None, 0
     if not args.gt_init:
         em_cfg = EgoMimicConfig(cfg.ego_mimic_cfg, create_dirs=False)
-        with open("%s/iter_%04d_%s.p" % (em_cfg.result_dir, cfg.ego_mimic_iter, args.data), "rb") as f:
+        with open("%s/iter_%04d_%s.p" % (em_cfg.result_dir, cfg.ego_mimic_iter, data), "rb") as f:
             em_res, _ = pickle.load(f)
         em_off = em_cfg.fr_margin
     ev = ForecastEvaluator(cfg, env, policy, policy_vs, running_state=cp["running_state"], gt_init=args.gt_init, em_res=em_res, em_off=em_off,
-                           num_envs=args.num_envs, device_index=args.gpu_index)
+                           num_envs=args.num_envs, device_index=args.gpu_index, cnn_feat_dict=cnn_feat_dict)
     results, meta = ev.run()
-    path = ev.save(results, meta, args.iter, args.data)
+    path = ev.save(results, meta, args.iter, data)
     print("saved results to %s (%d windows, %.2f s, %.2f s of it waiting for the physics)"
           % (path, ev.timing["windows"], ev.timing["total"], ev.timing["phys_wait"]))
+    if cnn_feat_dict is not None:                  # (no MoCap to compare with: `--mode wild-stats` scores the file)
+        env.close()
+        return
     stats = copy.deepcopy(results)
     metrics.remove_noisy_hands(stats)
     for horizon in (30, 90):

@@ -74,7 +74,22 @@ class ExpertSet:
         self.cnn_offset = np.concatenate([[0], np.cumsum(self.cnn_lens)]).astype(np.int64)
         self._cnn_table = {}
 
+    @classmethod
+    def features_only(cls, cnn_feat):
+        """The feature side alone (takes without MoCap): `cnn_table` / `cnn_offset` as above, no expert rows, no `head_height_lb`."""
+        if not cnn_feat:
+            raise ValueError("need at least one cnn feature array")
+        self = cls.__new__(cls)
+        self.expert_arr, self.cnn_feat = None, list(cnn_feat)
+        self.lens = self.take_offset = self.qpos = self.qvel = self.head_height_lb = None
+        self.cnn_lens = np.array([c.shape[0] for c in self.cnn_feat], np.int64)
+        self.cnn_offset = np.concatenate([[0], np.cumsum(self.cnn_lens)]).astype(np.int64)
+        self._cnn_table = {}
+        return self
+
     def upload(self, ctx):
+        if self.expert_arr is None:
+            raise ValueError("a features-only set has no expert rows to upload")
         ctx.upload_experts(self.expert_arr)
 
     def cnn_table(self, device, dtype):

@@ -43,8 +43,11 @@ class SpeculativeValueFailSafe:
     """`stat`: the true running statistic; it persists across `run()` calls as the evaluator's does.
     After a run: `passes`, `pass_takes` (takes per pass)."""
 
-    def __init__(self, stat=None):
+    def __init__(self, stat=None, decide_on_end=False):
+        """`decide_on_end`: the step that ends a take takes a decision too (the evaluation of feature-only takes, which has no
+        `end` break: ego_mimic_eval_wild.py:113-138)."""
         self.stat = RunningStat(1) if stat is None else stat
+        self.decide_on_end = bool(decide_on_end)
         self.passes, self.pass_takes = 0, []
 
     def run(self, take_ids, run_pass):
@@ -68,7 +71,7 @@ class SpeculativeValueFailSafe:
             first = done
             while done < n:
                 values, taken = latest[done]
-                want, after = decisions(values, len(values) - 1, self.stat)
+                want, after = decisions(values, -1 if self.decide_on_end else len(values) - 1, self.stat)
                 if not np.array_equal(want, taken):
                     break
                 self.stat = after

@@ -318,6 +318,43 @@ class EgpContext:
                                           _ptr(out.get("xpos")), _stream()), "egp_dynamics_f64")
         return out
 
+    # ------------------------------------------------------------------ K9: the 2D keypoint metric of in-the-wild takes
+    def set_pose2d_bodies(self, kp_body, roles):
+        """`kp_body` [12]: body (0 = root) of every keypoint row; `roles` [6]: the rows of LeftUpLeg, RightUpLeg, LeftLeg, RightLeg,
+        LeftArm, RightArm (pose2d.Pose2DContext.kernel_tables)."""
+        kb, ro = _np_i32(kp_body), _np_i32(roles)
+        if kb.shape != (12,) or ro.shape != (6,):
+            raise ValueError("kp_body must have 12 entries and roles 6")
+        L.check(self.lib.egp_set_pose2d_bodies(self.handle, _ip(kb), _ip(ro)), "egp_set_pose2d_bodies")
+        self._pose2d_tables = (tuple(kb.tolist()), tuple(ro.tolist()))
+
+    def pose2d(self, qpos, gt, flip, want_p=True, out=None):
+        """qpos float64 [n][nq], gt float64 [n][12][3] (x, y, confidence per keypoint body), flip int32 [n] -> dict(p [n][12][2]
+        aligned projection (absent with want_p=False), dist [n], valid int32 [n]) in one launch (egp_pose2d_f64). `out`: a dict of
+        preallocated p / dist / valid tensors to write into. `set_pose2d_bodies` must have been called."""
+        if not getattr(self, "_has_dynamics", False):
+            self.set_dynamics_model()
+        if getattr(self, "_pose2d_tables", None) is None:
+            raise RuntimeError("set_pose2d_bodies must be called before pose2d")
+        n = qpos.shape[0]
+        _need(qpos, (n, self.nq), torch.float64, "qpos")
+        _need(gt, (n, 12, 3), torch.float64, "gt")
+        _need(flip, (n,), torch.int32, "flip")
+        out = dict(out or {})
+        if want_p and "p" not in out:
+            out["p"] = torch.empty(n, 12, 2, dtype=torch.float64, device=qpos.device)
+        if "dist" not in out:
+            out["dist"] = torch.empty(n, dtype=torch.float64, device=qpos.device)
+        if "valid" not in out:
+            out["valid"] = torch.empty(n, dtype=torch.int32, device=qpos.device)
+        if "p" in out:
+            _need(out["p"], (n, 12, 2), torch.float64, "p")
+        _need(out["dist"], (n,), torch.float64, "dist")
+        _need(out["valid"], (n,), torch.int32, "valid")
+        L.check(self.lib.egp_pose2d_f64(self.handle, _ptr(qpos), _ptr(gt), _ptr(flip), _ptr(out.get("p")), _ptr(out["dist"]), _ptr(out["valid"]),
+                                        n, _stream()), "egp_pose2d_f64")
+        return out
+
     def pose_features(self, cur_qpos, prev_qpos, ee_wpos, expert_convention=False):
         """-> dict(qvel, rlinv_local, rangv, rq_rmh, ee_pos, bquat, bangvel) device tensors (K7)."""
         n, dt = cur_qpos.shape[0], cur_qpos.dtype

@@ -270,6 +270,21 @@ class StateRegTrainer:
         return {"traj_pred": res_pred, "traj_orig": res_orig}, meta
 
     @torch.no_grad()
+    def test_features(self, cnn_feat_dict):
+        """`--mode test --test-feat` (state_reg.py:162-175): the regressor on stored per-take features (the trainer is built with
+        no_cnn=True), no mocap -> (results, meta); every take is integrated from position (0, 0) and heading (1, 0, 0, 0)."""
+        ds, m, sd = self.dataset, self.cfg.fr_margin, self.state_dim
+        self.net.eval()
+        res_pred, n_sample = {}, 0
+        for take, cnn_feat in cnn_feat_dict.items():
+            x = torch.as_tensor(np.asarray(cnn_feat), dtype=self.dtype, device=self.device)
+            sp = self.net(x.unsqueeze(1)).squeeze(1)[m:-m].double().cpu().numpy()
+            sp = sp * ds.std[None, :sd] + ds.mean[None, :sd]
+            res_pred[take] = get_traj_from_state_pred(sp, np.zeros(2), np.array([1.0, 0.0, 0.0, 0.0]), ds.dt, ds.traj_dim)
+            n_sample += sp.shape[0]
+        return {"traj_pred": res_pred}, {"algo": "state_reg", "num_sample": n_sample}
+
+    @torch.no_grad()
     def cnn_features(self):
         """What ego_pose/data_process/gen_cnn_feature.py stores: per take the (frames, cnn_fdim) encoder output."""
         ds = self.dataset
@@ -309,6 +324,7 @@ def main(argv=None):
     ap.add_argument("--gpu-index", type=int, default=0)
     ap.add_argument("--iter", type=int, default=0)
     ap.add_argument("--bf16", action="store_true", help="autocast the encoder / GEMMs to bfloat16 (fp32 master weights)")
+    ap.add_argument("--test-feat", default=None, help="--mode test on datasets/features/cnn_feat_<NAME>.p (takes without mocap)")
     args = ap.parse_args(argv)
     data = args.data or (args.mode if args.mode in ("train", "test") else "train")
     cfg = StateRegConfig(args.cfg, create_dirs=(args.iter == 0 and args.mode == "train"))
@@ -316,9 +332,10 @@ def main(argv=None):
     torch.manual_seed(cfg.seed)
     ds = Dataset(cfg.meta_id, data, cfg.fr_num, cfg.iter_method, cfg.shuffle, 2 * cfg.fr_margin, cfg.num_sample)
     dev = torch.device("cuda", args.gpu_index) if torch.cuda.is_available() else torch.device("cpu")
-    tr = StateRegTrainer(cfg, ds, dev, no_cnn=args.mode == "save_inf", autocast=torch.bfloat16 if args.bf16 else None)
+    no_cnn = args.mode == "save_inf" or args.test_feat is not None
+    tr = StateRegTrainer(cfg, ds, dev, no_cnn=no_cnn, autocast=torch.bfloat16 if args.bf16 else None)
     if args.iter > 0:
-        meta = tr.load("%s/iter_%04d.p" % (cfg.model_dir, args.iter), strict=args.mode != "save_inf")
+        meta = tr.load("%s/iter_%04d.p" % (cfg.model_dir, args.iter), strict=not no_cnn)
         if data != "train":
             ds.set_mean_std(meta["mean"], meta["std"])
     if args.mode == "train":
@@ -327,6 +344,14 @@ def main(argv=None):
             print("epoch %4d    time %.2f     nsample %d   loss %.4f" % (ep, dt, n, loss))
             if cfg.save_model_interval > 0 and (ep + 1) % cfg.save_model_interval == 0:
                 tr.save("%s/iter_%04d.p" % (cfg.model_dir, ep + 1))
+    elif args.mode == "test" and args.test_feat is not None:
+        with open("%s/features/cnn_feat_%s.p" % (ds.base_folder, args.test_feat), "rb") as f:
+            cnn_feat_dict, _ = pickle.load(f)
+        results, meta = tr.test_features(cnn_feat_dict)
+        path = "%s/iter_%04d_%s.p" % (cfg.result_dir, args.iter, args.test_feat)
+        with open(path, "wb") as f:
+            pickle.dump((results, meta), f)
+        print("nsample %d\nsaved results to %s" % (meta["num_sample"], path))
     elif args.mode == "test":
         results, meta = tr.test()
         path = "%s/iter_%04d_%s.p" % (cfg.result_dir, args.iter, data)

@@ -495,6 +495,20 @@ int egp_set_dynamics_model(egp_ctx *ctx, const egp_dynamics_desc *desc);
 int egp_dynamics_f64(egp_ctx *ctx, const double *qpos, const double *qvel, int32_t n, double *qM, int64_t ld_m,
                      double *qfrc_bias, double *xpos, void *stream);
 
+/* ----------------------------------------------------------------------------------------
+ * K9: the 2D keypoint metric of in-the-wild takes (ego_pose/utils/pose2d.py:75-148: check_gt, project_qpos, align_qpos with
+ * scale=None, get_pose_dist) for n frames in one launch: forward kinematics (the FK phases of K8; egp_set_dynamics_model must
+ * have been called), the side camera along the hip line 10 m back from the hip midpoint (`flip` negates its x axis), perspective
+ * divide with y negated, base / scale alignment to the visible keypoints, and the confidence-masked mean keypoint distance scaled
+ * by 0.5 / |dy(arm, up-leg)|. `gt` rows are (x, y, confidence) of the EGP_POSE2D_NKP keypoint bodies in the row order given to
+ * egp_set_pose2d_bodies: kp_body[k] = body (0 = root) of keypoint row k; roles = the rows of LeftUpLeg, RightUpLeg, LeftLeg,
+ * RightLeg, LeftArm, RightArm. valid = check_gt; an invalid frame has dist = 0 and the unaligned projection in p_out. */
+#define EGP_POSE2D_NKP 12
+int egp_set_pose2d_bodies(egp_ctx *ctx, const int32_t *kp_body /*[12]*/, const int32_t *roles /*[6]*/);
+int egp_pose2d_f64(egp_ctx *ctx, const double *qpos /*[n][nq]*/, const double *gt /*[n][12][3]: x, y, confidence, body order*/,
+                   const int32_t *flip /*[n]*/, double *p_out /*[n][12][2], may be NULL*/, double *dist /*[n]*/,
+                   int32_t *valid /*[n]*/, int64_t n, void *stream);
+
 
 /* ----------------------------------------------------------------------------------------
  * Rollout-time policy step in one launch (replaces, for all envs of a group at once, the chain
