@@ -121,6 +121,20 @@ class PpoLossMbDesc(C.Structure):
 PPO_LOSS_MB_MAX_ROWS = 16384
 
 
+class TcnDesc(C.Structure):
+    """egp_tcn_desc (include/egopose_hip.h)."""
+    _fields_ = [("T", C.c_int32), ("B", C.c_int32), ("C_in", C.c_int32), ("C_out", C.c_int32),
+                ("taps", C.c_int32), ("shift0", C.c_int32), ("dshift", C.c_int32),
+                ("X", vp), ("ldx", C.c_int64),
+                ("W", vp),
+                ("bias", vp), ("relu", C.c_int32),
+                ("mask", vp), ("ldmask", C.c_int64),
+                ("gate", vp), ("ldgate", C.c_int64),
+                ("X2", vp), ("ldx2", C.c_int64), ("C2", C.c_int32), ("W2", vp), ("b2", vp), ("x2_after_act", C.c_int32),
+                ("out", vp), ("ldout", C.c_int64),
+                ("out2", vp), ("ldout2", C.c_int64)]
+
+
 class AdamSegment(C.Structure):
     """egp_adam_segment (include/egopose_hip.h)."""
     _fields_ = [("begin", C.c_int64), ("end", C.c_int64),
@@ -218,6 +232,7 @@ SIGNATURES = {
     "egp_ppo_loss_f32": (C.c_int, [C.POINTER(PpoLossDesc), vp]),
     "egp_minibatch_plan_f32": (C.c_int, [C.POINTER(MinibatchPlanDesc), vp]),
     "egp_ppo_loss_mb_f32": (C.c_int, [C.POINTER(PpoLossMbDesc), vp]),
+    "egp_tcn_conv_f32": (C.c_int, [C.POINTER(TcnDesc), vp]),
     "egp_adam_workspace_bytes": (_i64, []),
     "egp_adam_step_f32": (C.c_int, [_i32, C.POINTER(AdamSegment), vp, vp, vp, vp, vp, vp, vp]),
     "egp_adam_step_f64": (C.c_int, [_i32, C.POINTER(AdamSegment), vp, vp, vp, vp, vp, vp, vp, vp]),

@@ -374,6 +374,16 @@ class AgentPPO(AgentPG):
         """Hook: prepare the critic's and the actor's state transforms together (AgentEgo). False = nothing prepared."""
         return False
 
+    def _dropout_active(self):
+        """True when a module of the update draws dropout masks in train mode (a TCN video net with dropout > 0): a train-mode
+        forward pass then is not the eval-mode pass the reference takes its GAE values and fixed log-probs from."""
+        for net in self.update_modules:
+            for m in net.modules():
+                p = m.p if isinstance(m, torch.nn.modules.dropout._DropoutNd) else getattr(m, "dropout", 0.0)
+                if isinstance(p, (int, float)) and p > 0:
+                    return True
+        return False
+
     def _clip_list(self):
         return [(list(params), max_norm) for params, max_norm in (self.policy_grad_clip or [])]
 
@@ -576,7 +586,8 @@ class AgentPPO(AgentPG):
         """The epochs with optim.ppo_losses: forward passes -> ONE launch for both losses and d loss / d (values, action mean)
         -> autograd from those two tensors -> fused exchange / clip / Adam (`_optim_step`). Epoch 0's forward doubles as the
         pass that fixes the sampling policy's log-probabilities (the weights have not moved since the rollout), whether it
-        arrives as `first_pass` or is made here."""
+        arrives as `first_pass` or is made here -- unless the nets draw dropout masks in train mode (`_dropout_active`): the
+        log-probabilities are then fixed by an eval-mode pass of their own, as the reference's `to_test` block does."""
         dev = states.device
         n, A = states.shape[0], actions.shape[1]
         pol = self.cn.policy_net
@@ -587,6 +598,15 @@ class AgentPPO(AgentPG):
         d_mean = torch.empty(n_ind, A, dtype=torch.float32, device=dev)
         rec = torch.zeros(max(1, self.opt_num_epochs), 2, dtype=torch.float64, device=dev)
         act = actions if actions.stride(1) == 1 else actions.contiguous()
+        eval_fixed = first_pass is None and self._dropout_active()
+        if eval_fixed:
+            with to_test(*self.update_modules):
+                with torch.no_grad():
+                    x = self.trans_policy(states)
+                    mean = self._policy_mean(x if ind is None else x[ind])
+            # (only `fixed` is kept of this launch: the value columns are placeholders, epoch 0 rewrites rec[0] and the gradients)
+            O.ppo_losses(returns.reshape(-1, 1), returns, mean, act, log_std.detach(), advantages, fixed, True, self.clip_epsilon, n_val, n_exp,
+                         rows=ind, d_pred=d_pred, d_mean=d_mean, losses_out=rec[0])
         for epoch in range(self.opt_num_epochs):
             if first_pass is not None and epoch == 0:
                 pred, mean = first_pass[0], first_pass[1]
@@ -596,7 +616,7 @@ class AgentPPO(AgentPG):
                 x = self.trans_policy(states)
                 mean = self._policy_mean(x if ind is None else x[ind])
             self._zero_grads()
-            _, _, _, d_ls = O.ppo_losses(pred.detach(), returns, mean.detach(), act, log_std.detach(), advantages, fixed, epoch == 0,
+            _, _, _, d_ls = O.ppo_losses(pred.detach(), returns, mean.detach(), act, log_std.detach(), advantages, fixed, epoch == 0 and not eval_fixed,
                                          self.clip_epsilon, n_val, n_exp, rows=ind, d_pred=d_pred, d_mean=d_mean,
                                          want_d_log_std=learn_std, losses_out=rec[epoch])
             torch.autograd.backward([pred, mean], [d_pred, d_mean])
@@ -704,9 +724,10 @@ class AgentEgo(AgentPPO):
                 net.initialize(x_init)
         n_rows = c["states"].shape[0]
         ind, n_ind = self._exploration_rows(c["exps"], n_rows)
-        if self.value_opt_niter == 1 and self.reuse_first_pass:
+        if self.value_opt_niter == 1 and self.reuse_first_pass and not self._dropout_active():
             # ONE forward pass with autograd on serves three purposes: the values that GAE consumes, the fixed log-probs of
-            # the surrogate, and epoch 0's forward (nothing has stepped in between; no dropout / batch norm in these nets)
+            # the surrogate, and epoch 0's forward (nothing has stepped in between, and no net draws dropout masks: with a
+            # TCN video net and dropout > 0 a train-mode pass is not the eval-mode one, and the branch below runs instead)
             self._group_contexts(c["states"])
             pred0 = self.cn.value_net(self.trans_value(c["states"]))
             x = self.trans_policy(c["states"])

@@ -25,6 +25,8 @@ from . import dist as _dist
 from . import gemm as _gemm
 from . import gemm_tuning as _tuning
 from . import lstm as _hip_lstm
+from . import tcn as _tcn
+from .tcn import TemporalConvNet  # noqa: F401  (models/tcn.py: part of the nets' public surface)
 
 # Length buckets of the train-mode forward LSTM (1 = off: measured SLOWER on the MI355X -- the persistent LSTM kernel is
 # bound by its per-timestep latency, not by the batch, so four short launches in a row cost more than one long one; the
@@ -288,6 +290,21 @@ class RNN(nn.Module):
         return out
 
 
+def _video_net(input_dim, v_hdim, v_net_type, v_net_param, causal):
+    """The temporal net of the video slot: 'lstm' (bi-directional unless causal) or 'tcn' (tcn.from_param)."""
+    if v_net_type == "lstm":
+        return RNN(input_dim, v_hdim, v_net_type, bi_dir=not causal)
+    if v_net_type == "tcn":
+        return _tcn.from_param(input_dim, v_hdim, v_net_param, causal)
+    raise ValueError("v_net_type must be 'lstm' or 'tcn', got %r" % (v_net_type,))
+
+
+def _run_video_net(v_net, x):
+    """(T, B, D) -> (T, B, v_hdim); the TCN runs time-major as it is (the reference permutes to (B, C, T) and back,
+    models/video_state_net.py:72-78)."""
+    return v_net.forward_tm(x) if isinstance(v_net, _tcn.TemporalConvNet) else v_net(x)
+
+
 class VideoStateNet(nn.Module):
     """Temporal net over precomputed CNN features, concatenated in front of the state.
 
@@ -301,11 +318,9 @@ class VideoStateNet(nn.Module):
 
     def __init__(self, cnn_feat_dim, v_hdim=128, v_margin=10, v_net_type="lstm", v_net_param=None, causal=False):
         super().__init__()
-        if v_net_type != "lstm":
-            raise NotImplementedError("only the 'lstm' video net is on the hot path (tcn is out of scope)")
         self.mode = "test"
         self.cnn_feat_dim, self.v_hdim, self.v_margin, self.v_net_type = cnn_feat_dim, v_hdim, v_margin, v_net_type
-        self.v_net = RNN(cnn_feat_dim, v_hdim, v_net_type, bi_dir=not causal)
+        self.v_net = _video_net(cnn_feat_dim, v_hdim, v_net_type, v_net_param, causal)
         self.v_out = None
         self.t = 0
         self.indices = None
@@ -323,7 +338,7 @@ class VideoStateNet(nn.Module):
         self.mode = mode
 
     def forward_v_net(self, x):
-        return self.v_net(x)
+        return _run_video_net(self.v_net, x)
 
     def attach_feature_table(self, table, take_offset):
         """Device-resident concatenation of all takes' features (+ row offsets) for gather-built contexts."""
@@ -414,7 +429,8 @@ class VideoStateNet(nn.Module):
         # reference. Windows added to fill an episode bucket need no step at all.
         steps = np.zeros(self.cnn_feat_ctx.shape[1], np.int64)
         steps[:len(lens)] = lens + m
-        self._ragged = _hip_lstm.ragged_order(steps, device, T=self.cnn_feat_ctx.shape[0]) if self.cnn_feat_ctx.is_cuda else None
+        lstm_ctx = self.cnn_feat_ctx.is_cuda and isinstance(self.v_net, RNN)         # (a TCN has no sweeps to cut short)
+        self._ragged = _hip_lstm.ragged_order(steps, device, T=self.cnn_feat_ctx.shape[0]) if lstm_ctx else None
         # Length buckets for the forward direction: its output at frame t only depends on frames <= t and only frames
         # [m, m + len_e) of an episode are ever gathered, so episodes sorted by length let the forward LSTM stop early
         # (the backward direction starts at the end of the padded window and must run it all, as in the reference).
@@ -487,12 +503,14 @@ class VideoStateNet(nn.Module):
             (ctx, with_grad), self._v_ctx = self._v_ctx, None
             if with_grad != torch.is_grad_enabled():
                 ctx = None                   # left over from a pass in the other autograd mode: never reuse it
-        if ctx is None:
+        if ctx is None and isinstance(self.v_net, RNN):
             self.v_net.ragged = self._ragged
             try:
                 ctx = self.forward_v_net(self.cnn_feat_ctx)
             finally:
                 self.v_net.ragged = None
+        elif ctx is None:
+            ctx = self.forward_v_net(self.cnn_feat_ctx)
         ctx2d = ctx.reshape(-1, self.v_hdim)
         if self._gather_unique and _gemm.gather_concat_available(ctx2d, self._gather_tm, x):
             if lazy_width and _gemm.fused_gather_available(self.v_hdim, lazy_width, x.shape[1]):
@@ -560,18 +578,16 @@ class VideoRegNet(nn.Module):          # (ResNet is defined further down; resolv
         super().__init__()
         if not no_cnn and cnn_type != "resnet":
             raise NotImplementedError("only the 'resnet' image encoder is implemented (mobile net is out of scope)")
-        if v_net_type != "lstm":
-            raise NotImplementedError("only the 'lstm' video net is implemented (tcn is out of scope)")
         self.out_dim, self.cnn_fdim, self.v_hdim, self.no_cnn = out_dim, cnn_fdim, v_hdim, no_cnn
         self.frame_shape = tuple(frame_shape)
         self.cnn = None if no_cnn else ResNet(cnn_fdim)
         self.v_net_type = v_net_type
-        self.v_net = RNN(cnn_fdim, v_hdim, v_net_type, bi_dir=not causal)
+        self.v_net = _video_net(cnn_fdim, v_hdim, v_net_type, v_net_param, causal)
         self.mlp = MLP(v_hdim, mlp_dim, "relu")
         self.linear = nn.Linear(self.mlp.out_dim, out_dim)
 
     def forward_v_net(self, x):
-        return self.v_net(x)
+        return _run_video_net(self.v_net, x)
 
     def channels_last(self):
         """Keep the encoder's weights and activations NHWC (MIOpen's fp32 kernels run the ResNet-18 step 22 % faster in
@@ -622,7 +638,7 @@ class VideoRegNet(nn.Module):          # (ResNet is defined further down; resolv
 
 class VideoForecastNet(nn.Module):
     """Policy/value front end of ego_forecast (models/video_forecast_net.py:7-111): the video net sees only the
-    `v_margin` frames BEFORE the episode (causal LSTM, last output kept for the whole episode), the state goes through
+    `v_margin` frames BEFORE the episode (causal LSTM or causal TCN, last output kept for the whole episode), the state goes through
     its own LSTM (`s_net_type='lstm'`, stepped one env-step at a time while sampling) or through unchanged ('id').
 
     test mode   ``initialize(window)``: window (>= v_margin, D) of ONE episode, or (v_margin, B, D) for a batch of
@@ -636,15 +652,13 @@ class VideoForecastNet(nn.Module):
     def __init__(self, cnn_feat_dim, state_dim, v_hdim=128, v_margin=10, v_net_type="lstm", v_net_param=None,
                  s_hdim=None, s_net_type="id", dynamic_v=False):
         super().__init__()
-        if v_net_type != "lstm":
-            raise NotImplementedError("only the 'lstm' video net is implemented (tcn is out of scope)")
         if s_net_type not in ("id", "lstm"):
             raise ValueError("s_net_type must be 'id' or 'lstm'")
         s_hdim = state_dim if s_hdim is None else s_hdim
         self.cnn_feat_dim, self.state_dim, self.v_hdim, self.v_margin = cnn_feat_dim, state_dim, v_hdim, v_margin
         self.v_net_type, self.s_net_type, self.s_hdim, self.dynamic_v = v_net_type, s_net_type, s_hdim, dynamic_v
         self.out_dim = v_hdim + s_hdim
-        self.v_net = RNN(cnn_feat_dim, v_hdim, v_net_type, bi_dir=False)
+        self.v_net = _video_net(cnn_feat_dim, v_hdim, v_net_type, v_net_param, True)
         if s_net_type == "lstm":
             self.s_net = RNN(state_dim, s_hdim, s_net_type, bi_dir=False)
         self.v_out = None
@@ -661,7 +675,7 @@ class VideoForecastNet(nn.Module):
             self.s_net.set_mode("batch" if mode == "train" else "step")
 
     def forward_v_net(self, x):
-        return self.v_net(x)
+        return _run_video_net(self.v_net, x)
 
     def attach_feature_table(self, table, take_offset):
         host = np.asarray(take_offset, dtype=np.int64)
@@ -772,12 +786,12 @@ def grouped_video_context(nets):
     """Train-mode video contexts of several VideoStateNets (the critic's and the actor's) in ONE grouped recurrent
     launch each way (lstm.LstmGroup): their bi-LSTMs read the same windows with different weights, and a single sweep
     leaves most of the chip idle. Each net's next forward() consumes its context. Returns False (nothing done) when the
-    nets do not qualify; the nets then compute their contexts one by one as usual."""
+    nets do not qualify (a TCN video net among them); the nets then compute their contexts one by one as usual."""
     if _LSTM_IMPL == "torch" or len(nets) < 1:
         return False
     n0 = nets[0]
     for n in nets:
-        if not (isinstance(n, VideoStateNet) and n.mode == "train" and n._buckets is None and n.v_net.cell_type == "lstm"
+        if not (isinstance(n, VideoStateNet) and n.mode == "train" and n._buckets is None and getattr(n.v_net, "cell_type", None) == "lstm"
                 and n.cnn_feat_ctx is not None and n.cnn_feat_ctx.shape == n0.cnn_feat_ctx.shape and n._ctx_key == n0._ctx_key
                 and n.cnn_feat_ctx.dtype == n0.cnn_feat_ctx.dtype and n.v_net.bi_dir == n0.v_net.bi_dir):
             return False
@@ -798,7 +812,8 @@ def grouped_video_context(nets):
 
 def grouped_forecast_context(nets, x):
     """ego_forecast's counterpart of grouped_video_context: the causal video LSTMs of all nets in one grouped launch each
-    way, and their state LSTMs over the scattered states `x` in another. Each net's next forward(x) consumes its pair."""
+    way, and their state LSTMs over the scattered states `x` in another. Each net's next forward(x) consumes its pair.
+    False (nothing done) when a net's video side is a TCN: every net then runs its own two nets."""
     if _LSTM_IMPL == "torch" or len(nets) < 2 or x is None:
         return False
     n0 = nets[0]
@@ -806,7 +821,7 @@ def grouped_forecast_context(nets, x):
         if not (isinstance(n, VideoForecastNet) and n.mode == "train" and n.s_net_type == "lstm" and n.cnn_feat_ctx is not None
                 and n._ctx_key is not None and n._ctx_key == n0._ctx_key and n.cnn_feat_ctx.shape == n0.cnn_feat_ctx.shape
                 and n.cnn_feat_ctx.dtype == n0.cnn_feat_ctx.dtype and n.dynamic_v == n0.dynamic_v and n.state_dim == n0.state_dim
-                and not n.v_net.bi_dir and not n.s_net.bi_dir and n.v_net.cell_type == "lstm" and n.s_net.cell_type == "lstm"):
+                and isinstance(n.v_net, RNN) and not n.v_net.bi_dir and not n.s_net.bi_dir and n.v_net.cell_type == "lstm" and n.s_net.cell_type == "lstm"):
             return False
     v_cells, s_cells = [n.v_net.rnn_f for n in nets], [n.s_net.rnn_f for n in nets]
     s_in = n0.state_sequences(x)

@@ -411,6 +411,33 @@ int egp_scatter_rows_f32(const float *dout, int64_t ldd, const int64_t *idx, int
 int64_t egp_gemm_workspace_floats(int32_t M, int32_t N, int32_t ones_col, int32_t splits);
 int egp_gemm_f32(const egp_gemm_desc *desc, void *stream);
 
+/* ---------------------------------------------------------------------------------------- TCN
+ * Dilated temporal convolution of the TCN video net (models/tcn.py:15-70) on a time-major batch (csrc/egp_tcn.hip). In the
+ * (T*B, C) matrix of a (T, B, C) batch a tap is the matrix shifted by whole rows, so forward pass and data gradient are both
+ *     acc[r][:] = sum_j X[r + s_j*B][:] W[j]^T      s_j = shift0 + j*dshift, j < taps <= 7, W dense [taps][C_out][C_in]
+ * in exact float32 (v_mfma_f32_32x32x2_f32). A row whose source time step r/B + s_j leaves [0, T) contributes zero and is not
+ * read. Forward: shift0 = -pad, dshift = dilation; data gradient: shift0 = +pad, dshift = -dilation, W[j] transposed.
+ * Epilogue, every part optional (NULL pointer / 0):
+ *     X2 (ldx2, C2 columns), x2_after_act = 0:  acc += X2[r] W2^T  (W2 dense [C_out][C2]; W2 = NULL: acc += X2[r], C2 == C_out)
+ *     v = acc + bias[c];  relu: v = max(v, 0);  v *= mask[r][c];  gate: v = gate[r][c] > 0 ? v : 0;   out2[r][c] = v
+ *     X2, x2_after_act = 1:  v = max(v + X2[r] W2^T + b2[c], 0)     (the residual branch, the add and the last ReLU of a block)
+ *     out[r][c] = v
+ * C_in, C_out (and C2 with W2) multiples of 16 in [16, 512]; X, W, X2 (with W2), W2 16-byte aligned with leading dimensions
+ * that are multiples of 4; T*B < 2^31 - 128. Anything else is refused with EGP_E_INVALID. All pointers are device memory. */
+struct egp_tcn_desc {
+    int32_t T, B, C_in, C_out, taps, shift0, dshift;
+    const float *X; int64_t ldx;
+    const float *W;
+    const float *bias; int32_t relu;
+    const float *mask; int64_t ldmask;
+    const float *gate; int64_t ldgate;
+    const float *X2; int64_t ldx2; int32_t C2; const float *W2; const float *b2; int32_t x2_after_act;
+    float *out; int64_t ldout;
+    float *out2; int64_t ldout2;
+};
+typedef struct egp_tcn_desc egp_tcn_desc;
+int egp_tcn_conv_f32(const egp_tcn_desc *desc, void *stream);
+
 /* ---------------------------------------------------------------------------------------- LSTM
  * Recurrent sweep of ONE direction of the video-context LSTM (hidden size 64 or 128, float32, zero initial state):
  * the t-loop of RNN.batch_forward (models/rnn.py:45-61) in one launch.
