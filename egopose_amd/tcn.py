@@ -14,7 +14,8 @@ Two ways to run a block:
          to 512, odd kernel_size <= 7. Forward is two launches per block (conv1; conv2 with the residual product, the add and
          the last ReLU in its epilogue), the data gradient two more (the same kernel with the weights transposed and the
          shifts negated); the weight gradients are one `gemm.linear_wgrad` per tap over contiguous row slices.
-  torch  K `addmm` calls on row slices, plain autograd: every other dtype / device / shape, and `EGP_TCN=torch`.
+  torch  K `addmm` calls on row slices, plain autograd: every other dtype / device / shape (an empty batch among them), and
+         `EGP_TCN=torch`.
 """
 from __future__ import annotations
 
@@ -75,11 +76,18 @@ def conv_rows(x, T, B, w, shift0, dshift, bias=None, relu=False, mask=None, gate
         x2_after_act:  v = relu(v + x2 w2^T + b2)                    -> out
     `out` / `out2`: (T*B, C_out) row views to write into (allocated when `out` is None). Returns out."""
     global HIP_CALLS
+    if w.dim() != 3 or not w.is_contiguous() or w.dtype != torch.float32:
+        raise ValueError("w must be contiguous float32 (taps, C_out, C_in), got %s %s" % (tuple(w.shape), w.dtype))
+    if w2 is not None and (w2.dim() != 2 or not w2.is_contiguous() or w2.dtype != torch.float32):
+        raise ValueError("w2 must be contiguous float32 (C_out, C2), got %s %s" % (tuple(w2.shape), w2.dtype))
+    if b2 is not None and (x2 is None or w2 is None):
+        raise ValueError("b2 goes with the second product only: it needs x2 and w2")
     taps, c_out, c_in = w.shape
     M = T * B
-    x, w, x2, w2 = _vec(_rows(x, "x")), _vec(w), _vec(x2), _vec(w2)
-    if x.shape != (M, c_in) or not w.is_contiguous() or w.dtype != torch.float32:
-        raise ValueError("x must be (T*B, C_in) = (%d, %d) and w contiguous float32 (taps, C_out, C_in), got %s, %s" % (M, c_in, tuple(x.shape), tuple(w.shape)))
+    # an identity x2 is read element by element, at any offset and leading dimension
+    x, w, x2, w2 = _vec(_rows(x, "x")), _vec(w), (_vec(x2) if w2 is not None else x2), _vec(w2)
+    if x.shape != (M, c_in):
+        raise ValueError("x must be (T*B, C_in) = (%d, %d), got %s" % (M, c_in, tuple(x.shape)))
     if out is None:
         out = torch.empty(M, c_out, dtype=torch.float32, device=x.device)
     d = L.TcnDesc()
@@ -107,6 +115,10 @@ def conv_rows(x, T, B, w, shift0, dshift, bias=None, relu=False, mask=None, gate
     d.out, d.ldout = out.data_ptr(), _ld(out)
     if out2 is not None:
         d.out2, d.ldout2 = out2.data_ptr(), _ld(out2)
+    if M == 0:          # no row to compute; empty tensors have no address the launcher would accept
+        if not (_channels_ok(c_in) and _channels_ok(c_out) and 1 <= taps <= MAX_TAPS):
+            raise ValueError("C_in and C_out must be multiples of 16 in [16, %d], 1 to %d taps" % (MAX_CHANNELS, MAX_TAPS))
+        return out
     L.check(L.load().egp_tcn_conv_f32(C.byref(d), L.current_stream()), "egp_tcn_conv_f32")
     HIP_CALLS += 1
     return out
@@ -228,7 +240,8 @@ def run_block(x, w1, b1, w2, b2, wd, bd, m1, m2, dilation, causal):
     """A block on whichever path serves `x` (the same masks either way)."""
     c_out, c_in, K = w1.shape
     params = (w1, b1, w2, b2, wd, bd)
-    if hip_available(x, c_in, c_out, K, params + (m1, m2)):
+    # an empty batch has nothing to launch: the plain ops give the empty result and zero (or no) parameter gradients
+    if x.shape[0] * x.shape[1] > 0 and hip_available(x, c_in, c_out, K, params + (m1, m2)):
         train = torch.is_grad_enabled() and (x.requires_grad or any(p is not None and p.requires_grad for p in params))
         return TcnBlock.apply(x.contiguous(), w1, b1, w2, b2, wd, bd, m1, m2, dilation, causal, train)
     return block_torch(x, w1, b1, w2, b2, wd, bd, m1, m2, dilation, causal)
