@@ -16,34 +16,44 @@ in lockstep, in passes of N takes in take order, and a tick is
     -> host: fail-safe decision per slot -> re-seat the flagged slots on their take's state_pred[t + 1]
 
 with the bracket one launch (`FusedActorCritic.with_filter`, egp_policy_value_filter_f32) and the values' copy to pinned memory
-queued behind it. The video contexts and the state regressor's predictions of a take are computed once per take, at batch 1 as
-above (a take's result does not depend on the slot count). 'valuefs' compares against a running mean over ALL values in take
+queued behind it. The pass itself -- the batched env, the frozen filter's device state, seating and re-seating slots, the records and
+their copy-out, a tick's event / env-step / timed wait -- is `lockstep_eval.LockstepPass`, shared with the forecast evaluation; the
+launch, the value copy and the host decision are here. The video contexts and the state regressor's predictions of a take are
+computed once per take, at batch 1 as above (a take's result does not depend on the slot count). 'valuefs' compares against a running mean over ALL values in take
 order; `egopose_amd.failsafe` makes that exact for takes that run side by side (speculative runs, checked against the true
 statistic afterwards, re-run where a decision differs). The reward (which nothing reads) is not evaluated; `causal` and
 `show_noise` stay with `Evaluator`.
 
-Takes that have video features only (no MoCap, no expert): `egopose_amd.evaluate_wild` (`--test-feat NAME`), on the same pass.
+Takes that have video features only (no MoCap, no expert): `egopose_amd.evaluate_wild` (`--test-feat NAME`), on the same pass and,
+take by take, on the same loop (`Evaluator._eval_take`). `regressor_states` is the state regressor's prediction of a take for both.
 """
 from __future__ import annotations
 
 import copy
-import os
 import pickle
-import time
 
 import numpy as np
 import torch
 
 from . import metrics
+from .lockstep_eval import LockstepPass, Timing, check_frozen_filter
 from .reward import reward_func
 from .zfilter import RunningStat
 
 
-class Evaluator:
+def regressor_states(state_net, mean, std, cnn_feat, fr_margin):
+    """The state regressor's de-normalised prediction for the frames of a take between the margins, at batch 1
+    (ego_mimic_eval.py:121-122) -> float64 [len - 2 * fr_margin][state]."""
+    m, sp = fr_margin, next(state_net.parameters())
+    state_pred = state_net(cnn_feat.to(device=sp.device, dtype=sp.dtype).unsqueeze(1))[m:-m].double().cpu().numpy()
+    return state_pred * std[None, :] + mean[None, :]
+
+
+class _MimicEvaluator:
+    """What `Evaluator` and `BatchedEvaluator` share: the nets in test mode, the fail-safe's name, the trace, the pickle."""
 
     def __init__(self, cfg, env, policy_net, policy_vs_net, value_net, value_vs_net, state_net, state_net_mean, state_net_std,
-                 running_state=None, fail_safe="valuefs", causal=False, show_noise=False, sync=False, logger=None,
-                 keep_trace=False):
+                 running_state, fail_safe, causal, show_noise, sync, logger, keep_trace):
         if fail_safe not in ("valuefs", "naivefs", "none"):
             raise ValueError("fail_safe must be 'valuefs', 'naivefs' or 'none'")
         self.cfg, self.env = cfg, env
@@ -53,13 +63,27 @@ class Evaluator:
         self.state_net_mean, self.state_net_std = np.asarray(state_net_mean, float), np.asarray(state_net_std, float)
         self.running_state = running_state
         self.fail_safe, self.causal, self.show_noise, self.sync = fail_safe, causal, show_noise, sync
-        self.value_stat = RunningStat(1)
         self.logger = logger
         self.trace = {} if keep_trace else None      # per take: actions, values, reset frames, regressor states
         for net in (policy_net, policy_vs_net, value_net, value_vs_net, state_net):
             net.eval()
         for net in (policy_vs_net, value_vs_net):
             net.set_mode("test")
+
+    def save(self, results, meta, it, data="test"):
+        fs_tag = "" if self.fail_safe == "valuefs" else "_" + self.fail_safe
+        c_tag = "_causal" if self.causal else ""
+        return metrics.save_results("%s/iter_%04d_%s%s%s.p" % (self.cfg.result_dir, it, data, fs_tag, c_tag), results, meta)
+
+
+class Evaluator(_MimicEvaluator):
+
+    def __init__(self, cfg, env, policy_net, policy_vs_net, value_net, value_vs_net, state_net, state_net_mean, state_net_std,
+                 running_state=None, fail_safe="valuefs", causal=False, show_noise=False, sync=False, logger=None,
+                 keep_trace=False):
+        super().__init__(cfg, env, policy_net, policy_vs_net, value_net, value_vs_net, state_net, state_net_mean, state_net_std,
+                         running_state, fail_safe, causal, show_noise, sync, logger, keep_trace)
+        self.value_stat = RunningStat(1)
         p = next(policy_net.parameters())
         self.device, self.dtype = p.device, p.dtype
 
@@ -76,36 +100,43 @@ class Evaluator:
     def _filter(self, state):
         return self.running_state(state, update=False) if self.running_state is not None else state
 
-    # ------------------------------------------------------------------ ego_mimic_eval.py:103-175
+    # What a subclass over feature-only takes changes (evaluate_wild.WildEvaluator): how the env is reset to a take, and whether the
+    # take has an expert -- its row per tick, the reward, and the `info['end']` that ends the take before a decision.
+    HAS_EXPERT = True
+
+    def _reset_to_take(self, expert_ind):
+        """Reset the env to the take -> (its name, its features, its frames between the margins)."""
+        env, m = self.env, self.cfg.fr_margin
+        test_len = env.cnn_feat[expert_ind].shape[0] - 2 * m
+        env.set_fix_sampling(expert_ind, m, test_len)
+        env.reset()
+        return env.expert_list[expert_ind], env.get_episode_cnn_feat(), test_len
+
+    # ------------------------------------------------------------------ ego_mimic_eval.py:103-175, ego_mimic_eval_wild.py:94-140
     @torch.no_grad()
-    def eval_expert(self, expert_ind):
+    def _eval_take(self, key):
+        """-> (traj_pred, traj_orig or None, vel_pred, num_reset) of one take."""
         env, cfg = self.env, self.cfg
         m = cfg.fr_margin
-        data_len = env.cnn_feat[expert_ind].shape[0]
-        test_len = data_len - 2 * m
-        env.set_fix_sampling(expert_ind, m, test_len)
+        take, cnn_feat, test_len = self._reset_to_take(key)
         traj_pred, traj_orig, vel_pred = [], [], []
         num_reset, reward_episode = 0, 0.0
 
-        state = env.reset()
-        cnn_feat = torch.as_tensor(env.get_episode_cnn_feat(), dtype=self.dtype, device=self.device)
+        cnn_feat = torch.as_tensor(cnn_feat, dtype=self.dtype, device=self.device)
         self.policy_vs_net.initialize(cnn_feat)
         self.value_vs_net.initialize(cnn_feat)
-        sp = next(self.state_net.parameters())
-        state_pred = self.state_net(cnn_feat.to(device=sp.device, dtype=sp.dtype).unsqueeze(1))[m:-m].double().cpu().numpy()
-        state_pred = state_pred * self.state_net_std[None, :] + self.state_net_mean[None, :]
+        state_pred = regressor_states(self.state_net, self.state_net_mean, self.state_net_std, cnn_feat, m)
 
         state = self._filter(self.reset_env_state(state_pred[0], env.data.qpos))
         tr = None
         if self.trace is not None:
-            tr = self.trace[env.expert_list[expert_ind]] = dict(actions=[], values=[], resets=[], state_pred=state_pred)
+            tr = self.trace[take] = dict(actions=[], values=[], resets=[], state_pred=state_pred)
         for t in range(test_len):
-            ind = env.get_expert_index(t)
-            epos = env.get_expert_attr("qpos", ind).copy()
             data = env.data
             traj_pred.append(data.qpos.copy())
-            traj_orig.append(epos.copy())
             vel_pred.append(data.qvel.copy())
+            if self.HAS_EXPERT:
+                traj_orig.append(env.get_expert_attr("qpos", env.get_expert_index(t)).copy())
             if self.causal:
                 self.policy_vs_net.initialize(cnn_feat[:t + 2 * m + 1])
                 self.policy_vs_net.t = t
@@ -119,21 +150,29 @@ class Evaluator:
                 tr["values"].append(value)
             next_state, _, done, info = env.step(action)
             next_state = self._filter(next_state)
-            reward, _ = reward_func[cfg.reward_id](env, state, action, info)
-            reward_episode += reward
-            if info["end"]:
-                break
+            if self.HAS_EXPERT:
+                reward, _ = reward_func[cfg.reward_id](env, state, action, info)
+                reward_episode += reward
+                if info["end"]:
+                    break
             if (self.fail_safe == "valuefs" and value < 0.6 * self.value_stat.mean[0]) or (self.fail_safe == "naivefs" and info["fail"]):
                 if self.logger is not None:
                     self.logger.info("reset state!")
                 num_reset += 1
                 if tr is not None:
                     tr["resets"].append(t)
-                state = self._filter(self.reset_env_state(state_pred[t + 1], env.data.qpos))
+                # A decision on the last tick has no next frame to re-seat on. With an expert `end` has ended the take before it; without
+                # one the reference reads state_pred[test_len] there, an IndexError. It cannot change traj_pred: the last row is recorded.
+                if t + 1 < test_len:
+                    state = self._filter(self.reset_env_state(state_pred[t + 1], env.data.qpos))
             else:
                 state = next_state
-        self.last_reward = reward_episode
-        return np.vstack(traj_pred), np.vstack(traj_orig), np.vstack(vel_pred), num_reset
+        if self.HAS_EXPERT:
+            self.last_reward = reward_episode
+        return np.vstack(traj_pred), np.vstack(traj_orig) if traj_orig else None, np.vstack(vel_pred), num_reset
+
+    def eval_expert(self, expert_ind):
+        return self._eval_take(expert_ind)
 
     # ------------------------------------------------------------------ ego_mimic_eval.py:183-197
     def run(self, takes=None):
@@ -148,17 +187,8 @@ class Evaluator:
         meta = {"algo": "ego_mimic", "num_reset": num_reset}
         return results, meta
 
-    def save(self, results, meta, it, data="test"):
-        fs_tag = "" if self.fail_safe == "valuefs" else "_" + self.fail_safe
-        c_tag = "_causal" if self.causal else ""
-        path = "%s/iter_%04d_%s%s%s.p" % (self.cfg.result_dir, it, data, fs_tag, c_tag)
-        os.makedirs(os.path.dirname(path), exist_ok=True)
-        with open(path, "wb") as f:
-            pickle.dump((results, meta), f)
-        return path
 
-
-class BatchedEvaluator:
+class BatchedEvaluator(_MimicEvaluator):
     """`Evaluator` with the takes on `num_envs` lockstep slots (module docstring). `run()` -> the same (results, meta), `save()`
     the same pickle. `keep_trace`: `self.trace[take]` = dict(actions [T][nu], values [T], resets, state_pred, states [T][obs]) of
     the accepted run. `self.timing`: wall seconds of the last run, split into the wait for the host physics and the rest, and the
@@ -169,31 +199,17 @@ class BatchedEvaluator:
                  keep_trace=False, num_envs=8, device_index=0, n_threads=None):
         from . import policy_step
         from .failsafe import SpeculativeValueFailSafe
-        if fail_safe not in ("valuefs", "naivefs", "none"):
-            raise ValueError("fail_safe must be 'valuefs', 'naivefs' or 'none'")
         if causal or show_noise:
             raise NotImplementedError("causal / show_noise evaluation runs take by take: use Evaluator")
-        if running_state is not None and not (running_state.demean and running_state.destd):
-            raise NotImplementedError("running_state without demean / destd: use Evaluator")
+        check_frozen_filter(running_state, ": use Evaluator")
         if not (policy_step.supported(policy_net) and policy_step.supported_value(value_net)):
             raise NotImplementedError("the batched evaluation needs the HIP actor + critic step (float32 PolicyGaussian and Value "
                                       "over plain MLPs): use Evaluator")
-        self.cfg, self.env = cfg, env
-        self.policy_net, self.policy_vs_net = policy_net, policy_vs_net
-        self.value_net, self.value_vs_net = value_net, value_vs_net
-        self.state_net = state_net
-        self.state_net_mean, self.state_net_std = np.asarray(state_net_mean, float), np.asarray(state_net_std, float)
-        self.running_state = running_state
-        self.fail_safe, self.causal, self.show_noise, self.sync = fail_safe, False, False, sync
+        super().__init__(cfg, env, policy_net, policy_vs_net, value_net, value_vs_net, state_net, state_net_mean, state_net_std,
+                         running_state, fail_safe, False, False, sync, logger, keep_trace)
         self.num_envs, self.device_index, self.n_threads = int(num_envs), int(device_index), n_threads
         self._fs = SpeculativeValueFailSafe(decide_on_end=self.DECIDE_ON_END)
-        self.logger = logger
-        self.trace = {} if keep_trace else None
         self.timing = {}
-        for net in (policy_net, policy_vs_net, value_net, value_vs_net, state_net):
-            net.eval()
-        for net in (policy_vs_net, value_vs_net):
-            net.set_mode("test")
 
     value_stat = property(lambda self: self._fs.stat)      # the running statistic of every accepted value, across run() calls
 
@@ -217,9 +233,7 @@ class BatchedEvaluator:
         cnn_feat = torch.as_tensor(cnn_feat_np, dtype=p.dtype, device=p.device)
         self.policy_vs_net.initialize(cnn_feat)
         self.value_vs_net.initialize(cnn_feat)
-        sp = next(self.state_net.parameters())
-        state_pred = self.state_net(cnn_feat.to(device=sp.device, dtype=sp.dtype).unsqueeze(1))[m:-m].double().cpu().numpy()
-        state_pred = state_pred * self.state_net_std[None, :] + self.state_net_mean[None, :]
+        state_pred = regressor_states(self.state_net, self.state_net_mean, self.state_net_std, cnn_feat, m)
         return dict(len=cnn_feat.shape[0] - 2 * m, pol=self.policy_vs_net.v_out.float().contiguous(),
                     val=self.value_vs_net.v_out.float().contiguous(), state_pred=state_pred)
 
@@ -253,8 +267,20 @@ class BatchedEvaluator:
         """Run the takes `take_inds` (indices into the expert list), each from a copy of its prefix statistic, in passes of N
         slots -> [(values, taken re-seat decisions)]; the full records go to self._latest."""
         from .failsafe import below
-        env, R, tm = self.env, self._run, self.timing
-        sim, ctx, eng, fused, N = R["sim"], R["ctx"], R["eng"], R["fused"], self.num_envs
+        R = self._run
+        lp, fused, v_dev, v_host, N = R["lp"], R["fused"], R["v_dev"], R["v_host"], self.num_envs
+        eng = lp.eng
+
+        def launch(t, k):
+            fused.with_filter(lp.ctx, R["pol_slab"][:k], R["t_all"][t, :k], eng.qpos[:k], eng.qvel[:k], lp.zf_in, None, lp.clip, lp.states[t, :k],
+                              None, None, lp.actions[t, :k], R["val_slab"][:k], v_dev[t, :k], phase_t=lp.phase_t(t))
+
+        def value_copy(t):                         # to pinned memory, behind the event the env-step waits on -> its own event
+            v_host[t].copy_(v_dev[t], non_blocking=True)
+            ev_v = torch.cuda.Event()
+            ev_v.record()
+            return ev_v
+
         out = []
         for c0 in range(0, len(take_inds), N):
             chunk = take_inds[c0:c0 + N]
@@ -266,33 +292,12 @@ class BatchedEvaluator:
                 R["pol_slab"][j, :tb["len"]] = tb["pol"]
                 R["val_slab"][j, :tb["len"]] = tb["val"]
             ref0 = np.stack([self._seat_ref(i) for i in chunk])
-            q0, v0 = self._seat_rows(np.stack([tb["state_pred"][0] for tb in tabs]), ref0)
-            ids = np.arange(k)
-            if not R["seated"] and k < N:         # slots no take ever lands on: a valid state all the same (they are never stepped)
-                ids = np.arange(N)
-                q0, v0 = np.concatenate((q0, np.repeat(q0[:1], N - k, 0))), np.concatenate((v0, np.repeat(v0[:1], N - k, 0)))
-            R["seated"] = True
-            eng.reset(ids, q0, v0)
-            active = np.zeros(N, np.int32)
-            active[:k] = 1
+            active = lp.seat(*self._seat_rows(np.stack([tb["state_pred"][0] for tb in tabs]), ref0))
             resets = [[] for _ in range(k)]
             below_lb = np.array([self._reseat_below(i) for i in chunk]) if self.fail_safe == "naivefs" else None
-            traj, qv, actions, states, v_dev, v_host = R["traj"], R["qv"], R["actions"], R["states"], R["v_dev"], R["v_host"]
-            for t in range(int(lens.max())):
-                traj[t, :k].copy_(eng.qpos[:k])
-                qv[t, :k].copy_(eng.qvel[:k])
-                fused.with_filter(ctx, R["pol_slab"][:k], R["t_all"][t, :k], eng.qpos[:k], eng.qvel[:k], R["zf_in"], None, R["clip"], states[t, :k], None,
-                                  None, actions[t, :k], R["val_slab"][:k], v_dev[t, :k], phase_t=None if R["phase"] is None else R["phase"][t, :k])
-                ev = torch.cuda.Event()
-                ev.record()
-                v_host[t].copy_(v_dev[t], non_blocking=True)
-                ev_v = torch.cuda.Event()
-                ev_v.record()
-                eng.step_async(0, actions[t], active, ev)
-                t0 = time.time()
-                eng.wait(0)
-                tm["phys_wait"] += time.time() - t0
-                ev_v.synchronize()
+            T = int(lens.max())
+            for t in range(T):
+                lp.tick(t, launch, value_copy).synchronize()
                 flagged = []
                 for j in range(k):
                     if not active[j]:
@@ -318,12 +323,8 @@ class BatchedEvaluator:
                         active[j] = 0
                 if flagged:
                     fl = np.array(flagged)
-                    q1, v1 = self._seat_rows(np.stack([tabs[j]["state_pred"][t + 1] for j in flagged]), np.array(eng.qpos_host[fl], float))
-                    eng.reset(fl, q1, v1)
-                tm["ticks"] += 1
-            torch.cuda.synchronize(R["dev"])
-            T = int(lens.max())
-            h_traj, h_qv, h_act, h_st = (x[:T, :k].transpose(0, 1).cpu().numpy() for x in (traj, qv, actions, states))
+                    lp.reseat(fl, *self._seat_rows(np.stack([tabs[j]["state_pred"][t + 1] for j in flagged]), np.array(eng.qpos_host[fl], float)))
+            h_traj, h_qv, h_act, h_st = lp.copy_out(T, "traj", "qvel", "actions", "states")
             h_val = v_host[:T, :k].t().double().numpy().copy()
             for j, i in enumerate(chunk):
                 L = int(lens[j])
@@ -332,36 +333,27 @@ class BatchedEvaluator:
                 self._latest[i] = dict(traj_pred=h_traj[j, :L].copy(), vel_pred=h_qv[j, :L].copy(), actions=h_act[j, :L].copy(),
                                        states=h_st[j, :L].copy(), values=h_val[j, :L].copy(), resets=list(resets[j]))
                 out.append((h_val[j, :L], taken))
-            tm["passes"] += 1
         return out
 
     def run(self, takes=None):
         """Evaluate every take of the env's expert list (or of `takes`) -> (results, meta) in the reference's pickle layout."""
         from . import policy_step
-        env, N = self.env, self.num_envs
-        t_all = time.time()
+        N = self.num_envs
         sel = [i for i, take in enumerate(self._take_names()) if takes is None or take in takes]
-        self.timing = tm = {"phys_wait": 0.0, "passes": 0, "takes": len(sel), "ticks": 0, "fs_passes": 0, "fs_pass_takes": []}
+        self.timing = tm = Timing(takes=len(sel), fs_passes=0, fs_pass_takes=[])
         self._latest = {}
+        tables = {}
         if sel:
-            sim = env.batched(N, self.device_index, self.n_threads, 1)
-            ctx, eng = sim.ctx, sim.engine
-            dev = torch.device("cuda", ctx.device)
-            with torch.no_grad(), torch.cuda.device(dev):
+            with torch.no_grad(), torch.cuda.device(self.device_index):
                 tables = {i: self._take_tables(i) for i in sel}
                 Tm = max(tb["len"] for tb in tables.values())
-                f64, f32 = torch.float64, torch.float32
-                z = lambda *shape, dtype=f64: torch.zeros(*shape, dtype=dtype, device=dev)
-                zf_in, clip = None, 0.0
-                if self.running_state is not None:
-                    zf_in, clip = self.running_state.to_device_state(dev), float(self.running_state.clip or 0.0)
-                self._run = dict(sim=sim, ctx=ctx, eng=eng, dev=dev, tables=tables, seated=False, zf_in=zf_in, clip=clip,
-                                 fused=policy_step.FusedActorCritic(self.policy_net, self.value_net, dev),
-                                 pol_slab=z(N, Tm, self.policy_vs_net.v_hdim, dtype=f32), val_slab=z(N, Tm, self.value_vs_net.v_hdim, dtype=f32),
-                                 traj=z(Tm, N, ctx.nq), qv=z(Tm, N, ctx.nv), actions=z(Tm, N, ctx.nu), states=z(Tm, N, ctx.obs_dim),
-                                 v_dev=z(Tm, N, dtype=f32), v_host=torch.zeros(Tm, N, dtype=f32).pin_memory(),
-                                 t_all=torch.arange(Tm, dtype=torch.int64, device=dev).unsqueeze(1).expand(Tm, N).contiguous(),
-                                 phase=torch.arange(Tm, dtype=torch.int32, device=dev).unsqueeze(1).expand(Tm, N).contiguous() if ctx.obs_phase else None)
+                lp = LockstepPass(self.env, N, self.device_index, self.n_threads, self.running_state, Tm, tm)
+                dev, f32 = lp.dev, torch.float32
+                self._run = dict(lp=lp, tables=tables, fused=policy_step.FusedActorCritic(self.policy_net, self.value_net, dev),
+                                 pol_slab=torch.zeros(N, Tm, self.policy_vs_net.v_hdim, dtype=f32, device=dev),
+                                 val_slab=torch.zeros(N, Tm, self.value_vs_net.v_hdim, dtype=f32, device=dev),
+                                 v_dev=torch.zeros(Tm, N, dtype=f32, device=dev), v_host=torch.zeros(Tm, N, dtype=f32).pin_memory(),
+                                 t_all=torch.arange(Tm, dtype=torch.int64, device=dev).unsqueeze(1).expand(Tm, N).contiguous())
                 if self.fail_safe == "valuefs":
                     self._fs.run(sel, self._run_pass)
                     tm["fs_passes"], tm["fs_pass_takes"] = self._fs.passes, list(self._fs.pass_takes)
@@ -369,10 +361,9 @@ class BatchedEvaluator:
                     self._run_pass(sel, [None] * len(sel))
                     tm["fs_passes"], tm["fs_pass_takes"] = 1, [len(sel)]
             self._run = None
-        out = self._results(sel, tables if sel else {})
+        out = self._results(sel, tables)
         self._latest = None
-        tm["total"] = time.time() - t_all
-        tm["rest"] = tm["total"] - tm["phys_wait"]
+        tm.close()
         return out
 
     def _results(self, sel, tables):
@@ -391,8 +382,6 @@ class BatchedEvaluator:
                 self.trace[take] = dict(actions=rec["actions"], values=rec["values"], resets=rec["resets"], state_pred=tables[i]["state_pred"],
                                         states=rec["states"])
         return {"traj_pred": traj_pred, "traj_orig": traj_orig, "vel_pred": vel_pred}, {"algo": "ego_mimic", "num_reset": num_reset}
-
-    save = Evaluator.save
 
 
 def select_evaluator(policy_net, value_net, num_envs=1, sequential=False, causal=False, show_noise=False):
@@ -419,6 +408,7 @@ def main(argv=None):
     import argparse
     from .config import Config
     from .env import HumanoidEnv
+    from .evaluate_wild import BatchedWildEvaluator, WildEvaluator, cli_takes
     from .nets import MLP, PolicyGaussian, Value, VideoRegNet, VideoStateNet
     ap = argparse.ArgumentParser()
     ap.add_argument("--cfg", default="subject_03")
@@ -442,14 +432,7 @@ def main(argv=None):
     dev, dtype = torch.device("cuda", args.gpu_index), torch.float32
     env = HumanoidEnv(cfg)
     env.seed(cfg.seed)
-    cnn_feat_dict = None
-    if args.test_feat is not None:                 # ego_mimic_eval_wild.py:36-39: no experts
-        from .evaluate_wild import BatchedWildEvaluator, WildEvaluator, load_features
-        cnn_feat_dict = load_features(cfg, args.test_feat)
-        cnn_dim = next(iter(cnn_feat_dict.values())).shape[-1]
-    else:
-        env.load_experts(cfg.takes[args.data], cfg.expert_feat_file, cfg.cnn_feat_file)
-        cnn_dim = env.cnn_feat[0].shape[-1]
+    cnn_feat_dict, cnn_dim = cli_takes(cfg, env, args.data, args.test_feat)
     sd, ad = env.observation_space.shape[0], env.action_space.shape[0]
     mk = lambda hdim, kind, param: VideoStateNet(cnn_dim, hdim, cfg.fr_margin, kind, param, cfg.causal)
     policy_vs, value_vs = mk(cfg.policy_v_hdim, cfg.policy_v_net, cfg.policy_v_net_param), mk(cfg.value_v_hdim, cfg.value_v_net, cfg.value_v_net_param)
@@ -499,13 +482,9 @@ def main(argv=None):
 
 def _wild_stats(cfg, args):
     """eval_pose_wild.py --mode stats: the 2D keypoint distance and the smoothness of the saved wild results."""
-    import yaml
     from . import pose2d
     from .statereg import StateRegConfig
-    with open("%s/meta/meta_%s.yml" % (cfg.data_dir, args.test_feat)) as f:
-        meta = yaml.safe_load(f)
-    pose_ctx = pose2d.Pose2DContext()
-    loader = pose2d.file_keypoint_loader(cfg.data_dir, pose_ctx)
+    meta, pose_ctx, loader = pose2d.wild_stats_front(cfg, args.test_feat)
     jobs = [("ego mimic", "%s/iter_%04d_%s.p" % (cfg.result_dir, args.iter, args.test_feat))]
     if args.statereg_cfg is not None:
         sr_cfg = StateRegConfig(args.statereg_cfg, create_dirs=False)

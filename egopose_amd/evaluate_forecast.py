@@ -8,36 +8,38 @@ windows run here as the slots of `env.batched(N)` in strict lockstep, in passes 
 
     record qpos -> [observation -> frozen normalisation -> state-LSTM cell -> MLP -> mean action] -> env-step
 
-with the bracket one launch (`FusedForecastPolicy.with_filter(..., workspace=None)`, egp_policy_forecast_filter_f32).
+with the bracket one launch (`FusedForecastPolicy.with_filter(..., workspace=None)`, egp_policy_forecast_filter_f32). The pass
+around it -- slots, frozen filter state, records, env-step and timed wait -- is `lockstep_eval.LockstepPass`, shared with the
+ego_mimic evaluation; the plan, the launch with its LSTM state and the `failed` log are here.
 
 A window starts from the expert's state (`gt_init`) or from the ego_mimic result of the same take (ego_forecast_eval.py:107-120,
 `window_init_state`). The value nets are NOT evaluated: the reference only logs their output, which does not enter the results.
 Rendering (`--render`, `--mode vis`, `--show-noise`) and the per-step reward log (`--verbose`) are out of scope.
 
-Feature-only takes (ego_forecast_eval_wild.py): the window plan and the seat / history rows are here (`wild_window_plan`,
-`wild_window_init_state`), `ForecastEvaluator(..., cnn_feat_dict=...)` runs them -- the feature table comes from the pickle, seat and
-history from the wild ego_mimic result, there is no expert, no `sync_traj`, no `traj_orig` and no per-take head bound (`failed` is
+Feature-only takes (ego_forecast_eval_wild.py): the window plan (`wild_window_plan`: `window_plan` from another first start) and the
+seat / history rows (`wild_window_init_state`) are here, `ForecastEvaluator(..., cnn_feat_dict=...)` runs them -- the feature
+table comes from the pickle, seat and history from the wild ego_mimic result, there is no expert, no `sync_traj`, no `traj_orig` and no per-take head bound (`failed` is
 only logged against the env's `fix_head_lb`, if set) -- and `--mode wild-stats` scores the saved results with the 2D keypoint
 metric (`egopose_amd.pose2d`). `--test-feat NAME` selects this path.
 """
 from __future__ import annotations
 
-import os
 import pickle
-import time
 
 import numpy as np
 
 from . import metrics
+from .lockstep_eval import LockstepPass, Timing, check_frozen_filter
 
 
 # ---------------------------------------------------------------------- ego_forecast_eval.py:185-196
-def window_plan(take_lens, fr_margin, test_len):
-    """(take_ind[W], start_ind[W]) of every evaluated window: per take start = m, 2m, ... while start + test_len <= take_len."""
+def window_plan(take_lens, fr_margin, test_len, first_start=None):
+    """(take_ind[W], start_ind[W]) of every evaluated window: per take start = m, 2m, ... while start + test_len <= take_len
+    (`first_start`: another first start than m)."""
     m, test_len = int(fr_margin), int(test_len)
     take_ind, start_ind = [], []
     for i, take_len in enumerate(take_lens):
-        start = m
+        start = m if first_start is None else int(first_start)
         while start + test_len <= int(take_len):
             take_ind.append(i)
             start_ind.append(start)
@@ -77,15 +79,7 @@ def window_init_state(expert_qpos, expert_qvel, start, fr_margin, test_len, em_t
 def wild_window_plan(take_lens, fr_margin, em_margin, test_len):
     """(take_ind[W], start_ind[W]) of the windows of feature-only takes: per take start = m + em_m, m + em_m + m, ... while
     start + test_len <= take_len (take_len = rows of the take's feature array, em_m = the ego_mimic config's fr_margin)."""
-    m, em_m, test_len = int(fr_margin), int(em_margin), int(test_len)
-    take_ind, start_ind = [], []
-    for i, take_len in enumerate(take_lens):
-        start = m + em_m
-        while start + test_len <= int(take_len):
-            take_ind.append(i)
-            start_ind.append(start)
-            start += m
-    return np.asarray(take_ind, dtype=np.int64), np.asarray(start_ind, dtype=np.int64)
+    return window_plan(take_lens, fr_margin, test_len, int(fr_margin) + int(em_margin))
 
 
 # ---------------------------------------------------------------------- ego_forecast_eval_wild.py:102-120
@@ -125,8 +119,7 @@ class ForecastEvaluator:
             raise ValueError("feature-only takes have no expert: no gt_init, and an env without experts")
         if not gt_init and em_res is None:
             raise ValueError("ego_mimic results (em_res) are needed unless gt_init")
-        if running_state is not None and not (running_state.demean and running_state.destd):
-            raise NotImplementedError("running_state without demean / destd")
+        check_frozen_filter(running_state)
         self.cfg, self.env = cfg, env
         self.policy_net, self.policy_vs_net = policy_net, policy_vs_net
         self.running_state = running_state
@@ -142,38 +135,33 @@ class ForecastEvaluator:
         policy_vs_net.set_mode("test")
 
     # ------------------------------------------------------------------ host side of a run: plan, seat states, history rows
-    def plan(self, takes=None):
-        cfg, env = self.cfg, self.env
-        m, T = int(cfg.fr_margin), int(cfg.env_episode_len)
+    def _names_and_features(self):
+        return (self.take_names, self.cnn_feat) if self.wild else (self.env.expert_list, self.env.cnn_feat)
+
+    def _window_state(self, e, s, m, T):
+        """(qpos, qvel, history, miss_len) of the window at frame `s` of take `e`."""
         if self.wild:
-            return self._wild_plan(takes, m, T)
-        take_ind, start_ind = window_plan([c.shape[0] if takes is None or env.expert_list[i] in takes else 0 for i, c in enumerate(env.cnn_feat)], m, T)
+            take = self.take_names[e]
+            return wild_window_init_state(self.em_res["traj_pred"][take], self.em_res["vel_pred"][take], s, m, self.em_off, T) + (0,)
+        env = self.env
+        ex, take = env.expert_arr[e], env.expert_list[e]
+        if s + T > ex["qpos"].shape[0]:
+            raise ValueError("take %s: the expert has fewer frames than the features" % take)
+        em_t, em_v = (None, None) if self.gt_init else (self.em_res["traj_pred"][take], self.em_res["vel_pred"][take])
+        return window_init_state(ex["qpos"], ex["qvel"], s, m, T, em_t, em_v, self.em_off)
+
+    def plan(self, takes=None):
+        m, T = int(self.cfg.fr_margin), int(self.cfg.env_episode_len)
+        names, feats = self._names_and_features()
+        take_ind, start_ind = window_plan([c.shape[0] if takes is None or names[i] in takes else 0 for i, c in enumerate(feats)], m, T,
+                                          m + self.em_off if self.wild else None)
         W = len(take_ind)
-        nq, nv = env.skel.nq, env.skel.nv
+        nq, nv = self.env.skel.nq, self.env.skel.nv
         qpos0, qvel0, hist = np.empty((W, nq)), np.empty((W, nv)), np.empty((W, m, nq))
         miss = np.zeros(W, np.int64)
         for w, (e, s) in enumerate(zip(take_ind, start_ind)):
-            ex = env.expert_arr[e]
-            if s + T > ex["qpos"].shape[0]:
-                raise ValueError("take %s: the expert has fewer frames than the features" % env.expert_list[e])
-            if self.gt_init:
-                em_t = em_v = None
-            else:
-                take = env.expert_list[e]
-                em_t, em_v = self.em_res["traj_pred"][take], self.em_res["vel_pred"][take]
-            qpos0[w], qvel0[w], hist[w], miss[w] = window_init_state(ex["qpos"], ex["qvel"], s, m, T, em_t, em_v, self.em_off)
+            qpos0[w], qvel0[w], hist[w], miss[w] = self._window_state(e, s, m, T)
         return take_ind, start_ind, qpos0, qvel0, hist, miss
-
-    def _wild_plan(self, takes, m, T):
-        names, nq, nv = self.take_names, self.env.skel.nq, self.env.skel.nv
-        take_ind, start_ind = wild_window_plan([c.shape[0] if takes is None or names[i] in takes else 0 for i, c in enumerate(self.cnn_feat)],
-                                               m, self.em_off, T)
-        W = len(take_ind)
-        qpos0, qvel0, hist = np.empty((W, nq)), np.empty((W, nv)), np.empty((W, m, nq))
-        for w, (e, s) in enumerate(zip(take_ind, start_ind)):
-            em_t, em_v = self.em_res["traj_pred"][names[e]], self.em_res["vel_pred"][names[e]]
-            qpos0[w], qvel0[w], hist[w] = wild_window_init_state(em_t, em_v, s, m, self.em_off, T)
-        return take_ind, start_ind, qpos0, qvel0, hist, np.zeros(W, np.int64)
 
     # ------------------------------------------------------------------ ego_forecast_eval.py:95-204, batched
     def run(self, takes=None):
@@ -182,23 +170,21 @@ class ForecastEvaluator:
         from . import policy_step
         cfg, env = self.cfg, self.env
         m, T = int(cfg.fr_margin), int(cfg.env_episode_len)
-        t_all = time.time()
+        tm = Timing()
         take_ind, start_ind, qpos0, qvel0, hist, miss = self.plan(takes)
-        W = len(take_ind)
+        W = tm["windows"] = len(take_ind)
         N = self.num_envs
-        sim = env.batched(N, self.device_index, self.n_threads, 1)
-        ctx, eng, ex = sim.ctx, sim.engine, sim.experts
+        lp = LockstepPass(env, N, self.device_index, self.n_threads, self.running_state, T, tm, record_qvel=self.keep_trace)
+        ctx, eng, dev, ex = lp.ctx, lp.eng, lp.dev, lp.sim.experts
         if self.wild:
             from .expert import ExpertSet
             ex = ExpertSet.features_only(self.cnn_feat)
-        names = self.take_names if self.wild else env.expert_list
-        dev = torch.device("cuda", ctx.device)
+        names = self._names_and_features()[0]
         vs = self.policy_vs_net
         if not policy_step.supported_forecast(self.policy_net, vs):
             raise NotImplementedError("the forecast evaluation needs the HIP policy step: a float32 PolicyGaussian over an MLP behind a "
                                       "VideoForecastNet with an LSTMCell state net")
         nq, nv, nu, od = ctx.nq, ctx.nv, ctx.nu, ctx.obs_dim
-        f64 = torch.float64
         pred = np.empty((W, m + T, nq))
         orig = None if self.wild else np.empty((W, m + T, nq))
         for w, (e, s) in enumerate(zip(take_ind, start_ind)):
@@ -207,23 +193,14 @@ class ForecastEvaluator:
         pred[:, :m] = hist
         failed = np.zeros(W, bool)
         tr_act, tr_st, tr_qv = (np.empty((W, T, nu)), np.empty((W, T, od)), np.empty((W, T, nv))) if self.keep_trace else (None, None, None)
-        tm = {"phys_wait": 0.0, "passes": 0, "windows": W, "ticks": 0}
         with torch.no_grad(), torch.cuda.device(dev):
             fused = policy_step.FusedForecastPolicy(self.policy_net, vs, dev)
             vs.attach_feature_table(ex.cnn_table(dev, torch.float32), ex.cnn_offset)
             vs.check_windows(take_ind, start_ind, 0)
-            zf_in, clip = None, 0.0
-            if self.running_state is not None:
-                zf_in, clip = self.running_state.to_device_state(dev), float(self.running_state.clip or 0.0)
-            traj = torch.zeros(T, N, nq, dtype=f64, device=dev)
-            qv = torch.zeros(T, N, nv, dtype=f64, device=dev) if self.keep_trace else None
-            actions = torch.zeros(T, N, nu, dtype=f64, device=dev)
-            states = torch.zeros(T, N, od, dtype=f64, device=dev)
             v_out = torch.zeros(N, 1, vs.v_hdim, dtype=torch.float32, device=dev)
             h = torch.zeros(N, vs.s_hdim, dtype=torch.float32, device=dev)
             c = torch.zeros_like(h)
             t_idx = torch.zeros(N, dtype=torch.int64, device=dev)
-            phase = torch.arange(T, dtype=torch.int32, device=dev).unsqueeze(1).expand(T, N).contiguous() if ctx.obs_phase else None
             lb = ex.head_height_lb            # (feature-only takes: None)
             fix_lb = getattr(env, "fix_head_lb", None) if self.wild else None
             # the windows' video contexts, as LockstepRollout._draw_episodes computes them for forecast episodes: in batches whose
@@ -234,43 +211,27 @@ class ForecastEvaluator:
                 sl = slice(w0, min(W, w0 + self.CTX_BATCH))
                 e_d, s_d = torch.as_tensor(take_ind[sl], device=dev), torch.as_tensor(start_ind[sl], device=dev)
                 ctx_all[sl] = vs.context(vs.window_features(e_d, s_d))
+
+            def launch(t, k):
+                fused.with_filter(ctx, v_out[:k], t_idx[:k], eng.qpos[:k], eng.qvel[:k], lp.zf_in, None, lp.clip, lp.states[t, :k], None, None,
+                                  h[:k], c[:k], lp.actions[t, :k], phase_t=lp.phase_t(t))
+
             for w0 in range(0, W, N):
                 k = min(N, W - w0)
                 sl = slice(w0, w0 + k)
-                ids = np.arange(k)
-                q0, v0 = qpos0[sl], qvel0[sl]
-                if w0 == 0 and k < N:             # slots no window ever lands on: a valid state all the same (they are never stepped)
-                    ids = np.arange(N)
-                    q0, v0 = np.concatenate((q0, np.repeat(q0[:1], N - k, 0))), np.concatenate((v0, np.repeat(v0[:1], N - k, 0)))
-                eng.reset(ids, q0, v0)
+                lp.seat(qpos0[sl], qvel0[sl])
                 h.zero_(); c.zero_()
                 v_out[:k, 0] = ctx_all[sl]
-                active = np.zeros(N, np.int32)
-                active[:k] = 1
                 for t in range(T):
-                    traj[t, :k].copy_(eng.qpos[:k])
-                    if qv is not None:
-                        qv[t, :k].copy_(eng.qvel[:k])
-                    fused.with_filter(ctx, v_out[:k], t_idx[:k], eng.qpos[:k], eng.qvel[:k], zf_in, None, clip, states[t, :k], None, None,
-                                      h[:k], c[:k], actions[t, :k], phase_t=None if phase is None else phase[t, :k])
-                    ev = torch.cuda.Event()
-                    ev.record()
-                    eng.step_async(0, actions[t], active, ev)
-                    t0 = time.time()
-                    eng.wait(0)
-                    tm["phys_wait"] += time.time() - t0
+                    lp.tick(t, launch)
                     if lb is not None:
                         failed[sl] |= np.asarray(eng.head_z[:k]) < lb[take_ind[sl]] - 0.1      # (logged only: the window runs on)
                     elif fix_lb is not None:
                         failed[sl] |= np.asarray(eng.head_z[:k]) < fix_lb
-                torch.cuda.synchronize(dev)
-                pred[sl, m:] = traj[:, :k].transpose(0, 1).cpu().numpy()
                 if self.keep_trace:
-                    tr_act[sl] = actions[:, :k].transpose(0, 1).cpu().numpy()
-                    tr_st[sl] = states[:, :k].transpose(0, 1).cpu().numpy()
-                    tr_qv[sl] = qv[:, :k].transpose(0, 1).cpu().numpy()
-                tm["passes"] += 1
-                tm["ticks"] += T
+                    pred[sl, m:], tr_act[sl], tr_st[sl], tr_qv[sl] = lp.copy_out(T, "traj", "actions", "states", "qvel")
+                else:
+                    pred[sl, m:], = lp.copy_out(T, "traj")
         if self.logger is not None:
             for w in np.nonzero(failed)[0]:
                 self.logger.info("fail - expert_ind: %d, start_ind %d" % (take_ind[w], start_ind[w]))
@@ -285,19 +246,14 @@ class ForecastEvaluator:
         self.miss_len = miss
         if self.keep_trace:
             self.trace = dict(actions=tr_act, states=tr_st, qvel=tr_qv, take_ind=take_ind, start_ind=start_ind)
-        tm["total"] = time.time() - t_all
-        tm["rest"] = tm["total"] - tm["phys_wait"]
+        tm.close()
         self.timing = tm
         if self.wild:
             return {"traj_pred": traj_pred}, {"algo": "ego_forecast"}
         return {"traj_pred": traj_pred, "traj_orig": traj_orig}, {"algo": "ego_forecast"}
 
     def save(self, results, meta, it, data="test"):
-        path = result_path(self.cfg, it, data, self.gt_init)
-        os.makedirs(os.path.dirname(path), exist_ok=True)
-        with open(path, "wb") as f:
-            pickle.dump((results, meta), f)
-        return path
+        return metrics.save_results(result_path(self.cfg, it, data, self.gt_init), results, meta)
 
 
 def build_parser():
@@ -318,15 +274,12 @@ def build_parser():
 
 def _wild_stats(cfg, args):
     """eval_forecast_wild.py --mode stats on the saved forecast results of feature-only takes."""
-    import yaml
     from . import pose2d
-    with open("%s/meta/meta_%s.yml" % (cfg.data_dir, args.test_feat)) as f:
-        meta = yaml.safe_load(f)
-    pose_ctx = pose2d.Pose2DContext()
+    meta, pose_ctx, loader = pose2d.wild_stats_front(cfg, args.test_feat)
     with open("%s/iter_%04d_%s.p" % (cfg.result_dir, args.iter, args.test_feat), "rb") as f:
         res, _ = pickle.load(f)
-    return pose2d.eval_forecast_wild_stats(res, meta, pose2d.file_keypoint_loader(cfg.data_dir, pose_ctx), cfg, horizon=args.horizon,
-                                           backend="host" if args.host else "hip", pose_ctx=pose_ctx, verbose=True, device_index=args.gpu_index)
+    return pose2d.eval_forecast_wild_stats(res, meta, loader, cfg, horizon=args.horizon, backend="host" if args.host else "hip",
+                                           pose_ctx=pose_ctx, verbose=True, device_index=args.gpu_index)
 
 
 def main(argv=None):
@@ -336,6 +289,7 @@ def main(argv=None):
     import torch
     from .config import Config as EgoMimicConfig, ForecastConfig
     from .env import HumanoidEnv
+    from .evaluate_wild import cli_takes
     from .nets import MLP, PolicyGaussian, VideoForecastNet
     from .zfilter import load_reference_pickle
     args = build_parser().parse_args(argv)
@@ -349,14 +303,8 @@ def main(argv=None):
     dev = torch.device("cuda", args.gpu_index)
     env = HumanoidEnv(cfg)
     env.seed(cfg.seed)
-    cnn_feat_dict, data = None, args.data
-    if args.test_feat is not None:                 # ego_forecast_eval_wild.py:40-43: no experts
-        from .evaluate_wild import load_features
-        cnn_feat_dict, data = load_features(cfg, args.test_feat), args.test_feat
-        cnn_dim = next(iter(cnn_feat_dict.values())).shape[-1]
-    else:
-        env.load_experts(cfg.takes[args.data], cfg.expert_feat_file, cfg.cnn_feat_file)
-        cnn_dim = env.cnn_feat[0].shape[-1]
+    cnn_feat_dict, cnn_dim = cli_takes(cfg, env, args.data, args.test_feat)
+    data = args.data if args.test_feat is None else args.test_feat
     sd, ad = env.observation_space.shape[0], env.action_space.shape[0]
     policy_vs = VideoForecastNet(cnn_dim, sd, cfg.policy_v_hdim, cfg.fr_margin, cfg.policy_v_net, cfg.policy_v_net_param, cfg.policy_s_hdim,
                                  cfg.policy_s_net, cfg.policy_dyn_v)

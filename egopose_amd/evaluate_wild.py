@@ -1,7 +1,7 @@
 """ego_mimic on feature-only takes: videos that have CNN features but no MoCap, hence no expert (ego_pose/ego_mimic_eval_wild.py:85-155).
 
 The takes are the keys of `<data_dir>/features/cnn_feat_<test_feat>.p`, in that order. Per take the video contexts and the state
-regressor's predictions are computed once, at batch 1 (`BatchedEvaluator._feature_tables`); the humanoid is reset to the model's rest
+regressor's predictions are computed once, at batch 1 (`evaluate.regressor_states`); the humanoid is reset to the model's rest
 pose one metre up (`HumanoidEnv.reset()` without experts) and seated on `state_pred[0]` aligned to that pose; every tick takes the
 mean action, and the `valuefs` rule -- value below 0.6 x the running mean over all values of all takes, in take order -- is the only
 fail-safe. There is no `info['end']` break: the loop runs `test_len = len - 2 * fr_margin` ticks and the decision is also taken on
@@ -9,16 +9,15 @@ the last one. The reference then indexes `state_pred[t + 1]` with t = test_len -
 fires there); here that one re-seat is clamped away -- no re-seat after the last tick. It cannot change `traj_pred`: the last row was
 recorded before the tick. Results: ({'traj_pred', 'vel_pred'}, {'algo': 'ego_mimic'}), saved as iter_%04d_<test_feat>.p.
 
-`WildEvaluator` goes take by take through the single-env facade (and keeps `show_noise`); `BatchedWildEvaluator` puts the takes on
+`WildEvaluator` goes take by take through the single-env facade (and keeps `show_noise`): it IS `Evaluator`'s loop
+(`Evaluator._eval_take`, which carries that clamp) with another reset and `HAS_EXPERT = False` -- no expert row, no reward, no `end`.
+`BatchedWildEvaluator` puts the takes on
 `num_envs` lockstep slots: it IS `BatchedEvaluator`'s pass (fused actor + critic step with the frozen filter, pinned value copy,
 exact speculative `valuefs` scheduling) over another kind of take. A take's result does not depend on the slot count.
 """
 from __future__ import annotations
 
 import pickle
-
-import numpy as np
-import torch
 
 from .evaluate import BatchedEvaluator, Evaluator
 
@@ -30,6 +29,16 @@ def load_features(cfg, test_feat):
     return cnn_feat_dict
 
 
+def cli_takes(cfg, env, data, test_feat):
+    """What the evaluation CLIs run on -> (cnn_feat_dict or None, the features' width): the feature-only takes of `--test-feat`
+    (ego_mimic_eval_wild.py:36-39, ego_forecast_eval_wild.py:40-43: no experts), or else the experts of `--data`, loaded into `env`."""
+    if test_feat is not None:
+        cnn_feat_dict = load_features(cfg, test_feat)
+        return cnn_feat_dict, next(iter(cnn_feat_dict.values())).shape[-1]
+    env.load_experts(cfg.takes[data], cfg.expert_feat_file, cfg.cnn_feat_file)
+    return None, env.cnn_feat[0].shape[-1]
+
+
 def _check_no_experts(env):
     if env.expert_list is not None:
         raise ValueError("the wild evaluators need an env without experts (its reset is the rest pose)")
@@ -38,6 +47,8 @@ def _check_no_experts(env):
 class WildEvaluator(Evaluator):
     """`Evaluator` over `cnn_feat_dict` = {take: features}; the env has no experts. `trace[take]`: actions, values, resets, state_pred."""
 
+    HAS_EXPERT = False
+
     def __init__(self, cfg, env, cnn_feat_dict, policy_net, policy_vs_net, value_net, value_vs_net, state_net, state_net_mean, state_net_std,
                  running_state=None, show_noise=False, logger=None, keep_trace=False):
         _check_no_experts(env)
@@ -45,50 +56,17 @@ class WildEvaluator(Evaluator):
                          running_state=running_state, fail_safe="valuefs", show_noise=show_noise, logger=logger, keep_trace=keep_trace)
         self.cnn_feat_dict = cnn_feat_dict
 
-    # ------------------------------------------------------------------ ego_mimic_eval_wild.py:94-140
-    @torch.no_grad()
-    def eval_take(self, take):
-        env, m = self.env, self.cfg.fr_margin
-        cnn_feat = torch.as_tensor(self.cnn_feat_dict[take], dtype=self.dtype, device=self.device)
-        test_len = cnn_feat.shape[0] - 2 * m
+    def _reset_to_take(self, take):
+        test_len = self.cnn_feat_dict[take].shape[0] - 2 * self.cfg.fr_margin
         if test_len < 1:
             raise ValueError("take %s: no frames between the margins" % take)
-        traj_pred, vel_pred, num_reset = [], [], 0
-        env.reset()
-        self.policy_vs_net.initialize(cnn_feat)
-        self.value_vs_net.initialize(cnn_feat)
-        sp = next(self.state_net.parameters())
-        state_pred = self.state_net(cnn_feat.to(device=sp.device, dtype=sp.dtype).unsqueeze(1))[m:-m].double().cpu().numpy()
-        state_pred = state_pred * self.state_net_std[None, :] + self.state_net_mean[None, :]
-        state = self._filter(self.reset_env_state(state_pred[0], env.data.qpos))
-        tr = None
-        if self.trace is not None:
-            tr = self.trace[take] = dict(actions=[], values=[], resets=[], state_pred=state_pred)
-        for t in range(test_len):
-            data = env.data
-            traj_pred.append(data.qpos.copy())
-            vel_pred.append(data.qvel.copy())
-            state_var = torch.as_tensor(state, dtype=self.dtype, device=self.device).unsqueeze(0)
-            policy_in = self.policy_vs_net(state_var)
-            value = float(self.value_net(self.value_vs_net(state_var)).item())
-            self.value_stat.push(np.array([value]))
-            action = self.policy_net.select_action(policy_in, mean_action=not self.show_noise)[0].double().cpu().numpy()
-            if tr is not None:
-                tr["actions"].append(action.copy())
-                tr["values"].append(value)
-            next_state, _, _, _ = env.step(action)
-            next_state = self._filter(next_state)
-            if value < 0.6 * self.value_stat.mean[0]:
-                if self.logger is not None:
-                    self.logger.info("reset state!")
-                num_reset += 1
-                if tr is not None:
-                    tr["resets"].append(t)
-                if t + 1 < test_len:               # (module docstring: the reference's state_pred[t + 1] is out of range here)
-                    state = self._filter(self.reset_env_state(state_pred[t + 1], env.data.qpos))
-            else:
-                state = next_state
-        return np.vstack(traj_pred), np.vstack(vel_pred), num_reset
+        self.env.reset()
+        return take, self.cnn_feat_dict[take], test_len
+
+    # ------------------------------------------------------------------ ego_mimic_eval_wild.py:94-140 (Evaluator._eval_take)
+    def eval_take(self, take):
+        traj_pred, _, vel_pred, num_reset = self._eval_take(take)
+        return traj_pred, vel_pred, num_reset
 
     # ------------------------------------------------------------------ ego_mimic_eval_wild.py:147-156
     def run(self, takes=None):

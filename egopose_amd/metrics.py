@@ -209,3 +209,13 @@ def remove_noisy_hands(results):
         for take in traj.keys():
             traj[take][..., 32:35] = 0
             traj[take][..., 42:45] = 0
+
+
+def save_results(path, results, meta):
+    """The `(results, meta)` pickle every evaluation writes and `compute_metrics` / the `--mode stats` CLIs read -> path."""
+    import os
+    import pickle
+    os.makedirs(os.path.dirname(path), exist_ok=True)
+    with open(path, "wb") as f:
+        pickle.dump((results, meta), f)
+    return path

@@ -166,6 +166,16 @@ def file_keypoint_loader(data_dir, pose_ctx):
     return lambda take, gt_fr: pose_ctx.load_gt_pose("%s/tpv/poses/%s/%05d_keypoints.json" % (data_dir, take, gt_fr))
 
 
+def wild_stats_front(cfg, test_feat):
+    """What `--mode wild-stats` of both evaluation CLIs starts from -> (the takes' meta of <data_dir>/meta/meta_<test_feat>.yml,
+    a Pose2DContext, the keypoint loader over it)."""
+    import yaml
+    with open("%s/meta/meta_%s.yml" % (cfg.data_dir, test_feat)) as f:
+        meta = yaml.safe_load(f)
+    pose_ctx = Pose2DContext()
+    return meta, pose_ctx, file_keypoint_loader(cfg.data_dir, pose_ctx)
+
+
 def context_of(cfg, skel=None, device_index=0):
     """An EgpContext for scoring alone (the model constants of `cfg`, no engine, no experts)."""
     from .hip import EgpContext, obs_options_of

@@ -348,15 +348,11 @@ def main(argv=None):
         with open("%s/features/cnn_feat_%s.p" % (ds.base_folder, args.test_feat), "rb") as f:
             cnn_feat_dict, _ = pickle.load(f)
         results, meta = tr.test_features(cnn_feat_dict)
-        path = "%s/iter_%04d_%s.p" % (cfg.result_dir, args.iter, args.test_feat)
-        with open(path, "wb") as f:
-            pickle.dump((results, meta), f)
+        path = M.save_results("%s/iter_%04d_%s.p" % (cfg.result_dir, args.iter, args.test_feat), results, meta)
         print("nsample %d\nsaved results to %s" % (meta["num_sample"], path))
     elif args.mode == "test":
         results, meta = tr.test()
-        path = "%s/iter_%04d_%s.p" % (cfg.result_dir, args.iter, data)
-        with open(path, "wb") as f:
-            pickle.dump((results, meta), f)
+        path = M.save_results("%s/iter_%04d_%s.p" % (cfg.result_dir, args.iter, data), results, meta)
         print("nsample %d   loss %.4f\nsaved results to %s" % (meta["num_sample"], meta["epoch_loss"], path))
     else:
         tr.save("%s/iter_%04d_inf.p" % (cfg.model_dir, args.iter), inference=True)

@@ -144,11 +144,15 @@ def test_results_do_not_depend_on_the_slot_count(run8):
     ev5 = _evaluator(tr, cfg, 5, gt_init=True)
     r5, _ = ev5.run()
     assert ev5.timing["passes"] == 6
-    for take in results["traj_pred"]:
-        np.testing.assert_array_equal(r5["traj_pred"][take], results["traj_pred"][take])
-        np.testing.assert_array_equal(r5["traj_orig"][take], results["traj_orig"][take])
-    np.testing.assert_array_equal(ev5.trace["actions"], ev.trace["actions"])
-    np.testing.assert_array_equal(ev5.trace["states"], ev.trace["states"])
+    ev32 = _evaluator(tr, cfg, 32, gt_init=True)       # more slots than windows: the one pass leaves five slots without a window
+    r32, _ = ev32.run()
+    assert ev32.timing["passes"] == 1
+    for evn, rn in ((ev5, r5), (ev32, r32)):
+        for take in results["traj_pred"]:
+            np.testing.assert_array_equal(rn["traj_pred"][take], results["traj_pred"][take])
+            np.testing.assert_array_equal(rn["traj_orig"][take], results["traj_orig"][take])
+        np.testing.assert_array_equal(evn.trace["actions"], ev.trace["actions"])
+        np.testing.assert_array_equal(evn.trace["states"], ev.trace["states"])
 
 
 def test_ego_mimic_based_start(run8):

@@ -97,16 +97,18 @@ def test_env_without_experts_resets_to_the_rest_pose(setup, skel):
 def test_results_do_not_depend_on_the_slot_count(setup):
     ev2, r2, m2 = _batched(setup, 2)
     ev3, r3, m3 = _batched(setup, 3)
-    assert m2 == m3 == {"algo": "ego_mimic"} and set(r2) == {"traj_pred", "vel_pred"}
+    ev5, r5, m5 = _batched(setup, 5)                   # more slots than takes: the first pass leaves two slots without a take
+    assert m2 == m3 == m5 == {"algo": "ego_mimic"} and set(r2) == {"traj_pred", "vel_pred"}
     assert list(r2["traj_pred"]) == list(LENS) and ev3.timing["passes"] < ev2.timing["passes"]
     for take, n in LENS.items():
         assert r2["traj_pred"][take].shape == (n - 20, 59) and r2["vel_pred"][take].shape == (n - 20, 58)
-        for k in ("traj_pred", "vel_pred"):
-            np.testing.assert_array_equal(r2[k][take], r3[k][take])
-        a, b = ev2.trace[take], ev3.trace[take]
-        for k in ("actions", "values", "states"):
-            np.testing.assert_array_equal(a[k], b[k])
-        assert list(a["resets"]) == list(b["resets"])
+        for evn, rn in ((ev3, r3), (ev5, r5)):
+            for k in ("traj_pred", "vel_pred"):
+                np.testing.assert_array_equal(r2[k][take], rn[k][take])
+            a, b = ev2.trace[take], evn.trace[take]
+            for k in ("actions", "values", "states"):
+                np.testing.assert_array_equal(a[k], b[k])
+            assert list(a["resets"]) == list(b["resets"])
     # the first seat: state_pred[0] on the rest pose's position and heading
     first = r2["traj_pred"]["wild_c"][0]
     np.testing.assert_array_equal(first[:2], setup["env"].rest_qpos()[:2])
