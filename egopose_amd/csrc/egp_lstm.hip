@@ -13,6 +13,8 @@
 //             activated gates [T][B][4H] and cell states [T][B][H]
 //   backward: d h_out, saved gates / cells  ->  d gates_pre [T][B][4H] (what the weight-gradient GEMMs and
 //             the bias reduction consume); the recurrent term dgates W_hh stays in the kernel
+//   windows : gates_x [frames][4H] of ONE table, seq_base [B]  ->  out [B][H], the state after `steps` steps of each window
+//             (the forward kernel in its store mode LSTM_ST_LAST: the online evaluation's backward direction, one launch per take)
 // Gate order i, f, g, o as torch.nn.LSTMCell. Sequences start from zero state (as the reference does).
 #include <hip/hip_runtime.h>
 #include <math.h>
@@ -138,9 +140,16 @@ __device__ long long g_lstm_trace[8];
 #ifndef EGP_LSTM_BKCH
 #define EGP_LSTM_BKCH 64
 #endif
-template <int NQ, int LH, bool FULL, bool TRAIN>
+// STORE = what a step leaves in memory. LSTM_ST_STEP: h_out at every step (inference). LSTM_ST_TRAIN: h_out and the save-set
+// (activated gates, cell states). LSTM_ST_LAST: nothing per step -- only the hidden state after the last step, one row per
+// sequence at h_out + b * ld_h (egp_lstm_window_last_f32: inference over windows of a frame table). The step itself is the same
+// code. (One parameter with three values, in the place `bool TRAIN` had: what parses k_lstm_fwd_mfma<NQ, LH, FULL, x> in a
+// profiler's kernel names -- tests/test_lstm_reference_gpu.py -- still finds four arguments, x = 0 / 1 for the per-step sweeps.)
+constexpr int LSTM_ST_STEP = 0, LSTM_ST_TRAIN = 1, LSTM_ST_LAST = 2;
+template <int NQ, int LH, bool FULL, int STORE>
 __global__ __launch_bounds__(4 * LH) void k_lstm_fwd_mfma(const float *__restrict__ gx, const float *__restrict__ w_hh, int T, int B,
                                                           LstmGroup grp, float *__restrict__ gates_out, float *__restrict__ c_out) {
+    constexpr bool TRAIN = STORE == LSTM_ST_TRAIN, LAST = STORE == LSTM_ST_LAST;
     constexpr int LG = 4 * LH, ROWS = 4 * NQ;
     // Workgroups are dispatched x first, then y, and a grouped launch is a few rounds of the chip (1 100 workgroups on 768 / 512
     // slots at the update's shapes): the LAST problems' workgroups form the tail. The callers put the forward-running problems
@@ -159,13 +168,13 @@ __global__ __launch_bounds__(4 * LH) void k_lstm_fwd_mfma(const float *__restric
     float w[LH];
 #pragma unroll
     for (int k = 0; k < LH; ++k) w[k] = w_hh[(long)(sub * LH + u) * LH + k];
-    float cst[NQ];
+    float cst[NQ], hlast[NQ];
     f32x4 pre[PD][NQ];
     bool live[NQ];
     int rowc[NQ];               // row to read: a missing row of a ragged last tile reads the last real row instead
 #pragma unroll
     for (int q = 0; q < NQ; ++q) {
-        cst[q] = 0.f;
+        cst[q] = 0.f; hlast[q] = 0.f;
         live[q] = FULL || r0 + 4 * q + sub < B;
         const int pos = live[q] ? r0 + 4 * q + sub : B - 1;
         rowc[q] = grp.order ? grp.order[pos] : pos;
@@ -226,7 +235,9 @@ __global__ __launch_bounds__(4 * LH) void k_lstm_fwd_mfma(const float *__restric
             const float hn = og * tanhf_(cn);
             cst[q] = cn;
             s_h[par ^ 1][4 * q + sub][u] = hn;
-            if (FULL || live[q]) {
+            if constexpr (LAST) {
+                hlast[q] = hn;
+            } else if (FULL || live[q]) {
                 const long row = (long)t * B + rowc[q];
                 h_out[row * ld_h + u] = hn;
                 if (TRAIN) {
@@ -272,6 +283,12 @@ __global__ __launch_bounds__(4 * LH) void k_lstm_fwd_mfma(const float *__restric
     }
 #undef EGP_LSTM_FETCH_GX
     EGP_LT_END(Tp);
+    if constexpr (LAST) {                  // the one store per row: its state after the last step
+#pragma unroll
+        for (int q = 0; q < NQ; ++q)
+            if (FULL || live[q]) h_out[(long)rowc[q] * ld_h + u] = hlast[q];
+        return;
+    }
     // the steps a ragged forward-running workgroup skipped: zeros (a weight gradient multiplies these rows with a zero d_pre,
     // and 0 * whatever an uninitialised buffer holds may be NaN)
     // (leave_skipped: zeros only up to the longest sequence of the aligned group of 8 positions -- the granularity of the
@@ -469,21 +486,23 @@ static int lstm_launch_check(const char *what) {
 }
 
 template <int NQ, int LH>
-static void launch_fwd_mfma_t(bool full, bool train, int P, const float *gx, const float *w_hh, int T, int B, const LstmGroup &g,
+static void launch_fwd_mfma_t(bool full, bool train, bool last, int P, const float *gx, const float *w_hh, int T, int B, const LstmGroup &g,
                               float *gates_save, float *cells_save, hipStream_t s) {
     const dim3 grid((B + 4 * NQ - 1) / (4 * NQ), P), block(4 * LH);
-    if (full && train) k_lstm_fwd_mfma<NQ, LH, true, true><<<grid, block, 0, s>>>(gx, w_hh, T, B, g, gates_save, cells_save);
-    else if (full) k_lstm_fwd_mfma<NQ, LH, true, false><<<grid, block, 0, s>>>(gx, w_hh, T, B, g, gates_save, cells_save);
-    else if (train) k_lstm_fwd_mfma<NQ, LH, false, true><<<grid, block, 0, s>>>(gx, w_hh, T, B, g, gates_save, cells_save);
-    else k_lstm_fwd_mfma<NQ, LH, false, false><<<grid, block, 0, s>>>(gx, w_hh, T, B, g, gates_save, cells_save);
+    if (last && full) k_lstm_fwd_mfma<NQ, LH, true, LSTM_ST_LAST><<<grid, block, 0, s>>>(gx, w_hh, T, B, g, nullptr, nullptr);
+    else if (last) k_lstm_fwd_mfma<NQ, LH, false, LSTM_ST_LAST><<<grid, block, 0, s>>>(gx, w_hh, T, B, g, nullptr, nullptr);
+    else if (full && train) k_lstm_fwd_mfma<NQ, LH, true, LSTM_ST_TRAIN><<<grid, block, 0, s>>>(gx, w_hh, T, B, g, gates_save, cells_save);
+    else if (full) k_lstm_fwd_mfma<NQ, LH, true, LSTM_ST_STEP><<<grid, block, 0, s>>>(gx, w_hh, T, B, g, gates_save, cells_save);
+    else if (train) k_lstm_fwd_mfma<NQ, LH, false, LSTM_ST_TRAIN><<<grid, block, 0, s>>>(gx, w_hh, T, B, g, gates_save, cells_save);
+    else k_lstm_fwd_mfma<NQ, LH, false, LSTM_ST_STEP><<<grid, block, 0, s>>>(gx, w_hh, T, B, g, gates_save, cells_save);
 }
 static void launch_fwd_mfma(int hidden, int P, const float *gx, const float *w_hh, int T, int B, const LstmGroup &g,
-                            float *gates_save, float *cells_save, hipStream_t s) {
+                            float *gates_save, float *cells_save, hipStream_t s, bool last = false) {
     const int nq = hidden == 64 ? lstm_quads(B) : 1;      // (4-row workgroups also win for grouped launches: measured)
     const bool full = B % (4 * nq) == 0, train = gates_save != nullptr;
-    if (hidden == 128) launch_fwd_mfma_t<1, 128>(full, train, P, gx, w_hh, T, B, g, gates_save, cells_save, s);
-    else if (nq >= 2) launch_fwd_mfma_t<2, 64>(full, train, P, gx, w_hh, T, B, g, gates_save, cells_save, s);
-    else launch_fwd_mfma_t<1, 64>(full, train, P, gx, w_hh, T, B, g, gates_save, cells_save, s);
+    if (hidden == 128) launch_fwd_mfma_t<1, 128>(full, train, last, P, gx, w_hh, T, B, g, gates_save, cells_save, s);
+    else if (nq >= 2) launch_fwd_mfma_t<2, 64>(full, train, last, P, gx, w_hh, T, B, g, gates_save, cells_save, s);
+    else launch_fwd_mfma_t<1, 64>(full, train, last, P, gx, w_hh, T, B, g, gates_save, cells_save, s);
 }
 
 template <int NQ, int LH>
@@ -581,6 +600,19 @@ int egp_lstm_group_fwd_len_f32(const float *gates_x, const float *w_hh, int32_t 
     g.order = seq_order; g.steps = seq_steps; g.leave_skipped = seq_steps && leave_skipped; g.seq_base = seq_base;
     launch_fwd_mfma(hidden, n_problems, gates_x, w_hh, T, B, g, gates_save, cells_save, (hipStream_t)stream);
     return lstm_launch_check("k_lstm_fwd_mfma (group)");
+}
+
+int egp_lstm_window_last_f32(const float *gates_x, int32_t ld_g, const float *w_hh, const int32_t *seq_base, int32_t steps, int32_t B,
+                             int32_t hidden, int32_t reverse, float *out, int32_t ld_out, void *stream) {
+    EGP_REQUIRE(hidden == 64 || hidden == 128, "egp_lstm kernels are built for hidden size 64 and 128");
+    EGP_REQUIRE(steps >= 1 && B >= 0, "a window has at least one step, and no negative batch");
+    EGP_REQUIRE(ld_out >= hidden && ld_g >= 4 * hidden && ld_g % 4 == 0, "out row stride below the hidden size / projection row stride below 4H or unaligned");
+    if (B == 0) return EGP_OK;
+    EGP_REQUIRE(gates_x && w_hh && seq_base && out, "NULL pointer");
+    LstmGroup g = {};
+    g.ld_g = ld_g; g.rev_mask = reverse ? 1 : 0; g.ld_h = ld_out; g.h[0] = out; g.seq_base = seq_base;
+    launch_fwd_mfma(hidden, 1, gates_x, w_hh, steps, B, g, nullptr, nullptr, (hipStream_t)stream, true);
+    return lstm_launch_check("k_lstm_fwd_mfma (windows, last state)");
 }
 
 int egp_lstm_group_bwd_f32(const float *const *dh_out, int32_t ld_dh, const float *gates_save, const float *cells_save, const float *w_hh,

@@ -21,8 +21,14 @@ their copy-out, a tick's event / env-step / timed wait -- is `lockstep_eval.Lock
 launch, the value copy and the host decision are here. The video contexts and the state regressor's predictions of a take are
 computed once per take, at batch 1 as above (a take's result does not depend on the slot count). 'valuefs' compares against a running mean over ALL values in take
 order; `egopose_amd.failsafe` makes that exact for takes that run side by side (speculative runs, checked against the true
-statistic afterwards, re-run where a decision differs). The reward (which nothing reads) is not evaluated; `causal` and
-`show_noise` stay with `Evaluator`.
+statistic afterwards, re-run where a decision differs). The reward (which nothing reads) is not evaluated; `show_noise` stays
+with `Evaluator`, and so does `causal` as the reference wrote it (a full sweep over the prefix at every tick).
+
+`BatchedOnlineEvaluator` is the online (`--causal`) evaluation on the same slots: `BatchedEvaluator` with another policy-context table.
+The reference re-initialises the POLICY's video net at every tick on the frames seen so far (ego_mimic_eval.py:143-145), so row t of
+the table is row t + m of that net over frames [0, t + 2m] -- `VideoStateNet.online_contexts`, T + m forward steps and one launch of T
+windows of m + 1 steps per take instead of a sweep per tick. The value net and the state regressor keep their whole-take tables, as
+in the reference. `Evaluator(causal=True)`, prefix by prefix, is the yardstick it is tested against.
 
 Takes that have video features only (no MoCap, no expert): `egopose_amd.evaluate_wild` (`--test-feat NAME`), on the same pass and,
 take by take, on the same loop (`Evaluator._eval_take`). `regressor_states` is the state regressor's prediction of a take for both.
@@ -231,11 +237,16 @@ class BatchedEvaluator(_MimicEvaluator):
         m = self.cfg.fr_margin
         p = next(self.policy_net.parameters())
         cnn_feat = torch.as_tensor(cnn_feat_np, dtype=p.dtype, device=p.device)
-        self.policy_vs_net.initialize(cnn_feat)
+        pol = self._policy_contexts(cnn_feat)
         self.value_vs_net.initialize(cnn_feat)
         state_pred = regressor_states(self.state_net, self.state_net_mean, self.state_net_std, cnn_feat, m)
-        return dict(len=cnn_feat.shape[0] - 2 * m, pol=self.policy_vs_net.v_out.float().contiguous(),
+        return dict(len=cnn_feat.shape[0] - 2 * m, pol=pol.float().contiguous(),
                     val=self.value_vs_net.v_out.float().contiguous(), state_pred=state_pred)
+
+    def _policy_contexts(self, cnn_feat):
+        """[len - 2m][v_hdim]: the policy's context per tick of a take (BatchedOnlineEvaluator: the online ones)."""
+        self.policy_vs_net.initialize(cnn_feat)
+        return self.policy_vs_net.v_out
 
     def _take_tables(self, i):
         env, m = self.env, self.cfg.fr_margin
@@ -384,17 +395,35 @@ class BatchedEvaluator(_MimicEvaluator):
         return {"traj_pred": traj_pred, "traj_orig": traj_orig, "vel_pred": vel_pred}, {"algo": "ego_mimic", "num_reset": num_reset}
 
 
-def select_evaluator(policy_net, value_net, num_envs=1, sequential=False, causal=False, show_noise=False):
-    """Which evaluator `main()` uses -> (class, reason or None): BatchedEvaluator for num_envs > 1 unless something needs the
-    take-by-take path (then Evaluator, with the reason to print)."""
+class BatchedOnlineEvaluator(BatchedEvaluator):
+    """The online evaluation (ego_mimic_eval.py --causal) on lockstep slots: the policy's context at tick t is its video net over the
+    frames up to t + 2 * fr_margin only (module docstring). Everything else -- the pass, the fused launch, the fail-safe scheduler,
+    the records -- is BatchedEvaluator's; `save()` writes iter_%04d_<data>[_<fail_safe>]_causal.p."""
+
+    def __init__(self, cfg, env, policy_net, policy_vs_net, value_net, value_vs_net, state_net, state_net_mean, state_net_std,
+                 running_state=None, fail_safe="valuefs", sync=False, logger=None, keep_trace=False, num_envs=8, device_index=0,
+                 n_threads=None):
+        super().__init__(cfg, env, policy_net, policy_vs_net, value_net, value_vs_net, state_net, state_net_mean, state_net_std,
+                         running_state=running_state, fail_safe=fail_safe, sync=sync, logger=logger, keep_trace=keep_trace,
+                         num_envs=num_envs, device_index=device_index, n_threads=n_threads)
+        self.causal = True
+
+    def _policy_contexts(self, cnn_feat):
+        return self.policy_vs_net.online_contexts(cnn_feat)
+
+
+def select_evaluator(policy_net, value_net, num_envs=1, sequential=False, causal=False, show_noise=False, batched_online=False):
+    """Which evaluator `main()` uses -> (class, reason or None): BatchedEvaluator for num_envs > 1 -- BatchedOnlineEvaluator for a
+    `causal` run when the caller can take it (`batched_online`) -- unless something needs the take-by-take path (then Evaluator,
+    with the reason to print)."""
     from . import policy_step
     if sequential or int(num_envs) <= 1:
         return Evaluator, None
-    if causal or show_noise:
+    if show_noise or (causal and not batched_online):
         return Evaluator, "--causal / --show-noise run take by take"
     if not (policy_step.supported(policy_net) and policy_step.supported_value(value_net)):
         return Evaluator, "the nets are outside the fused actor + critic step (float32 PolicyGaussian and Value over plain MLPs)"
-    return BatchedEvaluator, None
+    return (BatchedOnlineEvaluator if causal else BatchedEvaluator), None
 
 
 def compute_metrics(results, dt=1.0 / 30.0, algo="ego_mimic", verbose=False):
@@ -418,7 +447,8 @@ def main(argv=None):
     ap.add_argument("--causal", action="store_true")
     ap.add_argument("--show-noise", action="store_true")
     ap.add_argument("--gpu-index", type=int, default=0)
-    ap.add_argument("--num-envs", type=int, default=1, help="> 1: takes side by side on that many env slots (BatchedEvaluator)")
+    ap.add_argument("--num-envs", type=int, default=1,
+                    help="> 1: takes side by side on that many env slots (BatchedEvaluator; with --causal BatchedOnlineEvaluator)")
     ap.add_argument("--sequential", action="store_true", help="take by take (Evaluator) whatever --num-envs says")
     ap.add_argument("--test-feat", default=None, help="evaluate the feature-only takes of datasets/features/cnn_feat_<NAME>.p (no MoCap)")
     ap.add_argument("--mode", default="eval", choices=["eval", "wild-stats"], help="wild-stats: 2D keypoint statistics of saved --test-feat results")
@@ -450,7 +480,8 @@ def main(argv=None):
     state_net.load_state_dict(sn_cp["state_net_dict"])
     for net in (policy, policy_vs, value, value_vs, state_net):
         net.to(dev, dtype)
-    cls, why = select_evaluator(policy, value, args.num_envs, args.sequential, args.causal, args.show_noise)
+    # (the feature-only takes have no online mode: the reference has none)
+    cls, why = select_evaluator(policy, value, args.num_envs, args.sequential, args.causal, args.show_noise, batched_online=cnn_feat_dict is None)
     if why is not None:
         print("falling back to the sequential Evaluator: %s" % why)
     if cnn_feat_dict is not None:
@@ -465,11 +496,11 @@ def main(argv=None):
         print("num reset: %d, saved results to %s" % (ev.num_reset, path))
         env.close()
         return
-    if cls is BatchedEvaluator:
+    if cls is not Evaluator:                           # BatchedEvaluator, or BatchedOnlineEvaluator for --causal
         if args.fail_safe == "naivefs":
             env.set_fix_head_lb(0.3)                   # ego_mimic_eval.py:51-52 (the sequential path keeps the take's own bound)
-        ev = BatchedEvaluator(cfg, env, policy, policy_vs, value, value_vs, state_net, meta["mean"], meta["std"], running_state=cp["running_state"],
-                              fail_safe=args.fail_safe, num_envs=args.num_envs, device_index=args.gpu_index)
+        ev = cls(cfg, env, policy, policy_vs, value, value_vs, state_net, meta["mean"], meta["std"], running_state=cp["running_state"],
+                 fail_safe=args.fail_safe, num_envs=args.num_envs, device_index=args.gpu_index)
     else:
         ev = Evaluator(cfg, env, policy, policy_vs, value, value_vs, state_net, meta["mean"], meta["std"], running_state=cp["running_state"],
                        fail_safe=args.fail_safe, causal=args.causal, show_noise=args.show_noise)

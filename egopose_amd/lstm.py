@@ -325,6 +325,46 @@ def lstm_group(x, cells, reverses, pairs=False, ragged=None, frames=None):
     return list(LstmGroup.apply(x.contiguous(), mask, len(cells), 2 if pairs else 1, _wants_grad(x, params), ragged, frames, *params))
 
 
+WINDOW_CALLS = 0              # launches of egp_lstm_window_last_f32 so far (tests assert which path ran)
+
+
+def window_available(table, cell):
+    """The windowed last-state kernel serves what the sweeps serve, in the unit-major gate layout."""
+    return available(table, cell) and L.load().egp_lstm_gate_layout() != 0
+
+
+@torch.no_grad()
+def window_last(cell, table, seq_base, steps, reverse, out):
+    """Hidden state of `cell` after `steps` steps from zero over each window of consecutive frames of `table` (F, D): window b =
+    frames seq_base[b] .. seq_base[b] + steps - 1, walked from its last frame to its first when `reverse`
+    (egp_lstm_window_last_f32, include/egopose_hip.h). The input projection runs over the table's F rows once, whatever the
+    windows share. `out`: (B, H) float32 rows to write, row stride free (a column block of a wider table). Inference only."""
+    global WINDOW_CALLS
+    H, B = cell.hidden_size, seq_base.shape[0]
+    if not (table.dim() == 2 and table.is_contiguous() and window_available(table, cell)):
+        raise ValueError("window_last needs a contiguous float32 (F, D) table on the device and an LSTMCell of hidden size 64 or 128")
+    if not (seq_base.is_cuda and seq_base.dtype == torch.int32 and seq_base.dim() == 1 and seq_base.is_contiguous()):
+        raise ValueError("seq_base must be a contiguous int32 device vector")
+    if not (out.is_cuda and out.dtype == torch.float32 and out.shape == (B, H) and (H == 1 or out.stride(1) == 1)
+            and (B <= 1 or out.stride(0) >= H)):
+        raise ValueError("out must be float32 (B, H) = (%d, %d) device rows, got %s" % (B, H, tuple(out.shape)))
+    if steps < 1:
+        raise ValueError("a window has at least one step, got %d" % steps)
+    if B == 0:
+        return out
+    lo, hi = int(seq_base.min()), int(seq_base.max())             # the kernel trusts the windows: keep them inside the table
+    if lo < 0 or hi + steps > table.shape[0]:
+        raise ValueError("windows [%d, %d) leave the table's %d frames" % (lo, hi + steps, table.shape[0]))
+    perm, _ = _gate_perm(H, table.device)
+    w_in, bias = cell.weight_ih.index_select(0, perm), (cell.bias_ih + cell.bias_hh).index_select(0, perm)
+    gx = G.linear_fwd(table, w_in.contiguous(), bias) if G.enabled() else torch.addmm(bias, table, w_in.t())      # (F, 4H)
+    L.check(L.load().egp_lstm_window_last_f32(_p(gx), 4 * H, _p(cell.weight_hh.contiguous()), _p(seq_base), int(steps), B, H,
+                                              1 if reverse else 0, _p(out), out.stride(0) if B > 1 else max(out.stride(0), H), _s()),
+            "egp_lstm_window_last_f32")
+    WINDOW_CALLS += 1
+    return out
+
+
 def lstm_direction(cell, x, reverse):
     params = (cell.weight_ih, cell.weight_hh, cell.bias_ih, cell.bias_hh)
     return LstmDirection.apply(x, *params, bool(reverse), _wants_grad(x, params))

@@ -448,6 +448,48 @@ class VideoStateNet(nn.Module):
             lens_sorted = lens[order]
             self._buckets = [(cuts[k], cuts[k + 1], int(m + lens_sorted[cuts[k]])) for k in range(_FWD_BUCKETS)]
 
+    @torch.no_grad()
+    def online_contexts(self, x):
+        """The contexts of the reference's ONLINE evaluation (ego_pose/ego_mimic_eval.py:143-145: the net is re-initialised at
+        every tick on the frames seen so far) for one take's features x (T + 2m, D) -> (T, v_hdim): row t is what
+        ``initialize(x[:t + 2m + 1]); v_out[t]`` gives, i.e. row t + m of the net over frames [0, t + 2m]. Test mode, no gradients;
+        `v_out` and `t` stay as they are.
+
+        bi-LSTM      left half: the forward direction at frame t + m sees frames <= t + m whatever the prefix -- rows [m, m + T)
+                     of one sweep. Right half: rnn_b after m + 1 steps from zero over frames t + 2m .. t + m -- T windows of
+                     m + 1 frames, one launch of `lstm.window_last` over one per-frame projection (float32 on the device), else
+                     a gathered (m + 1, T, D) batch through the module's own reverse sweep.
+        causal nets  (uni-directional LSTM, causal TCN): no look-ahead, online == offline.
+        TCN          one-sided reach R = (kernel_size - 1) * (2**levels - 1) frames: while R <= m row t + m never reaches the
+                     prefix's padded end, online == offline exactly. R > m: by the definition, one net pass per tick -- O(T^2)
+                     frames, slow; no shipped config has it."""
+        if self.mode != "test":
+            raise RuntimeError("online_contexts is a test-mode (evaluation) call")
+        m = self.v_margin
+        p = next(self.parameters())
+        x = x.to(device=p.device, dtype=p.dtype)
+        if x.dim() != 2 or x.shape[0] < 2 * m + 1:
+            raise ValueError("online_contexts takes one take's features (T + 2m, D) with T >= 1, got %s" % (tuple(x.shape),))
+        T, net = x.shape[0] - 2 * m, self.v_net
+        offline = lambda: self.forward_v_net(x.unsqueeze(1))[m:m + T, 0]
+        if isinstance(net, _tcn.TemporalConvNet):
+            reach = (net.kernel_size - 1) * (2 ** len(net.network) - 1)
+            if net.causal or reach <= m:
+                return offline()
+            return torch.stack([self.forward_v_net(x[:t + 2 * m + 1].unsqueeze(1))[t + m, 0] for t in range(T)], 0)
+        if not net.bi_dir:
+            return offline()
+        H = net.rnn_f.hidden_size
+        out = x.new_empty(T, 2 * H)
+        out[:, :H] = net._sweep(net.rnn_f, x.unsqueeze(1), False)[m:m + T, 0]
+        if net.cell_type == "lstm" and _LSTM_IMPL != "torch" and _hip_lstm.window_available(x, net.rnn_b):
+            base = torch.arange(m, m + T, dtype=torch.int32, device=x.device)
+            _hip_lstm.window_last(net.rnn_b, x.contiguous(), base, m + 1, True, out[:, H:])
+        else:
+            rows = torch.arange(m + 1, device=x.device).unsqueeze(1) + torch.arange(m, m + T, device=x.device).unsqueeze(0)
+            out[:, H:] = net._sweep(net.rnn_b, x[rows], True)[0]
+        return out
+
     _TRAIN_CONTEXT = ("indices", "cnn_feat_ctx", "gather_indices", "_gather_tm", "_gather_unique", "_ctx_key", "_ragged",
                       "_buckets", "_gather_sorted", "_ctx_sorted", "_frames")
 

@@ -498,6 +498,19 @@ int egp_lstm_group_bwd_rows_f32(const float *const *dh_out, int32_t ld_dh, const
                                 int32_t T, int32_t B, int32_t hidden, int32_t n_problems, int32_t reverse_mask, float *d_pre, float *d_bias_rows,
                                 const int32_t *seq_order, const int32_t *seq_steps, int32_t leave_skipped, void *stream);
 
+/* Windowed recurrence, last state only (inference): B windows of `steps` consecutive frames of one table, each swept from zero
+ * state, and only the hidden state after the last step is kept. This is the backward direction of the ONLINE evaluation
+ * (ego_pose/ego_mimic_eval.py:143-145 re-initialises the policy's video net on cnn_feat[:t + 2*fr_margin + 1] at every tick t;
+ * row t + fr_margin of rnn_b's sweep over that prefix, models/rnn.py:45-61, is its state after fr_margin + 1 steps from the
+ * prefix's end): one launch for all ticks of a take instead of a sweep per tick.
+ *   gates_x [n_frames][ld_g]: per-FRAME input projection + both biases, unit-major gate layout, ld_g >= 4H (a multiple of 4);
+ *   w_hh [4H][H];  seq_base (device, B entries): window b = frames seq_base[b] .. seq_base[b] + steps - 1 (windows may overlap;
+ *   the caller keeps them inside the table);  reverse: walked from the last frame of the window to the first;
+ *   out[b * ld_out + u] (u < H, ld_out >= H) = h of window b after `steps` (>= 1) steps -- nothing else is written, so `out` may
+ *   point into a wider table (the right half of a [T][2H] bi-LSTM context).  B == 0: nothing to do. */
+int egp_lstm_window_last_f32(const float *gates_x, int32_t ld_g, const float *w_hh, const int32_t *seq_base, int32_t steps, int32_t B,
+                             int32_t hidden, int32_t reverse, float *out, int32_t ld_out, void *stream);
+
 /* ----------------------------------------------------------------------------------------
  * K8: dynamics terms on the GPU. From (qpos, qvel) per env: body frame positions (mjData.xpos[1:]),
  * the joint-space inertia in MuJoCo's legacy sparse order (mjData.qM, what mj_fullM expands) and the bias force
