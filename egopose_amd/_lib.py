@@ -64,6 +64,28 @@ class MlpLayer(C.Structure):
     _fields_ = [("wt", vp), ("bias", vp), ("in_dim", C.c_int32), ("out_dim", C.c_int32)]
 
 
+class PolicyDesc(C.Structure):
+    """egp_policy_desc (include/egopose_hip.h)."""
+    _fields_ = [("n", C.c_int32),
+                ("ctx_rows", vp), ("ctx_row_stride", C.c_int64), ("ctx_dim", C.c_int32),
+                ("t_idx", vp),
+                ("state", vp), ("state_dim", C.c_int32),
+                ("ctx", vp),
+                ("qpos", vp), ("qvel", vp), ("phase_t", vp),
+                ("zf_in", vp), ("zf_out", vp), ("clip", C.c_double),
+                ("y", vp), ("y2", vp),
+                ("zf_workspace", vp),
+                ("layers", C.POINTER(MlpLayer)), ("n_layers", C.c_int32), ("activation", C.c_int32),
+                ("log_std", vp), ("noise", vp),
+                ("action", vp), ("mean_out", vp),
+                ("cell", C.POINTER(MlpLayer)),
+                ("h", vp), ("c", vp), ("hc_row_stride", C.c_int64),
+                ("vctx_rows", vp), ("vctx_row_stride", C.c_int64), ("vctx_dim", C.c_int32),
+                ("vlayers", C.POINTER(MlpLayer)), ("n_vlayers", C.c_int32), ("vactivation", C.c_int32),
+                ("value_out", vp),
+                ("stage_src", vp), ("stage_dst", vp), ("stage_bytes", C.c_int64)]
+
+
 class GemmDesc(C.Structure):
     _fields_ = [("M", C.c_int32), ("N", C.c_int32), ("K", C.c_int32),
                 ("A", vp), ("lda", C.c_int64), ("a_kcontig", C.c_int32),
@@ -246,8 +268,6 @@ SIGNATURES = {
     "egp_obs_zfilter_split_max_rows": (C.c_int32, []),
     "egp_obs_zfilter_stats_f64": (C.c_int, [vp, vp, vp, vp, vp, _i32, vp, vp]),
     "egp_obs_zfilter_apply_f64": (C.c_int, [vp, vp, vp, vp, _i32, vp, vp, C.c_double, vp, vp, vp, vp]),
-    "egp_policy_gaussian_filter_f32": (C.c_int, [vp, vp, C.c_int64, _i32, vp, vp, vp, vp, _i32, vp, vp, C.c_double, vp, vp, vp,
-                                                vp, _i32, _i32, vp, vp, vp, vp, vp, vp, C.c_int64, vp]),
     "egp_rollout_tick_post": (C.c_int, [vp, _i32, _i32, _i32, _i32, vp, vp, vp, vp]),
     "egp_rollout_reset": (C.c_int, [vp, _i32, _i32, _i32, _i32, vp, _i32, vp, vp, vp, vp, vp, vp, vp, vp, vp]),
     "egp_engine_group_stream": (vp, [vp, _i32]),
@@ -262,15 +282,7 @@ SIGNATURES = {
     "egp_pose2d_f64": (C.c_int, [vp, vp, vp, vp, vp, vp, vp, C.c_int64, vp]),
     "egp_mlp_pack_floats": (C.c_int64, [_i32, _i32]),
     "egp_mlp_pack_f32": (C.c_int, [vp, C.c_int64, _i32, _i32, vp, vp]),
-    "egp_policy_gaussian_f32": (C.c_int, [vp, C.c_int64, _i32, vp, vp, _i32, _i32, C.POINTER(MlpLayer), _i32, _i32, vp, vp, vp, vp, vp]),
-    "egp_policy_forecast_f32": (C.c_int, [vp, C.c_int64, _i32, vp, vp, _i32, C.POINTER(MlpLayer), vp, vp, C.c_int64, _i32,
-                                          C.POINTER(MlpLayer), _i32, _i32, vp, vp, vp, vp, vp]),
-    "egp_policy_forecast_filter_f32": (C.c_int, [vp, vp, C.c_int64, _i32, vp, vp, vp, vp, _i32, vp, vp, C.c_double, vp, vp, vp,
-                                                 C.POINTER(MlpLayer), vp, vp, C.c_int64, C.POINTER(MlpLayer), _i32, _i32, vp, vp, vp, vp, vp]),
-    "egp_policy_value_filter_f32": (C.c_int, [vp, vp, C.c_int64, _i32, vp, C.c_int64, _i32, vp, vp, vp, vp, _i32, vp, vp, C.c_double, vp, vp,
-                                              C.POINTER(MlpLayer), _i32, _i32, vp, vp, vp, vp, C.POINTER(MlpLayer), _i32, _i32, vp, vp]),
-    "egp_policy_gaussian_staged_f32": (C.c_int, [vp, C.c_int64, _i32, vp, vp, _i32, _i32, C.POINTER(MlpLayer), _i32, _i32, vp, vp, vp, vp, vp, vp,
-                                                 C.c_int64, vp]),
+    "egp_policy_step_f32": (C.c_int, [C.POINTER(PolicyDesc), vp]),
     "egp_physics_register": (C.c_int, [C.POINTER(PhysicsVtable), _i32, C.POINTER(vp)]),
     "egp_physics_create_surrogate": (C.c_int, [C.POINTER(SurrogateDesc), _i32, C.POINTER(vp)]),
     "egp_physics_destroy": (C.c_int, [vp]),

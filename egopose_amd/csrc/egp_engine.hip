@@ -1122,30 +1122,31 @@ int egp_rollout_tick_pre(const egp_rollout_tick *d, int32_t group, int32_t a, in
         ti[i] = d->cur_t[e] < d->ctx_T - 1 ? d->cur_t[e] : d->ctx_T - 1;
     }
     uint8_t *fbase = d->slab_dev + soff;
-    int rc = EGP_OK;
     const size_t row = (size_t)k * N + a;
     // The policy kernel moves the flag slab to its device copy itself and reads its context-row indices straight from the pinned
     // one (one dependent operation less per tick than a copy-engine transfer in front of it).
+    egp_policy_desc p = {};
+    p.n = n;
+    p.ctx_rows = d->v_out + (size_t)a * d->v_stride; p.ctx_row_stride = d->v_stride; p.ctx_dim = d->ctx_dim;
+    p.t_idx = ti;
     if (apply_pending) {
         // the apply pass of the previous env-step's filter (its statistics pass ran in `post`) rides in this policy step:
         // next_states[k - 1] and states[k] are written on the way into the MLP
-        rc = egp_policy_gaussian_filter_f32(d->ctx, d->v_out + (size_t)a * d->v_stride, d->v_stride, d->ctx_dim,
-                                            reinterpret_cast<const int64_t *>(d->slab_host + soff + 16 * (size_t)nmax),
-                                            d->qpos + (size_t)a * d->nq, d->qvel + (size_t)a * d->nv,
-                                            // (obs_phase: cur_t of the state = the step counter staged for the PREVIOUS env-step, slab slot (k - 1) & 1)
-                                            reinterpret_cast<const int32_t *>(d->slab_dev + (size_t)(group * 2 + ((k - 1) & 1)) * 24 * nmax),
-                                            n, zf_cur, zf_new, d->zf_clip,
-                                            d->next_states + (row - N) * d->obs_dim, d->states + row * d->obs_dim, d->zf_workspace,
-                                            d->layers, d->n_layers, d->activation, d->log_std,
-                                            d->noise ? d->noise + row * d->nu : nullptr, d->actions + row * d->nu, nullptr,
-                                            d->slab_host + soff, fbase, 24 * (int64_t)nmax, ts);
+        p.ctx = d->ctx;
+        p.qpos = d->qpos + (size_t)a * d->nq; p.qvel = d->qvel + (size_t)a * d->nv;
+        // (obs_phase: cur_t of the state = the step counter staged for the PREVIOUS env-step, slab slot (k - 1) & 1)
+        p.phase_t = reinterpret_cast<const int32_t *>(d->slab_dev + (size_t)(group * 2 + ((k - 1) & 1)) * 24 * nmax);
+        p.zf_in = zf_cur; p.zf_out = zf_new; p.clip = d->zf_clip;
+        p.y = d->next_states + (row - N) * d->obs_dim; p.y2 = d->states + row * d->obs_dim;
+        p.zf_workspace = d->zf_workspace;
     } else {
-        rc = egp_policy_gaussian_staged_f32(d->v_out + (size_t)a * d->v_stride, d->v_stride, d->ctx_dim,
-                                            reinterpret_cast<const int64_t *>(d->slab_host + soff + 16 * (size_t)nmax),
-                                            d->states + row * d->obs_dim, d->obs_dim, n, d->layers, d->n_layers, d->activation, d->log_std,
-                                            d->noise ? d->noise + row * d->nu : nullptr, d->actions + row * d->nu, nullptr,
-                                            d->slab_host + soff, fbase, 24 * (int64_t)nmax, ts);
+        p.state = d->states + row * d->obs_dim; p.state_dim = d->obs_dim;
     }
+    p.layers = d->layers; p.n_layers = d->n_layers; p.activation = d->activation; p.log_std = d->log_std;
+    p.noise = d->noise ? d->noise + row * d->nu : nullptr;
+    p.action = d->actions + row * d->nu;
+    p.stage_src = d->slab_host + soff; p.stage_dst = fbase; p.stage_bytes = 24 * (int64_t)nmax;
+    int rc = egp_policy_step_f32(&p, ts);
     if (rc != EGP_OK) return rc;
     EGP_HIP_CHECK(hipEventRecord((hipEvent_t)ready_event, ts));
     if (d->reward_job) {      // K2 rides behind this env-step's kernel on the engine's stream

@@ -2051,6 +2051,7 @@ int64_t egp_abi_sizeof(const char *name) {
     EGP_ABI_SIZE(egp_surrogate_desc) EGP_ABI_SIZE(egp_engine_desc) EGP_ABI_SIZE(egp_rollout_tick)
     EGP_ABI_SIZE(egp_ppo_loss_desc) EGP_ABI_SIZE(egp_adam_segment) EGP_ABI_SIZE(egp_host_probe_result)
     EGP_ABI_SIZE(egp_minibatch_plan_desc) EGP_ABI_SIZE(egp_ppo_loss_mb_desc) EGP_ABI_SIZE(egp_tcn_desc)
+    EGP_ABI_SIZE(egp_policy_desc)
 #undef EGP_ABI_SIZE
     return -1;
 }
@@ -2679,7 +2680,7 @@ int egp_obs_zfilter_f32(egp_ctx *c, const float *qpos, const float *qvel, const 
 }
 // egp_obs_zfilter_f64 in two calls, for batches of at most egp_obs_zfilter_split_max_rows() rows (the apply pass merges the tile
 // statistics itself there): _stats = the first launch, _apply = the second, same kernels with the same arguments. Whoever runs
-// the apply pass may instead be the policy step of the next tick (egp_policy_gaussian_filter_f32).
+// the apply pass may instead be the policy step of the next tick (egp_policy_step_f32 with the descriptor's filter block).
 int32_t egp_obs_zfilter_split_max_rows(void) { return 64 * ZF_FUSED_TILES; }
 int egp_obs_zfilter_stats_f64(egp_ctx *ctx, const double *qpos, const double *qvel, const int32_t *phase_t, const int32_t *active, int32_t n, void *ws, void *stream) {
     EGP_REQUIRE(ctx && ws, "NULL pointer");

@@ -17,7 +17,7 @@
 // activations), and the first layer's before the input rows are gathered: the dependent global round trips of a tick
 // (context-row index -> context row, tile statistics -> filtered observation) overlap the weight stream.
 //
-// ego_forecast (egp_policy_forecast_f32, forecast_body below): the state first goes through one step of the state LSTM cell
+// ego_forecast (egp_policy_desc.cell, forecast_body below): the state first goes through one step of the state LSTM cell
 // (models/rnn.py:29-36, models/video_forecast_net.py:88-93) -- its gate pre-activations are one more layer of the same passes, its
 // epilogue the gates -- and x = [context row | h']; h / c are updated in place.
 #include <hip/hip_runtime.h>
@@ -33,7 +33,7 @@ namespace {
 
 typedef float f32x4 __attribute__((ext_vector_type(4)));
 
-// The filter's apply pass folded into the policy step (egp_policy_gaussian_filter_f32): the observation rows of the tile are
+// The filter's apply pass folded into the policy step (egp_policy_desc's filter block): the observation rows of the tile are
 // formed, normalised with the running statistics merged from the tick's tile partials (exactly k_zf_apply's arithmetic: same
 // merge order, same expression, float64) and written to next_states[k] / states[k + 1] on their way into the MLP's input -- one
 // launch and its dependent memory round trips less on the chain filter -> policy -> env-step of every tick without a reset.
@@ -618,7 +618,7 @@ __global__ __launch_bounds__(256) void k_policy_gaussian_w4(const float *__restr
                                   stage_src, stage_dst, stage_words, F);
 }
 
-// Actor and critic of a tick in one launch (egp_policy_value_filter_f32): a second grid dimension selects the net. Workgroup
+// Actor and critic of a tick in one launch (egp_policy_desc.vlayers): a second grid dimension selects the net. Workgroup
 // (x, 0) is k_policy_gaussian_w4 for rows x R ..: observation -> filter (frozen statistics) -> [policy ctx row | state] -> MLP ->
 // Gaussian head, and it alone writes y / y2 / st_out. Workgroup (x, 1) takes the same rows through the value stack --
 // [value ctx row | state] -> MLP -> value_head, one float32 per row -- and repeats the cheap frozen normalisation for itself, so
@@ -644,7 +644,7 @@ __global__ __launch_bounds__(256) void k_policy_value_w4(PolNets P, const long l
 }
 
 // ---------------------------------------------------------------------------------------------------------------- forecast
-// The ego_forecast policy step (egp_policy_forecast_f32): the state goes through one step of the state LSTM
+// The ego_forecast policy step (egp_policy_desc.cell): the state goes through one step of the state LSTM
 // (models/rnn.py:29-36 in step mode, as models/video_forecast_net.py:88-93 calls it) before it joins the video context:
 //   pre = [W_ih | W_hh] [s | h] + (b_ih + b_hh);  c' = sigmoid(f) c + sigmoid(i) tanh(g);  h' = sigmoid(o) tanh(c');  x = [ctx | h']
 // The gate pre-activations are layer 0 of the same pass machinery (L.wp[0]: the cell, input [s | h] in `cur`, 4 Hs outputs with
@@ -653,7 +653,7 @@ __global__ __launch_bounds__(256) void k_policy_value_w4(PolNets P, const long l
 // gathered into `nxt` -- the MLP's input -- and h' / c' back to the caller's rows. Layers 1 .. L.n - 1 are the MLP and the head.
 // In place: a workgroup's h / c rows are read in the prologue (into LDS) and written in layer 0's epilogue, behind barriers;
 // no workgroup touches another's rows, and rows >= n are neither read nor written.
-// FILTER (egp_policy_forecast_filter_f32): the state columns are the observations of (qpos, qvel) pushed through the filter's apply
+// FILTER (the descriptor's filter block): the state columns are the observations of (qpos, qvel) pushed through the filter's apply
 // pass on their way into `cur` (see PolFilter) -- k_zf_apply's two phases in its plain form: every workgroup merges the tile
 // partials into the running statistics for itself (F.n_tiles == 0: the statistics as they stand, the frozen filter of an
 // evaluation), one column per thread and round, then normalises its rows element by element. `state` is unused then.
@@ -842,194 +842,100 @@ static int pol_launched(const char *what) {
     return EGP_OK;
 }
 
-static int policy_launch(const float *ctx_rows, int64_t ctx_row_stride, int32_t ctx_dim, const int64_t *t_idx,
-                         const double *state, int32_t state_dim, int32_t n, const egp_mlp_layer *layers,
-                         int32_t n_layers, int32_t activation, const float *log_std, const float *noise,
-                         double *action, float *mean_out, const void *stage_src, void *stage_dst, int64_t stage_bytes, void *stream,
-                         const PolFilter *flt = nullptr) {
-    EGP_REQUIRE(n >= 0, "n < 0");
-    EGP_REQUIRE(stage_bytes >= 0 && stage_bytes % 4 == 0 && stage_bytes < (1ll << 31) && (stage_bytes == 0 || (stage_src && stage_dst)), "bad staging slab");
-    if (n == 0) return EGP_OK;
-    EGP_REQUIRE(ctx_rows && t_idx && (state || flt) && layers && action, "NULL pointer");
-    EGP_REQUIRE(!noise || log_std, "noise needs log_std");
-    EGP_REQUIRE(n_layers >= 1 && n_layers <= POL_MAX_LAYERS, "1..8 layers (hidden layers + output layer)");
-    EGP_REQUIRE(activation >= 0 && activation <= 2, "activation: 0 tanh, 1 relu, 2 sigmoid");
-    EGP_REQUIRE(ctx_dim >= 0 && state_dim >= 0 && ctx_dim + state_dim > 0, "bad input dims");
-    PolLayers L;
-    int kmax, xs;
-    size_t lds;
-    if (int rc = pol_layer_table(nullptr, layers, n_layers, ctx_dim + state_dim, "layer dims do not chain", L, &kmax)) return rc;
-    // the tail: the pad float in front of the doubles, and with the filter its merged mean | 1 / std
-    if (int rc = pol_lds(L, kmax, 0, flt ? 2 * state_dim : 0, &xs, &lds)) return rc;
-    const dim3 grid((n + POL_R - 1) / POL_R), block(POL_NW * 64);
-    const PolFilter F = flt ? *flt : PolFilter{};
-    const unsigned *ssrc = stage_bytes ? (const unsigned *)stage_src : nullptr;
-#define POL_GO(FLT) k_policy_gaussian_w4<POL_R, POL_PF, FLT><<<grid, block, lds, (hipStream_t)stream>>>(                                          \
-        ctx_rows, (long)ctx_row_stride, ctx_dim, (const long long *)t_idx, state, state_dim, n, L, activation, xs, log_std, noise, action, mean_out, \
-        ssrc, (unsigned *)stage_dst, (int)(stage_bytes / 4), F)
-    if (flt) POL_GO(true); else POL_GO(false);
-#undef POL_GO
-    return pol_launched("k_policy_gaussian");
-}
-
-extern "C" int egp_policy_gaussian_f32(const float *ctx_rows, int64_t ctx_row_stride, int32_t ctx_dim, const int64_t *t_idx,
-                                       const double *state, int32_t state_dim, int32_t n, const egp_mlp_layer *layers,
-                                       int32_t n_layers, int32_t activation, const float *log_std, const float *noise,
-                                       double *action, float *mean_out, void *stream) {
-    return policy_launch(ctx_rows, ctx_row_stride, ctx_dim, t_idx, state, state_dim, n, layers, n_layers, activation, log_std, noise, action,
-                         mean_out, nullptr, nullptr, 0, stream);
-}
-
-// The ego_forecast policy step: one step of the state LSTM cell (models/rnn.py:29-36, models/video_forecast_net.py:88-93), then
-// [ctx | h'] -> MLP -> Gaussian head as above, h' / c' written back in place. `cell` is the gate layer in egp_mlp_layer form
-// (include/egopose_hip.h gives the column order); see forecast_body.
-static int forecast_launch(const float *ctx_rows, int64_t ctx_row_stride, int32_t ctx_dim, const int64_t *t_idx,
-                           const double *state, int32_t state_dim, const egp_mlp_layer *cell, float *h, float *c,
-                           int64_t hc_row_stride, int32_t n, const egp_mlp_layer *layers, int32_t n_layers,
-                           int32_t activation, const float *log_std, const float *noise, double *action, float *mean_out,
-                           void *stream, const PolFilter *flt = nullptr) {
-    EGP_REQUIRE(n >= 0, "n < 0");
-    if (n == 0) return EGP_OK;
-    EGP_REQUIRE((state || flt) && cell && h && c && h != c && layers && action, "NULL pointer (or h == c)");
-    EGP_REQUIRE(ctx_dim >= 0 && (ctx_dim == 0 || (ctx_rows && t_idx)), "bad context");
-    EGP_REQUIRE(!noise || log_std, "noise needs log_std");
-    EGP_REQUIRE(n_layers >= 1 && n_layers + 1 <= POL_MAX_LAYERS, "1..7 layers (hidden layers + output layer) behind the cell");
-    EGP_REQUIRE(activation >= 0 && activation <= 2, "activation: 0 tanh, 1 relu, 2 sigmoid");
-    EGP_REQUIRE(cell->wt && cell->bias && ((uintptr_t)cell->wt & 15) == 0, "cell: NULL or misaligned packed weights");
-    EGP_REQUIRE(cell->out_dim >= 4 && cell->out_dim % 4 == 0 && cell->out_dim <= 2048, "cell: out_dim = 4 x hidden size, at most 2048");
-    const int hs = cell->out_dim / 4;
-    EGP_REQUIRE(state_dim >= 1 && cell->in_dim == state_dim + hs && cell->in_dim <= 2048, "cell: in_dim = state_dim + hidden size, at most 2048");
-    EGP_REQUIRE(hc_row_stride >= hs, "h / c row stride below the hidden size");
-    PolLayers L;
-    int kmax, xs;
-    size_t lds;
-    if (int rc = pol_layer_table(cell, layers, n_layers, ctx_dim + hs, "layer dims do not chain (first layer: ctx_dim + hidden size)", L, &kmax)) return rc;
-    // the tail: the cell's c rows, and with the filter its merged mean | 1 / std
-    if (int rc = pol_lds(L, kmax, POL_R * hs, flt ? 2 * state_dim : 0, &xs, &lds)) return rc;
-    const dim3 grid((n + POL_R - 1) / POL_R), block(POL_NW * 64);
-    const PolFilter F = flt ? *flt : PolFilter{};
-#define POL_GO(FLT) k_policy_forecast_w4<POL_R, POL_PF, FLT><<<grid, block, lds, (hipStream_t)stream>>>(                                         \
-        ctx_rows, (long)ctx_row_stride, ctx_dim, (const long long *)t_idx, state, state_dim, h, c, (long)hc_row_stride, hs, n, L, activation, xs, \
-        log_std, noise, action, mean_out, F)
-    if (flt) POL_GO(true); else POL_GO(false);
-#undef POL_GO
-    return pol_launched("k_policy_forecast");
-}
-
-extern "C" int egp_policy_forecast_f32(const float *ctx_rows, int64_t ctx_row_stride, int32_t ctx_dim, const int64_t *t_idx,
-                                       const double *state, int32_t state_dim, const egp_mlp_layer *cell, float *h, float *c,
-                                       int64_t hc_row_stride, int32_t n, const egp_mlp_layer *layers, int32_t n_layers,
-                                       int32_t activation, const float *log_std, const float *noise, double *action, float *mean_out,
-                                       void *stream) {
-    return forecast_launch(ctx_rows, ctx_row_stride, ctx_dim, t_idx, state, state_dim, cell, h, c, hc_row_stride, n, layers, n_layers, activation,
-                           log_std, noise, action, mean_out, stream);
-}
-
-// egp_policy_forecast_f32 with the filter's apply pass in front (see PolFilter and forecast_body): the cell's state input is the
-// observation of (qpos, qvel), normalised with `zf_in` merged with the tile statistics that egp_obs_zfilter_stats_f64 left in
-// `zf_workspace` -- exactly what egp_obs_zfilter_apply_f64 followed by egp_policy_forecast_f32 on y2 computes -- or, with
-// zf_workspace == NULL, with `zf_in` as it stands (the frozen filter of an evaluation: ZFilter.__call__(x, update=False)).
-extern "C" int egp_policy_forecast_filter_f32(egp_ctx *ctx, const float *ctx_rows, int64_t ctx_row_stride, int32_t ctx_dim, const int64_t *t_idx,
-                                              const double *qpos, const double *qvel, const int32_t *phase_t, int32_t n,
-                                              const double *zf_in, double *zf_out, double clip, double *y, double *y2, const void *zf_workspace,
-                                              const egp_mlp_layer *cell, float *h, float *c, int64_t hc_row_stride,
-                                              const egp_mlp_layer *layers, int32_t n_layers, int32_t activation, const float *log_std,
-                                              const float *noise, double *action, float *mean_out, void *stream) {
-    EGP_REQUIRE(n >= 0, "n < 0");
-    if (n == 0) return EGP_OK;
-    EGP_REQUIRE(ctx && qpos && qvel && zf_in && y && zf_in != zf_out, "NULL pointer / zf_out must differ from zf_in");
-    EGP_REQUIRE(!zf_workspace || (zf_out && n <= 64 * egp::ZF_FUSED_TILES),
+// The PolFilter of a descriptor's filter block (zf_in != NULL). `need_out`: the kernel stores to zf_out without a null check (every
+// step but the forecast one). Frozen statistics (zf_workspace == NULL): no tiles, and ws = zf_in -- the plain step's wave merge
+// loads tile 0 unconditionally and discards it (`zf_in` has a tile partial's layout); zf_merge_column never reads ws then.
+static int pol_filter(const egp_policy_desc *d, bool need_out, PolFilter &f) {
+    EGP_REQUIRE(d->ctx && d->qpos && d->qvel && d->y && (d->zf_out || !need_out) && d->zf_in != d->zf_out,
+                "NULL pointer / zf_out must differ from zf_in");
+    EGP_REQUIRE(!d->zf_workspace || (d->zf_out && d->n <= 64 * egp::ZF_FUSED_TILES),
                 "merged statistics: zf_out is required and at most egp_obs_zfilter_split_max_rows() rows");
-    EGP_REQUIRE(!ctx->dm.obs_phase || phase_t, "the model has obs_phase: phase_t (the rows' cur_t) is required");
-    const int dim = ctx->dm.obs_dim;
+    const auto &dm = d->ctx->dm;
+    EGP_REQUIRE(!dm.obs_phase || d->phase_t, "the model has obs_phase: phase_t (the rows' cur_t) is required");
     int rpt, nt = 0;
-    if (zf_workspace) egp::zf_tiling(n, &rpt, &nt);
-    PolFilter f;
-    f.src = egp::ZfSrc<double>{nullptr, qpos, qvel, ctx->dm.nq, ctx->dm.nv, dim, egp::obs_opt_of(ctx->dm), phase_t};
-    f.st_in = zf_in; f.st_out = zf_out; f.ws = (const double *)zf_workspace; f.n_tiles = nt; f.clip = clip; f.y = y; f.y2 = y2;
-    return forecast_launch(ctx_rows, ctx_row_stride, ctx_dim, t_idx, nullptr, dim, cell, h, c, hc_row_stride, n, layers, n_layers, activation,
-                           log_std, noise, action, mean_out, stream, &f);
-}
-
-extern "C" int egp_policy_gaussian_staged_f32(const float *ctx_rows, int64_t ctx_row_stride, int32_t ctx_dim, const int64_t *t_idx,
-                                              const double *state, int32_t state_dim, int32_t n, const egp_mlp_layer *layers,
-                                              int32_t n_layers, int32_t activation, const float *log_std, const float *noise,
-                                              double *action, float *mean_out, const void *stage_src, void *stage_dst, int64_t stage_bytes,
-                                              void *stream) {
-    return policy_launch(ctx_rows, ctx_row_stride, ctx_dim, t_idx, state, state_dim, n, layers, n_layers, activation, log_std, noise, action,
-                         mean_out, stage_src, stage_dst, stage_bytes, stream);
-}
-
-// egp_policy_gaussian_staged_f32 with the filter's apply pass in front (see PolFilter): the policy input's state columns are the
-// filtered observations of (qpos, qvel) -- the group's n rows -- normalised with `zf_in` merged with the tile statistics that
-// egp_obs_zfilter_stats_f64 left in `zf_workspace`; they are also written to y (and y2), and the merged statistics to zf_out:
-// together exactly what egp_obs_zfilter_apply_f64 followed by egp_policy_gaussian_staged_f32 on y2 computes, in one launch.
-// the PolFilter of a *_filter_f32 entry point. zf_workspace == NULL: frozen statistics (no tiles; the wave merge's unconditional
-// tile-0 loads read `zf_in` itself, which has a tile partial's layout, and are discarded)
-static int pol_filter_of(egp_ctx *ctx, const double *qpos, const double *qvel, const int32_t *phase_t, int32_t n, const double *zf_in, double *zf_out,
-                         double clip, double *y, double *y2, const void *zf_workspace, PolFilter &f) {
-    EGP_REQUIRE(ctx && qpos && qvel && zf_in && zf_out && zf_in != zf_out && y, "NULL pointer / zf_out must differ from zf_in");
-    EGP_REQUIRE(n > 0 && (!zf_workspace || n <= 64 * egp::ZF_FUSED_TILES), "merged statistics: 1 .. egp_obs_zfilter_split_max_rows() rows");
-    EGP_REQUIRE(!ctx->dm.obs_phase || phase_t, "the model has obs_phase: phase_t (the rows' cur_t) is required");
-    int rpt, nt = 0;
-    if (zf_workspace) egp::zf_tiling(n, &rpt, &nt);
-    f.src = egp::ZfSrc<double>{nullptr, qpos, qvel, ctx->dm.nq, ctx->dm.nv, ctx->dm.obs_dim, egp::obs_opt_of(ctx->dm), phase_t};
-    f.st_in = zf_in; f.st_out = zf_out; f.ws = zf_workspace ? (const double *)zf_workspace : zf_in; f.n_tiles = nt; f.clip = clip; f.y = y; f.y2 = y2;
+    if (d->zf_workspace) egp::zf_tiling(d->n, &rpt, &nt);
+    f.src = egp::ZfSrc<double>{nullptr, d->qpos, d->qvel, dm.nq, dm.nv, dm.obs_dim, egp::obs_opt_of(dm), d->phase_t};
+    f.st_in = d->zf_in; f.st_out = d->zf_out; f.ws = d->zf_workspace ? (const double *)d->zf_workspace : d->zf_in; f.n_tiles = nt;
+    f.clip = d->clip; f.y = d->y; f.y2 = d->y2;
     return EGP_OK;
 }
 
-// egp_policy_gaussian_staged_f32 with the filter's apply pass in front (see PolFilter): the policy input's state columns are the
-// filtered observations of (qpos, qvel) -- the group's n rows -- normalised with `zf_in` merged with the tile statistics that
-// egp_obs_zfilter_stats_f64 left in `zf_workspace`; they are also written to y (and y2), and the merged statistics to zf_out:
-// together exactly what egp_obs_zfilter_apply_f64 followed by egp_policy_gaussian_staged_f32 on y2 computes, in one launch.
-// zf_workspace == NULL: `zf_in` as it stands (the frozen filter of an evaluation); zf_out receives a copy of it.
-extern "C" int egp_policy_gaussian_filter_f32(egp_ctx *ctx, const float *ctx_rows, int64_t ctx_row_stride, int32_t ctx_dim, const int64_t *t_idx,
-                                              const double *qpos, const double *qvel, const int32_t *phase_t, int32_t n, const double *zf_in, double *zf_out,
-                                              double clip, double *y, double *y2, const void *zf_workspace,
-                                              const egp_mlp_layer *layers, int32_t n_layers, int32_t activation, const float *log_std,
-                                              const float *noise, double *action, float *mean_out, const void *stage_src, void *stage_dst,
-                                              int64_t stage_bytes, void *stream) {
-    PolFilter f;
-    if (int rc = pol_filter_of(ctx, qpos, qvel, phase_t, n, zf_in, zf_out, clip, y, y2, zf_workspace, f)) return rc;
-    return policy_launch(ctx_rows, ctx_row_stride, ctx_dim, t_idx, nullptr, ctx->dm.obs_dim, n, layers, n_layers, activation, log_std, noise, action,
-                         mean_out, stage_src, stage_dst, stage_bytes, stream, &f);
-}
-
-// Actor and critic of an evaluation tick in one launch (k_policy_value_w4): per row the observation of (qpos, qvel), the frozen
-// filter, [policy ctx row | state] -> `layers` -> Gaussian head -> action (as egp_policy_gaussian_filter_f32 with zf_workspace ==
-// NULL, bit for bit) and [value ctx row | state] -> `vlayers` -> value_out[row] (float32; the last of vlayers is the value head,
-// out_dim 1). zf_in == NULL: no filter -- `y` must hold the rows' states already and is read, not written.
-extern "C" int egp_policy_value_filter_f32(egp_ctx *ctx, const float *ctx_rows, int64_t ctx_row_stride, int32_t ctx_dim, const float *vctx_rows,
-                                           int64_t vctx_row_stride, int32_t vctx_dim, const int64_t *t_idx, const double *qpos, const double *qvel,
-                                           const int32_t *phase_t, int32_t n, const double *zf_in, double *zf_out, double clip, double *y, double *y2,
-                                           const egp_mlp_layer *layers, int32_t n_layers, int32_t activation, const float *log_std,
-                                           const float *noise, double *action, float *mean_out, const egp_mlp_layer *vlayers, int32_t n_vlayers,
-                                           int32_t vactivation, float *value_out, void *stream) {
-    EGP_REQUIRE(n >= 0, "n < 0");
-    if (n == 0) return EGP_OK;
-    EGP_REQUIRE(ctx && ctx_rows && vctx_rows && t_idx && y && layers && vlayers && action && value_out, "NULL pointer");
-    EGP_REQUIRE(!noise || log_std, "noise needs log_std");
-    EGP_REQUIRE(n_layers >= 1 && n_layers <= POL_MAX_LAYERS && n_vlayers >= 1 && n_vlayers <= POL_MAX_LAYERS, "1..8 layers per net (hidden layers + output layer)");
-    EGP_REQUIRE(activation >= 0 && activation <= 2 && vactivation >= 0 && vactivation <= 2, "activation: 0 tanh, 1 relu, 2 sigmoid");
-    EGP_REQUIRE(ctx_dim >= 0 && vctx_dim >= 0 && ctx_row_stride >= 0 && vctx_row_stride >= 0, "bad context dims");
-    const int dim = ctx->dm.obs_dim;
-    PolFilter f{};
-    if (zf_in)
-        if (int rc = pol_filter_of(ctx, qpos, qvel, phase_t, n, zf_in, zf_out, clip, y, y2, nullptr, f)) return rc;
-    PolNets P{{{ctx_rows, (long)ctx_row_stride, ctx_dim, activation, 0, {}}, {vctx_rows, (long)vctx_row_stride, vctx_dim, vactivation, 0, {}}}};
-    PolNet &A = P.net[0], &V = P.net[1];
-    int kmax;
-    size_t lds_a, lds_v;
-    if (int rc = pol_layer_table(nullptr, layers, n_layers, ctx_dim + dim, "policy layer dims do not chain", A.L, &kmax)) return rc;
-    if (int rc = pol_lds(A.L, kmax, 0, zf_in ? 2 * dim : 0, &A.xs, &lds_a)) return rc;
-    if (int rc = pol_layer_table(nullptr, vlayers, n_vlayers, vctx_dim + dim, "value layer dims do not chain", V.L, &kmax)) return rc;
-    if (int rc = pol_lds(V.L, kmax, 0, zf_in ? 2 * dim : 0, &V.xs, &lds_v)) return rc;
-    EGP_REQUIRE(vlayers[n_vlayers - 1].out_dim == 1, "the value net's last layer is the value head (out_dim 1)");
-    const size_t lds = lds_a > lds_v ? lds_a : lds_v;
-    const dim3 grid((n + POL_R - 1) / POL_R, 2), block(POL_NW * 64);
-#define POL_GO(FLT) k_policy_value_w4<POL_R, POL_PF, FLT><<<grid, block, lds, (hipStream_t)stream>>>(                                       \
-        P, (const long long *)t_idx, y, dim, n, log_std, noise, action, mean_out, value_out, f)
-    if (zf_in) POL_GO(true); else POL_GO(false);
+// Every form of the policy step (include/egopose_hip.h: egp_policy_desc): validated once, then one launch of the plain kernel, of
+// the forecast kernel (d->cell: one step of the state LSTM cell in front, see forecast_body) or of the actor + critic kernel
+// (d->vlayers, k_policy_value_w4), each with the filter's apply pass in front (d->zf_in, see PolFilter) or without.
+extern "C" int egp_policy_step_f32(const egp_policy_desc *d, void *stream) {
+    EGP_REQUIRE(d, "desc is NULL");
+    EGP_REQUIRE(d->n >= 0, "n < 0");
+    EGP_REQUIRE(d->stage_bytes >= 0 && d->stage_bytes % 4 == 0 && d->stage_bytes < (1ll << 31) && (d->stage_bytes == 0 || (d->stage_src && d->stage_dst)),
+                "bad staging slab");
+    if (d->n == 0) return EGP_OK;
+    const bool cell = d->cell, both = d->vlayers, flt = d->zf_in;
+    EGP_REQUIRE(!cell || !both, "cell with vlayers: no kernel runs the LSTM cell and the critic together");
+    EGP_REQUIRE(d->stage_bytes == 0 || (!cell && !both), "a staging slab rides in the plain step only (no cell, no vlayers)");
+    EGP_REQUIRE(!both || !d->zf_workspace, "the actor + critic step normalises with frozen statistics only (zf_workspace == NULL)");
+    PolFilter F{};
+    if (flt)
+        if (int rc = pol_filter(d, !cell, F)) return rc;
+    const int n = d->n, ctx_dim = d->ctx_dim, state_dim = flt ? d->ctx->dm.obs_dim : d->state_dim;
+    EGP_REQUIRE((d->state || flt) && d->layers && d->action && (cell || (d->ctx_rows && d->t_idx)) && (!both || (d->vctx_rows && d->value_out)), "NULL pointer");
+    EGP_REQUIRE(!cell || (d->h && d->c && d->h != d->c), "NULL pointer (or h == c)");
+    EGP_REQUIRE(!cell || (ctx_dim >= 0 && (ctx_dim == 0 || (d->ctx_rows && d->t_idx))), "bad context");
+    EGP_REQUIRE(!d->noise || d->log_std, "noise needs log_std");
+    EGP_REQUIRE(d->n_layers >= 1 && d->n_layers + (cell ? 1 : 0) <= POL_MAX_LAYERS,
+                cell ? "1..7 layers (hidden layers + output layer) behind the cell" : "1..8 layers (hidden layers + output layer)");
+    EGP_REQUIRE(d->activation >= 0 && d->activation <= 2, "activation: 0 tanh, 1 relu, 2 sigmoid");
+    int hs = 0;
+    if (cell) {
+        const egp_mlp_layer *cl = d->cell;
+        EGP_REQUIRE(cl->wt && cl->bias && ((uintptr_t)cl->wt & 15) == 0, "cell: NULL or misaligned packed weights");
+        EGP_REQUIRE(cl->out_dim >= 4 && cl->out_dim % 4 == 0 && cl->out_dim <= 2048, "cell: out_dim = 4 x hidden size, at most 2048");
+        hs = cl->out_dim / 4;
+        EGP_REQUIRE(state_dim >= 1 && cl->in_dim == state_dim + hs && cl->in_dim <= 2048, "cell: in_dim = state_dim + hidden size, at most 2048");
+        EGP_REQUIRE(d->hc_row_stride >= hs, "h / c row stride below the hidden size");
+    } else {
+        EGP_REQUIRE(ctx_dim >= 0 && state_dim >= 0 && ctx_dim + state_dim > 0, "bad input dims");
+    }
+    PolLayers L;
+    int kmax, xs;
+    size_t lds;
+    if (int rc = pol_layer_table(d->cell, d->layers, d->n_layers, ctx_dim + (cell ? hs : state_dim),
+                                 cell ? "layer dims do not chain (first layer: ctx_dim + hidden size)"
+                                      : both ? "policy layer dims do not chain" : "layer dims do not chain", L, &kmax)) return rc;
+    // the tail: the cell's c rows, and with the filter its merged mean | 1 / std (behind the pad float)
+    const int ms = flt ? 2 * state_dim : 0;
+    if (int rc = pol_lds(L, kmax, POL_R * hs, ms, &xs, &lds)) return rc;
+    const dim3 block(POL_NW * 64);
+    dim3 grid((n + POL_R - 1) / POL_R);
+    const long long *t_idx = (const long long *)d->t_idx;
+#define POL_GO(KERNEL, ...) do {                                                                                        \
+        if (flt) KERNEL<POL_R, POL_PF, true><<<grid, block, lds, (hipStream_t)stream>>>(__VA_ARGS__);                    \
+        else KERNEL<POL_R, POL_PF, false><<<grid, block, lds, (hipStream_t)stream>>>(__VA_ARGS__);                       \
+    } while (0)
+    if (!cell && !both) {
+        POL_GO(k_policy_gaussian_w4, d->ctx_rows, (long)d->ctx_row_stride, ctx_dim, t_idx, d->state, state_dim, n, L, d->activation, xs, d->log_std,
+               d->noise, d->action, d->mean_out, d->stage_bytes ? (const unsigned *)d->stage_src : nullptr, (unsigned *)d->stage_dst,
+               (int)(d->stage_bytes / 4), F);
+        return pol_launched("k_policy_gaussian");
+    }
+    if (cell) {
+        POL_GO(k_policy_forecast_w4, d->ctx_rows, (long)d->ctx_row_stride, ctx_dim, t_idx, d->state, state_dim, d->h, d->c, (long)d->hc_row_stride, hs, n,
+               L, d->activation, xs, d->log_std, d->noise, d->action, d->mean_out, F);
+        return pol_launched("k_policy_forecast");
+    }
+    // the critic's own layer table and carve-up; the launch's dynamic LDS is the larger of the two
+    EGP_REQUIRE(d->n_vlayers >= 1 && d->n_vlayers <= POL_MAX_LAYERS, "1..8 layers per net (hidden layers + output layer)");
+    EGP_REQUIRE(d->vactivation >= 0 && d->vactivation <= 2, "activation: 0 tanh, 1 relu, 2 sigmoid");
+    EGP_REQUIRE(d->vctx_dim >= 0 && d->ctx_row_stride >= 0 && d->vctx_row_stride >= 0, "bad context dims");
+    PolNets P{{{d->ctx_rows, (long)d->ctx_row_stride, ctx_dim, d->activation, xs, L},
+               {d->vctx_rows, (long)d->vctx_row_stride, d->vctx_dim, d->vactivation, 0, {}}}};
+    PolNet &V = P.net[1];
+    size_t lds_v;
+    if (int rc = pol_layer_table(nullptr, d->vlayers, d->n_vlayers, d->vctx_dim + state_dim, "value layer dims do not chain", V.L, &kmax)) return rc;
+    if (int rc = pol_lds(V.L, kmax, 0, ms, &V.xs, &lds_v)) return rc;
+    EGP_REQUIRE(d->vlayers[d->n_vlayers - 1].out_dim == 1, "the value net's last layer is the value head (out_dim 1)");
+    if (lds_v > lds) lds = lds_v;
+    grid.y = 2;
+    POL_GO(k_policy_value_w4, P, t_idx, d->state, state_dim, n, d->log_std, d->noise, d->action, d->mean_out, d->value_out, F);
 #undef POL_GO
     return pol_launched("k_policy_value");
 }

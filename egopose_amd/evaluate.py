@@ -15,7 +15,7 @@ in lockstep, in passes of N takes in take order, and a tick is
     record qpos / qvel -> [observation -> frozen filter -> policy MLP -> mean action | value MLP -> value] -> env-step
     -> host: fail-safe decision per slot -> re-seat the flagged slots on their take's state_pred[t + 1]
 
-with the bracket one launch (`FusedActorCritic.with_filter`, egp_policy_value_filter_f32) and the values' copy to pinned memory
+with the bracket one launch (`FusedActorCritic.with_filter`, egp_policy_step_f32 (vlayers)) and the values' copy to pinned memory
 queued behind it. The pass itself -- the batched env, the frozen filter's device state, seating and re-seating slots, the records and
 their copy-out, a tick's event / env-step / timed wait -- is `lockstep_eval.LockstepPass`, shared with the forecast evaluation; the
 launch, the value copy and the host decision are here. The video contexts and the state regressor's predictions of a take are

@@ -8,7 +8,7 @@ windows run here as the slots of `env.batched(N)` in strict lockstep, in passes 
 
     record qpos -> [observation -> frozen normalisation -> state-LSTM cell -> MLP -> mean action] -> env-step
 
-with the bracket one launch (`FusedForecastPolicy.with_filter(..., workspace=None)`, egp_policy_forecast_filter_f32). The pass
+with the bracket one launch (`FusedForecastPolicy.with_filter(..., workspace=None)`, egp_policy_step_f32 (cell + filter block)). The pass
 around it -- slots, frozen filter state, records, env-step and timed wait -- is `lockstep_eval.LockstepPass`, shared with the
 ego_mimic evaluation; the plan, the launch with its LSTM state and the `failed` log are here.
 

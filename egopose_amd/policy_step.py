@@ -1,12 +1,13 @@
-"""Rollout-time policy step through `egp_policy_gaussian_f32` (csrc/egp_policy.hip): the VideoStateNet concat, the MLP
+"""Rollout-time policy step through `egp_policy_step_f32` (csrc/egp_policy.hip): the VideoStateNet concat, the MLP
 and the Gaussian head of the reference's `policy_net.select_action` (core/agent.py:38-44, models/policy_gaussian.py:
 19-27, models/mlp.py:5-25) for a whole env group in one launch. The module keeps transposed float32 copies of the
 weights, packed for the kernel's matrix-core tiles, in persistent buffers (`refresh()` re-reads the live parameters,
-addresses stay fixed for hipGraphs). `FusedForecastPolicy` is the ego_forecast form (`egp_policy_forecast_f32`): one step
-of VideoForecastNet's state LSTM cell (models/video_forecast_net.py:88-93, models/rnn.py:29-36) in front of the same MLP,
-the cell's h / c updated in place; its `with_filter` (`egp_policy_forecast_filter_f32`) puts the observation filter's apply
-pass in front of it, merged with a tick's tile statistics or frozen. `FusedActorCritic` is the ego_mimic evaluation's tick
-(`egp_policy_value_filter_f32`): the frozen filter, the policy step and the value net of the same rows in one launch."""
+addresses stay fixed for hipGraphs). Every class fills one `egp_policy_desc` per call. `FusedForecastPolicy` is the
+ego_forecast form (the descriptor's `cell`): one step of VideoForecastNet's state LSTM cell (models/video_forecast_net.py:
+88-93, models/rnn.py:29-36) in front of the same MLP, the cell's h / c updated in place; its `with_filter` (the filter
+block) puts the observation filter's apply pass in front of it, merged with a tick's tile statistics or frozen.
+`FusedActorCritic` is the ego_mimic evaluation's tick (the descriptor's `vlayers`): the frozen filter, the policy step and
+the value net of the same rows in one launch."""
 from __future__ import annotations
 
 import ctypes as C
@@ -19,8 +20,8 @@ from . import _lib as L
 _ACT_CODE = {torch.tanh: 0, torch.relu: 1, torch.sigmoid: 2}
 
 
-def _ptr(t):
-    return C.c_void_p(t.data_ptr()) if t is not None else C.c_void_p(0)
+def _addr(t):
+    return t.data_ptr() if t is not None else None
 
 
 def _check_io(ctx_rows, t_idx, state, action_out, noise, mean_out, nu):
@@ -115,9 +116,27 @@ class FusedGaussianPolicy:
         if H + S != self.in_dim:
             raise ValueError("context dim %d + state dim %d != policy input %d" % (H, S, self.in_dim))
         _check_io(ctx_rows, t_idx, state, action_out, noise, mean_out, self.nu)
-        L.check(self.lib.egp_policy_gaussian_f32(_ptr(ctx_rows), int(ctx_rows.stride(0)), H, _ptr(t_idx), _ptr(state), S, n, self.desc,
-                                                 len(self.layers), self.act, _ptr(self.log_std), _ptr(noise), _ptr(action_out), _ptr(mean_out),
-                                                 L.current_stream()), "egp_policy_gaussian_f32")
+        d = self._desc(ctx_rows, t_idx, action_out, noise, mean_out)
+        d.state, d.state_dim = _addr(state), S
+        return self._step(d, action_out)
+
+    def _desc(self, ctx_rows, t_idx, action_out, noise, mean_out):
+        """A PolicyDesc (built per call: the tensors change) with the fields every step shares: rows, context, actor, outputs."""
+        d = L.PolicyDesc()
+        d.n, _, d.ctx_dim = ctx_rows.shape
+        d.ctx_rows, d.ctx_row_stride, d.t_idx = _addr(ctx_rows), ctx_rows.stride(0), _addr(t_idx)
+        d.layers, d.n_layers, d.activation, d.log_std = self.desc, len(self.layers), self.act, _addr(self.log_std)
+        d.noise, d.action, d.mean_out = _addr(noise), _addr(action_out), _addr(mean_out)
+        return d
+
+    def _filter(self, d, ctx, qpos, qvel, phase_t, zf_in, zf_out, clip, y, y2, workspace):
+        """The descriptor's filter block."""
+        d.ctx, d.qpos, d.qvel, d.phase_t = ctx.handle, _addr(qpos), _addr(qvel), _addr(ctx._phase_t(phase_t, d.n))
+        d.zf_in, d.zf_out, d.clip = _addr(zf_in), _addr(zf_out), float(clip or 0.0)
+        d.y, d.y2, d.zf_workspace = _addr(y), _addr(y2), _addr(workspace)
+
+    def _step(self, d, action_out):
+        L.check(self.lib.egp_policy_step_f32(C.byref(d), L.current_stream()), "egp_policy_step_f32")
         return action_out
 
     def _zf_scratch(self, zf_in):
@@ -127,24 +146,20 @@ class FusedGaussianPolicy:
 
     def with_filter(self, ctx, ctx_rows, t_idx, qpos, qvel, zf_in, zf_out, clip, y, y2, workspace, action_out, noise=None, mean_out=None,
                     phase_t=None):
-        """The filter's apply pass + the policy step in one launch (`egp_policy_gaussian_filter_f32`): the state columns are the
+        """The filter's apply pass + the policy step in one launch (`egp_policy_step_f32` with the filter block): the state columns are the
         observations of (qpos, qvel) normalised with `zf_in` merged with the tile statistics `ctx.obs_zfilter_stats` left in
         `workspace`; y / y2 receive them, `zf_out` the merged statistics. `workspace=None`: `zf_in` as it stands -- the frozen
         filter of an evaluation, `running_state(x, update=False)`; `zf_out` may be None then. `ctx`: the EgpContext of the model."""
         n, T, H = ctx_rows.shape
         if workspace is None and zf_out is None:      # the frozen filter (`zf_in` as it stands): the kernel still writes its copy of the statistics
             zf_out = self._zf_scratch(zf_in)
-        L.check(self.lib.egp_policy_gaussian_filter_f32(ctx.handle, _ptr(ctx_rows), int(ctx_rows.stride(0)), H, _ptr(t_idx), _ptr(qpos), _ptr(qvel),
-                                                        _ptr(ctx._phase_t(phase_t, n)), n,
-                                                        _ptr(zf_in), _ptr(zf_out), float(clip or 0.0), _ptr(y), _ptr(y2), _ptr(workspace),
-                                                        C.cast(self.desc, C.c_void_p), len(self.layers), self.act, _ptr(self.log_std), _ptr(noise),
-                                                        _ptr(action_out), _ptr(mean_out), None, None, 0, L.current_stream()),
-                "egp_policy_gaussian_filter_f32")
-        return action_out
+        d = self._desc(ctx_rows, t_idx, action_out, noise, mean_out)
+        self._filter(d, ctx, qpos, qvel, phase_t, zf_in, zf_out, clip, y, y2, workspace)
+        return self._step(d, action_out)
 
 
 class FusedForecastPolicy(FusedGaussianPolicy):
-    """The ego_forecast tick in one launch (`egp_policy_forecast_f32`): state LSTM cell step, [context | h'] -> MLP -> Gaussian
+    """The ego_forecast tick in one launch (`egp_policy_step_f32` with `cell`): state LSTM cell step, [context | h'] -> MLP -> Gaussian
     head, h / c written back in place. The cell's packed gate layer sits in front of the MLP's in `wt_all`."""
 
     def __init__(self, policy_net, vs_net, device):
@@ -181,14 +196,17 @@ class FusedForecastPolicy(FusedGaussianPolicy):
         for t in (h, c):
             assert t.dtype == torch.float32 and t.shape == (n, self.Hs) and t.stride(1) == 1 and t.stride(0) == h.stride(0) >= self.Hs
         assert h.data_ptr() != c.data_ptr()
-        L.check(self.lib.egp_policy_forecast_f32(_ptr(ctx_rows), int(ctx_rows.stride(0)), H, _ptr(t_idx), _ptr(state), self.S, self.cell_desc,
-                                                 _ptr(h), _ptr(c), int(h.stride(0)), n, self.desc, len(self.layers), self.act, _ptr(self.log_std),
-                                                 _ptr(noise), _ptr(action_out), _ptr(mean_out), L.current_stream()), "egp_policy_forecast_f32")
-        return action_out
+        d = self._desc(ctx_rows, t_idx, action_out, noise, mean_out)
+        d.state, d.state_dim = _addr(state), self.S
+        return self._step(self._cell(d, h, c), action_out)
+
+    def _cell(self, d, h, c):
+        d.cell, d.h, d.c, d.hc_row_stride = self.cell_desc, _addr(h), _addr(c), h.stride(0)
+        return d
 
     def with_filter(self, ctx, ctx_rows, t_idx, qpos, qvel, zf_in, zf_out, clip, y, y2, workspace, h, c, action_out, noise=None, mean_out=None,
                     phase_t=None):
-        """The filter's apply pass + the forecast step in one launch (`egp_policy_forecast_filter_f32`): the cell's state input is
+        """The filter's apply pass + the forecast step in one launch (`cell` and the filter block): the cell's state input is
         the observation of (qpos, qvel), normalised with `zf_in` merged with the tile statistics `ctx.obs_zfilter_stats` left in
         `workspace` (`zf_out` receives the merged statistics), or with `workspace=None` with `zf_in` as it stands -- the frozen
         filter of an evaluation, `running_state(x, update=False)`; `zf_out` may be None then. y (and y2, optional): float64
@@ -214,17 +232,13 @@ class FusedForecastPolicy(FusedGaussianPolicy):
             return self(ctx_rows, t_idx, y, h, c, action_out, noise=noise, mean_out=mean_out)
         for t in (zf_in, zf_out):
             assert t is None or (t.dtype == torch.float64 and t.is_contiguous() and t.shape == (1 + 2 * S,))
-        L.check(self.lib.egp_policy_forecast_filter_f32(ctx.handle, _ptr(ctx_rows), int(ctx_rows.stride(0)), H, _ptr(t_idx), _ptr(qpos), _ptr(qvel),
-                                                        _ptr(ctx._phase_t(phase_t, n)), n, _ptr(zf_in), _ptr(zf_out), float(clip or 0.0),
-                                                        _ptr(y), _ptr(y2), _ptr(workspace), self.cell_desc, _ptr(h), _ptr(c), int(h.stride(0)),
-                                                        self.desc, len(self.layers), self.act, _ptr(self.log_std), _ptr(noise),
-                                                        _ptr(action_out), _ptr(mean_out), L.current_stream()),
-                "egp_policy_forecast_filter_f32")
-        return action_out
+        d = self._desc(ctx_rows, t_idx, action_out, noise, mean_out)
+        self._filter(d, ctx, qpos, qvel, phase_t, zf_in, zf_out, clip, y, y2, workspace)
+        return self._step(self._cell(d, h, c), action_out)
 
 
 class FusedActorCritic(FusedGaussianPolicy):
-    """The ego_mimic evaluation's tick in one launch (`egp_policy_value_filter_f32`): observation -> frozen filter ->
+    """The ego_mimic evaluation's tick in one launch (`egp_policy_step_f32` with `vlayers`): observation -> frozen filter ->
     [policy context row | state] -> policy MLP -> Gaussian head, and [value context row | state] -> value MLP -> value_head for
     the same rows. The value net's packed layers sit behind the policy's in `wt_all`."""
 
@@ -283,10 +297,11 @@ class FusedActorCritic(FusedGaussianPolicy):
                 assert t is None or (t.dtype == torch.float64 and t.is_contiguous() and t.shape == (1 + 2 * S,))
             if zf_out is None:
                 zf_out = self._zf_scratch(zf_in)
-        L.check(self.lib.egp_policy_value_filter_f32(ctx.handle, _ptr(ctx_rows), int(ctx_rows.stride(0)), H, _ptr(value_ctx_rows),
-                                                     int(value_ctx_rows.stride(0)), Hv, _ptr(t_idx), _ptr(qpos), _ptr(qvel),
-                                                     _ptr(ctx._phase_t(phase_t, n)), n, _ptr(zf_in), _ptr(zf_out), float(clip or 0.0), _ptr(y), _ptr(y2),
-                                                     self.desc, len(self.layers), self.act, _ptr(self.log_std), _ptr(noise), _ptr(action_out),
-                                                     _ptr(mean_out), self.vdesc, len(self.vlayers), self.vact, _ptr(value_out), L.current_stream()),
-                "egp_policy_value_filter_f32")
-        return action_out
+        d = self._desc(ctx_rows, t_idx, action_out, noise, mean_out)
+        if zf_in is None:
+            d.state, d.state_dim = _addr(y), S
+        else:
+            self._filter(d, ctx, qpos, qvel, phase_t, zf_in, zf_out, clip, y, y2, None)
+        d.vctx_rows, d.vctx_row_stride, d.vctx_dim = _addr(value_ctx_rows), value_ctx_rows.stride(0), Hv
+        d.vlayers, d.n_vlayers, d.vactivation, d.value_out = self.vdesc, len(self.vlayers), self.vact, _addr(value_out)
+        return self._step(d, action_out)

@@ -230,7 +230,7 @@ int egp_obs_zfilter_f32(egp_ctx *ctx, const float *qpos, const float *qvel, cons
 /* egp_obs_zfilter_f64 (all rows written, no write mask) in two calls, for batches of at most egp_obs_zfilter_split_max_rows() rows:
  * _stats = its first launch (tile statistics of the rows with active != 0 into `workspace`), _apply = its second (merge into
  * state_in -> state_out, normalise, clip, write y / y2): the same kernels with the same arguments, bit-identical results.
- * The apply pass can instead ride in the policy step that consumes y2 (egp_policy_gaussian_filter_f32). */
+ * The apply pass can instead ride in the policy step that consumes y2 (egp_policy_step_f32, the descriptor's filter block). */
 int32_t egp_obs_zfilter_split_max_rows(void);
 int egp_obs_zfilter_stats_f64(egp_ctx *ctx, const double *qpos, const double *qvel, const int32_t *phase_t, const int32_t *active, int32_t n, void *workspace,
                               void *stream);
@@ -570,87 +570,70 @@ typedef struct egp_mlp_layer {
 /* nn.Linear weight W[out_dim][in_dim] (device, row stride ldw floats) -> packed (device, egp_mlp_pack_floats(in_dim, out_dim) floats) */
 int64_t egp_mlp_pack_floats(int32_t in_dim, int32_t out_dim);
 int egp_mlp_pack_f32(const float *weight, int64_t ldw, int32_t in_dim, int32_t out_dim, float *packed, void *stream);
-int egp_policy_gaussian_f32(const float *ctx_rows, int64_t ctx_row_stride, int32_t ctx_dim, const int64_t *t_idx,
-                            const double *state, int32_t state_dim, int32_t n, const egp_mlp_layer *layers,
-                            int32_t n_layers, int32_t activation, const float *log_std, const float *noise,
-                            double *action, float *mean_out, void *stream);
-/* The same launch also moving a staging slab: `stage_bytes` (a multiple of 4) bytes from `stage_src` -- device-visible pinned
- * host memory, `t_idx` may point into it -- to `stage_dst` in HBM, spread over the launch's workgroups. The rollout's tick
- * uses it for its per-tick flag slab (egp_rollout_tick.slab_host / slab_dev) instead of a copy-engine transfer in front of
- * the policy step; kernels launched later on the stream read `stage_dst`. */
-int egp_policy_gaussian_staged_f32(const float *ctx_rows, int64_t ctx_row_stride, int32_t ctx_dim, const int64_t *t_idx,
-                                   const double *state, int32_t state_dim, int32_t n, const egp_mlp_layer *layers,
-                                   int32_t n_layers, int32_t activation, const float *log_std, const float *noise,
-                                   double *action, float *mean_out, const void *stage_src, void *stage_dst, int64_t stage_bytes,
-                                   void *stream);
-/* ... with the observation filter's apply pass in front (agents/agent.py:50-51 followed by :42-46 of the next step: the filtered
- * next state IS the policy's next input): the state columns of the policy input are the observations of (qpos, qvel) -- the
- * group's n rows, n <= egp_obs_zfilter_split_max_rows() -- normalised with `zf_in` merged with the tile statistics that
- * egp_obs_zfilter_stats_f64 left in `zf_workspace`; they are written to y (and y2) and the merged statistics to zf_out. One launch
- * computes exactly what egp_obs_zfilter_apply_f64 followed by egp_policy_gaussian_staged_f32 on y2 computes (bit-identical). */
-int egp_policy_gaussian_filter_f32(egp_ctx *ctx, const float *ctx_rows, int64_t ctx_row_stride, int32_t ctx_dim, const int64_t *t_idx,
-                                   const double *qpos, const double *qvel, const int32_t *phase_t, int32_t n, const double *zf_in, double *zf_out,
-                                   double clip, double *y, double *y2, const void *zf_workspace,
-                                   const egp_mlp_layer *layers, int32_t n_layers, int32_t activation, const float *log_std,
-                                   const float *noise, double *action, float *mean_out, const void *stage_src, void *stage_dst,
-                                   int64_t stage_bytes, void *stream);
-/* zf_workspace == NULL in egp_policy_gaussian_filter_f32 (frozen statistics): normalises with `zf_in` as it stands --
- * ZFilter.__call__(x, update=False) of utils/zfilter.py, what an evaluation does; zf_out receives a copy of zf_in; no row limit.
- *
- * Actor and critic of an evaluation tick in one launch (ego_mimic_eval.py:147-161 for all takes of a pass at once): per row r the
- * observation of (qpos, qvel), the frozen filter (`zf_in` as it stands; y, and y2 when non-NULL, receive the normalised rows,
- * zf_out a copy of zf_in), then
- *   [ctx_rows [r*ctx_row_stride  + t_idx[r]*ctx_dim  ...] | state] -> layers  -> Gaussian head -> action[r] (and mean_out[r])
- *   [vctx_rows[r*vctx_row_stride + t_idx[r]*vctx_dim ...] | state] -> vlayers -> value_out[r]   (float32)
- * `vlayers` are the value net's MLP and, last, its value_head (out_dim 1; hidden layers with `vactivation`). The launch's grid has a
- * second dimension that selects the net: the actor's workgroups run the code of egp_policy_gaussian_filter_f32 with zf_workspace ==
- * NULL (action, mean_out, y, y2 bit-identical to it), the critic's repeat the normalisation for themselves; no workgroup depends on
- * another. zf_in == NULL (a checkpoint without running_state): no filter -- `y` must already hold the rows' states ([n][obs_dim],
- * e.g. from egp_obs_f64) and is only read; qpos, qvel, zf_out, y2 are unused. Rows >= n of every output are untouched. No
- * allocation, no synchronisation, capturable; n == 0 returns EGP_OK. */
-int egp_policy_value_filter_f32(egp_ctx *ctx, const float *ctx_rows, int64_t ctx_row_stride, int32_t ctx_dim, const float *vctx_rows,
-                                int64_t vctx_row_stride, int32_t vctx_dim, const int64_t *t_idx, const double *qpos, const double *qvel,
-                                const int32_t *phase_t, int32_t n, const double *zf_in, double *zf_out, double clip, double *y, double *y2,
-                                const egp_mlp_layer *layers, int32_t n_layers, int32_t activation, const float *log_std,
-                                const float *noise, double *action, float *mean_out, const egp_mlp_layer *vlayers, int32_t n_vlayers,
-                                int32_t vactivation, float *value_out, void *stream);
-/* The ego_forecast policy step in one launch: the state goes through ONE STEP of the state LSTM before it joins the video
- * context (VideoForecastNet in test mode, models/video_forecast_net.py:88-93, over the step-mode cell of models/rnn.py:29-36;
- * torch's nn.LSTMCell, gate order i, f, g, o), then the MLP and the Gaussian head exactly as egp_policy_gaussian_f32:
- *   s = float(state[r]);  pre = W_ih s + b_ih + W_hh h[r] + b_hh
- *   c' = sigmoid(f) c[r] + sigmoid(i) tanh(g);  h' = sigmoid(o) tanh(c')
- *   x[r] = [ctx_rows[r*ctx_row_stride + t_idx[r]*ctx_dim ...] | h'] -> layers -> action[r] (and mean_out[r])
- * h and c (float32, row r at r * hc_row_stride, hidden size Hs = cell->out_dim / 4) are updated IN PLACE: a row is read before it
- * is written, and only rows 0 .. n - 1 are touched -- the rollout passes row slices of its per-slot buffers.
- * `cell` is the gate pre-activation as one more packed layer: in_dim = state_dim + Hs, out_dim = 4 Hs,
- *   wt   = egp_mlp_pack_f32 of the [4 Hs][state_dim + Hs] matrix whose row 4 u + g is [W_ih[g Hs + u] | W_hh[g Hs + u]]
- *          (the four gates g = 0..3 = i, f, g, o of unit u in adjacent columns), bias[4 u + g] = b_ih[g Hs + u] + b_hh[g Hs + u].
- * `layers` (n_layers <= 7) are the MLP and the output layer; layers[0].in_dim = ctx_dim + Hs. Limits: state_dim >= 1, Hs >= 1,
- * 4 Hs <= 2048, state_dim + Hs <= 2048, ctx_dim >= 0 (ctx_rows / t_idx may be NULL when it is 0). float32 accumulation in a
- * fixed order (a row's result does not depend on n or on the row's position); expf / tanhf, no fast approximations. No
- * allocation, no synchronisation: the launch can be captured in a hipGraph. n == 0 returns EGP_OK. */
-int egp_policy_forecast_f32(const float *ctx_rows, int64_t ctx_row_stride, int32_t ctx_dim, const int64_t *t_idx,
-                            const double *state, int32_t state_dim, const egp_mlp_layer *cell, float *h, float *c,
-                            int64_t hc_row_stride, int32_t n, const egp_mlp_layer *layers, int32_t n_layers, int32_t activation,
-                            const float *log_std, const float *noise, double *action, float *mean_out, void *stream);
-/* ... with the observation filter's apply pass in front, the forecast counterpart of egp_policy_gaussian_filter_f32: the cell's
- * state input is the observation of (qpos, qvel) row r (width: the model's obs_dim, the phase column from `phase_t` included
- * when it has obs_phase; cell->in_dim = obs_dim + Hs), normalised and clipped as egp_obs_zfilter_apply_f64 does, written to y
- * (and y2 when non-NULL; float64 [n][obs_dim]) and cast to float32 on its way into the cell. Everything from the cell on is
- * egp_policy_forecast_f32.
- *   zf_workspace != NULL (merged statistics): `zf_in` is merged with the tile statistics that egp_obs_zfilter_stats_f64 left in
- *     the workspace (same ordered merge) and the merged state goes to zf_out; needs zf_out != NULL and
- *     n <= egp_obs_zfilter_split_max_rows(). One launch computes exactly what egp_obs_zfilter_apply_f64 followed by
- *     egp_policy_forecast_f32 on y2 computes (bit-identical).
- *   zf_workspace == NULL (frozen statistics): normalises with `zf_in` as it stands -- ZFilter.__call__(x, update=False) of
- *     utils/zfilter.py, what an evaluation does; zf_out may be NULL and receives a copy of zf_in otherwise; no row limit.
- * zf_out != zf_in. No allocation, no synchronisation, capturable; n == 0 returns EGP_OK. */
-int egp_policy_forecast_filter_f32(egp_ctx *ctx, const float *ctx_rows, int64_t ctx_row_stride, int32_t ctx_dim, const int64_t *t_idx,
-                                   const double *qpos, const double *qvel, const int32_t *phase_t, int32_t n,
-                                   const double *zf_in, double *zf_out, double clip, double *y, double *y2, const void *zf_workspace,
-                                   const egp_mlp_layer *cell, float *h, float *c, int64_t hc_row_stride,
-                                   const egp_mlp_layer *layers, int32_t n_layers, int32_t activation, const float *log_std,
-                                   const float *noise, double *action, float *mean_out, void *stream);
+/* One descriptor for every form of the step; egp_policy_step_f32 validates it and launches one kernel: the plain step, the
+ * forecast step (`cell` != NULL) or the actor + critic step (`vlayers` != NULL), each with the filter block on (`zf_in` != NULL)
+ * or off. A zeroed descriptor with the fields of one's form filled in is valid; `cell` with `vlayers`, a staging slab with either,
+ * and `zf_workspace` with `vlayers` are refused (no kernel serves them). float32 accumulation in a fixed order (a row's result
+ * does not depend on n or on the row's position); expf / tanhf, no fast approximations. Rows >= n of every output are untouched.
+ * No allocation, no synchronisation: the launch can be captured in a hipGraph. n == 0 returns EGP_OK. */
+typedef struct egp_policy_desc {
+    /* Rows and context. ctx_dim >= 0; ctx_rows and t_idx are required (the forecast step: only when ctx_dim > 0). */
+    int32_t n;
+    const float *ctx_rows; int64_t ctx_row_stride; int32_t ctx_dim;
+    const int64_t *t_idx;
+    /* State input, zf_in == NULL: the rows' states as they are, float64 [n][state_dim]. */
+    const double *state; int32_t state_dim;
+    /* State input, zf_in != NULL: the observation filter's apply pass in front (agents/agent.py:50-51 followed by :42-46 of the
+     * next step: the filtered next state IS the policy's next input). The state columns are the observations of (qpos, qvel) row r
+     * (width: the obs_dim of `ctx`'s model, the phase column from `phase_t` -- the rows' cur_t -- included when it has obs_phase;
+     * `state` / `state_dim` are unused), normalised and clipped as egp_obs_zfilter_apply_f64 does, written to y (and y2 when
+     * non-NULL; float64 [n][obs_dim]) and cast to float32 on their way into the net.
+     *   zf_workspace != NULL (merged statistics): `zf_in` is merged with the tile statistics that egp_obs_zfilter_stats_f64 left in
+     *     the workspace (same ordered merge) and the merged state goes to zf_out; needs n <= egp_obs_zfilter_split_max_rows().
+     *     One launch computes exactly what egp_obs_zfilter_apply_f64 followed by the unfiltered step on y2 computes (bit-identical).
+     *   zf_workspace == NULL (frozen statistics): normalises with `zf_in` as it stands -- ZFilter.__call__(x, update=False) of
+     *     utils/zfilter.py, what an evaluation does; zf_out receives a copy of zf_in; no row limit.
+     * zf_out != zf_in; zf_out is required, except in the forecast step with frozen statistics. */
+    egp_ctx *ctx;
+    const double *qpos; const double *qvel; const int32_t *phase_t;
+    const double *zf_in; double *zf_out; double clip;
+    double *y; double *y2;
+    const void *zf_workspace;
+    /* Actor: 1..8 packed layers (1..7 behind a cell), the formulas above. noise needs log_std; mean_out may be NULL. */
+    const egp_mlp_layer *layers; int32_t n_layers, activation;
+    const float *log_std; const float *noise;
+    double *action; float *mean_out;
+    /* Optional LSTM cell in front -- the ego_forecast step: the state goes through ONE STEP of the state LSTM before it joins the
+     * video context (VideoForecastNet in test mode, models/video_forecast_net.py:88-93, over the step-mode cell of
+     * models/rnn.py:29-36; torch's nn.LSTMCell, gate order i, f, g, o), then the MLP and the Gaussian head exactly as without it:
+     *   s = float(state[r]);  pre = W_ih s + b_ih + W_hh h[r] + b_hh
+     *   c' = sigmoid(f) c[r] + sigmoid(i) tanh(g);  h' = sigmoid(o) tanh(c')
+     *   x[r] = [ctx_rows[r*ctx_row_stride + t_idx[r]*ctx_dim ...] | h'] -> layers -> action[r] (and mean_out[r])
+     * h and c (float32, row r at r * hc_row_stride, hidden size Hs = cell->out_dim / 4, h != c) are updated IN PLACE: a row is read
+     * before it is written, and only rows 0 .. n - 1 are touched -- the rollout passes row slices of its per-slot buffers.
+     * `cell` is the gate pre-activation as one more packed layer: in_dim = state_dim + Hs, out_dim = 4 Hs,
+     *   wt   = egp_mlp_pack_f32 of the [4 Hs][state_dim + Hs] matrix whose row 4 u + g is [W_ih[g Hs + u] | W_hh[g Hs + u]]
+     *          (the four gates g = 0..3 = i, f, g, o of unit u in adjacent columns), bias[4 u + g] = b_ih[g Hs + u] + b_hh[g Hs + u].
+     * layers[0].in_dim = ctx_dim + Hs. Limits: state_dim >= 1, Hs >= 1, 4 Hs <= 2048, state_dim + Hs <= 2048. */
+    const egp_mlp_layer *cell;
+    float *h; float *c; int64_t hc_row_stride;
+    /* Optional critic -- actor and critic of an evaluation tick in one launch (ego_mimic_eval.py:147-161 for all takes of a pass
+     * at once), frozen statistics only:
+     *   [ctx_rows [r*ctx_row_stride  + t_idx[r]*ctx_dim  ...] | state] -> layers  -> Gaussian head -> action[r] (and mean_out[r])
+     *   [vctx_rows[r*vctx_row_stride + t_idx[r]*vctx_dim ...] | state] -> vlayers -> value_out[r]   (float32)
+     * `vlayers` are the value net's MLP and, last, its value_head (out_dim 1; hidden layers with `vactivation`). The launch's grid
+     * has a second dimension that selects the net: the actor's workgroups run the code of the plain step (action, mean_out, y, y2
+     * bit-identical to it), the critic's repeat the normalisation for themselves; no workgroup depends on another. */
+    const float *vctx_rows; int64_t vctx_row_stride; int32_t vctx_dim;
+    const egp_mlp_layer *vlayers; int32_t n_vlayers, vactivation;
+    float *value_out;
+    /* Optional staging slab, the plain step only: the launch also moves `stage_bytes` (a multiple of 4) bytes from `stage_src`
+     * -- device-visible pinned host memory, `t_idx` may point into it -- to `stage_dst` in HBM, spread over its workgroups. The
+     * rollout's tick uses it for its per-tick flag slab (egp_rollout_tick.slab_host / slab_dev) instead of a copy-engine transfer
+     * in front of the policy step; kernels launched later on the stream read `stage_dst`. */
+    const void *stage_src; void *stage_dst; int64_t stage_bytes;
+} egp_policy_desc;
+int egp_policy_step_f32(const egp_policy_desc *desc, void *stream);
 
 /* ----------------------------------------------------------------------------------------
  * Host physics boundary (replaces mujoco_py's MjSim inside HumanoidEnv: envs/common/mujoco_env.py:84-105,
@@ -763,7 +746,7 @@ int egp_engine_group_range(egp_engine *e, int32_t group, int32_t *env_begin, int
  * Python (flags of the coming env-step, their upload, the fused policy step, the reward job, the env-step; then the wait,
  * K3 + K6, K2 and the termination flags of HumanoidEnv.step, ego_pose/envs/humanoid_v1.py:182-199). The driver fills the
  * descriptor once per rollout; the arrays are its own (NumPy / device tensors) and stay valid for the rollout.
- *   the tick's flag slab (pinned) reaches its device copy inside the policy step (egp_policy_gaussian_staged_f32 / _filter_f32)
+ *   the tick's flag slab (pinned) reaches its device copy inside the policy step (egp_policy_step_f32's staging slab)
  *   pre : flags / context rows of tick k for slots [a, b) -> policy -> env-step (asynchronous)
  *   post: wait for the env-step, observation + filter into states[k + 1] / next_states[k], reward, cur_t / done / record rows;
  *         *n_done = slots whose episode ended, *wait_s = seconds blocked on the env-step */

@@ -665,7 +665,7 @@ def test_engine_follows_changing_inertia(ctx, skel, mode, monkeypatch):
 @pytest.mark.parametrize("act,hidden,n", [("relu", (300, 200), 517), ("tanh", (64,), 3), ("sigmoid", (130, 70, 33), 64),
                                           ("tanh", (330, 6), 5)])
 def test_fused_policy_step_matches_torch(act, hidden, n):
-    """egp_policy_gaussian_f32 == cat(v_out[t], state) -> MLP -> action_mean -> mean + exp(log_std) * noise in torch
+    """egp_policy_step_f32 (plain) == cat(v_out[t], state) -> MLP -> action_mean -> mean + exp(log_std) * noise in torch
     (float32; tolerance 2e-5 relative to the output scale: different summation order only).
     (330, 6): a hidden layer of two column chunks (> 5 x 64) whose width is no multiple of 4 -- the zeroed pad columns of its
     last quad feed the next layer -- on two workgroups, the second ragged."""
@@ -707,7 +707,7 @@ def test_fused_policy_step_matches_torch(act, hidden, n):
 
 def test_fused_policy_step_matches_the_reference_policy_vectors():
     """policy_value.npz -- PolicyGaussian over MLP[10, 6] evaluated by the REFERENCE (core/policy_gaussian.py:19-24, models/mlp.py:22-25)
-    -- straight through `egp_policy_gaussian_f32`: the golden input's first 5 columns play the video context, the other 8 the
+    -- straight through `egp_policy_step_f32` (plain): the golden input's first 5 columns play the video context, the other 8 the
     state. float32 kernel against the reference's float64 numbers: 1e-5 (one link, no torch module in between)."""
     from egopose_amd.nets import MLP, PolicyGaussian
     from egopose_amd import policy_step
@@ -729,6 +729,37 @@ def test_fused_policy_step_matches_the_reference_policy_vectors():
     noise = torch.as_tensor((g["a"] - g["mean"]) / g["std"], dtype=torch.float32, device="cuda")      # the draw that gave the golden action
     fp(v_out, t_idx, state, act, noise=noise)
     np.testing.assert_allclose(act.cpu().numpy(), g["a"], rtol=1e-5, atol=1e-5)
+
+
+def test_policy_desc_filled_by_hand_equals_the_wrapper():
+    """The plain step through an `egp_policy_desc` written out field by field here, on 5 rows of the policy_value.npz net: the
+    same bits as `FusedGaussianPolicy.__call__` -- the field mapping, held without the wrapper's helpers."""
+    import ctypes
+    from egopose_amd.nets import MLP, PolicyGaussian
+    from egopose_amd import policy_step, _lib as L
+    g = load_golden("policy_value.npz")
+    pol = PolicyGaussian(MLP(13, [10, 6], "relu"), 4, log_std=-2.3, fix_std=True)
+    pol.load_state_dict({k[4:]: torch.as_tensor(g[k], dtype=torch.float32) for k in g.files if k.startswith("pol_")}, strict=True)
+    fp = policy_step.FusedGaussianPolicy(pol.cuda(), torch.device("cuda"))
+    n, H, T = 5, 5, 3
+    torch.manual_seed(5)
+    v_out = torch.randn(n, T, H, device="cuda")
+    t_idx = torch.tensor([i % T for i in range(n)], device="cuda")
+    state = torch.as_tensor(g["x"][:n, H:], device="cuda").contiguous()
+    noise = torch.randn(n, 4, device="cuda")
+    want, want_mean = torch.empty(n, 4, dtype=torch.float64, device="cuda"), torch.empty(n, 4, device="cuda")
+    fp(v_out, t_idx, state, want, noise=noise, mean_out=want_mean)
+    got, got_mean = torch.full_like(want, -9.0), torch.full_like(want_mean, -9.0)
+    d = L.PolicyDesc()
+    d.n = n
+    d.ctx_rows, d.ctx_row_stride, d.ctx_dim, d.t_idx = v_out.data_ptr(), T * H, H, t_idx.data_ptr()
+    d.state, d.state_dim = state.data_ptr(), 13 - H
+    d.layers, d.n_layers, d.activation = fp.desc, 3, 1
+    d.log_std, d.noise = fp.log_std.data_ptr(), noise.data_ptr()
+    d.action, d.mean_out = got.data_ptr(), got_mean.data_ptr()
+    L.check(fp.lib.egp_policy_step_f32(ctypes.byref(d), L.current_stream()), "egp_policy_step_f32")
+    assert torch.equal(got, want) and torch.equal(got_mean, want_mean)
+    assert not torch.equal(want, want_mean.double())          # (the noise took part)
 
 
 @pytest.mark.parametrize("mode", ["resident", "per-substep", "resident-2-per-wave"])
@@ -918,7 +949,7 @@ def test_constant_and_pose_dist_rewards_on_device(skel):
 
 @pytest.mark.parametrize("n,H", [(512, 128), (37, 128), (1024, 128), (300, 192), (512, 40)])
 def test_filter_apply_in_the_policy_step_is_bit_identical_to_the_two_launches(ctx, n, H):
-    """egp_obs_zfilter_stats_f64 + egp_policy_gaussian_filter_f32 against egp_obs_zfilter_f64 + egp_policy_gaussian_f32 (what a
+    """egp_obs_zfilter_stats_f64 + egp_policy_step_f32 (filter block) against egp_obs_zfilter_f64 + egp_policy_step_f32 (plain) (what a
     rollout tick without resets runs, rollout.py defer_apply): filtered observations, running statistics and actions equal
     bit for bit; so does the split pair stats + apply. Context widths: 128 (shipped; one input column per thread, the thread
     that normalises a state column merges its statistics -- with the merge coefficients shared across the wave), 192 (more

@@ -1,4 +1,4 @@
-"""The ego_mimic evaluation with the takes side by side: the actor + critic step (`egp_policy_value_filter_f32`,
+"""The ego_mimic evaluation with the takes side by side: the actor + critic step (`egp_policy_step_f32` (`vlayers`),
 FusedActorCritic) against the policy step it shares its code with and against float64 chains, and BatchedEvaluator
 (egopose_amd/evaluate.py) replayed by the oracle's CPU env, its `valuefs` decisions against the sequential statistic, its
 independence of the slot count, its pickle and the forecast evaluation that starts from it."""

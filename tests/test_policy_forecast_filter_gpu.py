@@ -1,5 +1,5 @@
-"""The forecast policy step with the observation filter's apply pass in front (`egp_policy_forecast_filter_f32`,
-FusedForecastPolicy.with_filter): bit for bit the chain egp_obs_zfilter_apply_f64 -> egp_policy_forecast_f32 in its merged
+"""The forecast policy step with the observation filter's apply pass in front (`egp_policy_step_f32` (`cell` + filter block),
+FusedForecastPolicy.with_filter): bit for bit the chain egp_obs_zfilter_apply_f64 -> egp_policy_step_f32 (cell) in its merged
 form, ZFilter(update=False) in its frozen form; in-place h / c, argument checks, graph capture."""
 import ctypes as C
 
@@ -196,16 +196,20 @@ def test_rows_beyond_n_untouched_n_zero_and_bad_cell_width(ctxs, fused):
     torch.cuda.synchronize()
     assert torch.equal(h, before[0]) and torch.equal(c, before[1]) and torch.equal(y, before[2])
     # a cell whose input width is not obs_dim + Hs: EGP_E_INVALID
-    p = lambda t: C.c_void_p(t.data_ptr())
+    p = lambda t: t.data_ptr()
     bad = (L.MlpLayer * 1)()
     bad[0].wt, bad[0].bias = fp.cell_desc[0].wt, fp.cell_desc[0].bias
     bad[0].in_dim, bad[0].out_dim = fp.cell_desc[0].in_dim + 1, fp.cell_desc[0].out_dim
-    rc = fp.lib.egp_policy_forecast_filter_f32(ctx.handle, p(d["ctx"]), int(d["ctx"].stride(0)), 128, p(d["t_idx"]), p(d["qpos"]), p(d["qvel"]), None, n,
-                                               p(d["st"]), None, 5.0, p(y), None, None, bad, p(h), p(c), 128, fp.desc, len(fp.layers), fp.act,
-                                               p(fp.log_std), None, p(act), None, L.current_stream())
+    pd = L.PolicyDesc()
+    pd.n, pd.ctx_rows, pd.ctx_row_stride, pd.ctx_dim, pd.t_idx = n, p(d["ctx"]), d["ctx"].stride(0), 128, p(d["t_idx"])
+    pd.ctx, pd.qpos, pd.qvel, pd.zf_in, pd.clip, pd.y = ctx.handle, p(d["qpos"]), p(d["qvel"]), p(d["st"]), 5.0, p(y)
+    pd.layers, pd.n_layers, pd.activation, pd.log_std, pd.action = fp.desc, len(fp.layers), fp.act, p(fp.log_std), p(act)
+    pd.cell, pd.h, pd.c, pd.hc_row_stride = bad, p(h), p(c), 128
+    rc = fp.lib.egp_policy_step_f32(C.byref(pd), L.current_stream())
     assert rc == -1
-    with pytest.raises(ValueError, match="egp_policy_forecast_filter_f32"):
-        L.check(rc, "egp_policy_forecast_filter_f32")
+    with pytest.raises(ValueError, match="egp_policy_step_f32") as err:
+        L.check(rc, "egp_policy_step_f32")
+    assert "cell: in_dim = state_dim + hidden size" in str(err.value)
     # merged statistics need zf_out
     with pytest.raises(ValueError):
         fp.with_filter(ctx, d["ctx"][:n], d["t_idx"][:n], d["qpos"][:n], d["qvel"][:n], d["st"], None, 5.0, y[:n], None, d["ws"], h[:n], c[:n], act[:n])

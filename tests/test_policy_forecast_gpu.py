@@ -1,4 +1,4 @@
-"""The ego_forecast policy step in one launch (`egp_policy_forecast_f32`, policy_step.FusedForecastPolicy): one step of the
+"""The ego_forecast policy step in one launch (`egp_policy_step_f32` (`cell`), policy_step.FusedForecastPolicy): one step of the
 state LSTM cell, [video context | h'] -> MLP -> Gaussian head, h / c updated in place -- against the reference's own
 vectors, against float64 torch at the configs' widths, and inside the lockstep rollout."""
 import copy

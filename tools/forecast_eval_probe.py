@@ -2,7 +2,7 @@
 """The two figures profiles/forecast_eval.md asks for, one JSON line:
 
   (a) per-launch time of FusedForecastPolicy.with_filter (frozen and merged form) at 512 rows against the two-launch pair
-      obs_zfilter_apply + egp_policy_forecast_f32 (the merged form's and the pair's statistics pass is launched once, outside
+      obs_zfilter_apply + egp_policy_step_f32 (cell) (the merged form's and the pair's statistics pass is launched once, outside
       the timed loops: all three read the same workspace), HIP events over `--launches` launches after `--warm` warm-up launches;
   (b) wall time of ForecastEvaluator.run on a synthetic dataset at `--slots` slots, split into host physics wait and the rest.
 
