@@ -168,6 +168,26 @@ class AdamSegment(C.Structure):
 ADAM_MAX_SEGMENTS = 8
 
 
+class GailRowsDesc(C.Structure):
+    """egp_gail_rows_desc (include/egopose_hip.h)."""
+    _fields_ = [("n", C.c_int32), ("H", C.c_int32), ("S", C.c_int32),
+                ("ctx", vp), ("ld_ctx", C.c_int64), ("ctx_rows", C.c_int64),
+                ("idx", vp),
+                ("x", vp), ("ldx", C.c_int64),
+                ("tab", vp), ("ld_tab", C.c_int64), ("tab_rows", C.c_int64),
+                ("src", vp), ("src_host", vp),
+                ("mean", vp), ("inv_std", vp),
+                ("out", vp), ("ldo", C.c_int64),
+                ("dout", vp), ("dctx", vp)]
+
+
+class BceLogitsDesc(C.Structure):
+    """egp_bce_logits_desc (include/egopose_hip.h)."""
+    _fields_ = [("n", C.c_int32), ("n_e", C.c_int32), ("z", vp),
+                ("inv_n_g", C.c_double), ("inv_n_e", C.c_double),
+                ("dz", vp), ("score_out", vp), ("losses", vp), ("workspace", vp)]
+
+
 class RolloutTick(C.Structure):
     """egp_rollout_tick (include/egopose_hip.h): field order and types must match the header."""
     _fields_ = [("ctx", vp), ("eng", vp), ("stream", vp),
@@ -254,6 +274,10 @@ SIGNATURES = {
     "egp_ppo_loss_f32": (C.c_int, [C.POINTER(PpoLossDesc), vp]),
     "egp_minibatch_plan_f32": (C.c_int, [C.POINTER(MinibatchPlanDesc), vp]),
     "egp_ppo_loss_mb_f32": (C.c_int, [C.POINTER(PpoLossMbDesc), vp]),
+    "egp_gail_rows_f32": (C.c_int, [C.POINTER(GailRowsDesc), vp]),
+    "egp_gail_rows_bwd_f32": (C.c_int, [C.POINTER(GailRowsDesc), vp]),
+    "egp_bce_logits_workspace_bytes": (_i64, [_i32]),
+    "egp_bce_logits_f32": (C.c_int, [C.POINTER(BceLogitsDesc), vp]),
     "egp_tcn_conv_f32": (C.c_int, [C.POINTER(TcnDesc), vp]),
     "egp_adam_workspace_bytes": (_i64, []),
     "egp_adam_step_f32": (C.c_int, [_i32, C.POINTER(AdamSegment), vp, vp, vp, vp, vp, vp, vp]),

@@ -4,6 +4,7 @@
   AgentPG    agents/agent_pg.py:7-57     update_value / update_policy (A2C) / update_params
   AgentPPO   agents/agent_ppo.py:6-65    clipped-surrogate update, grad-norm clip
   AgentEgo   ego_pose/core/agent_ego.py:8-57   video-context nets, v_metas, TrajBatchEgo
+  AgentVGAIL ego_pose/core/agent_vgail.py:7-88 AgentEgo + a video-conditioned GAIL discriminator trained after every PPO update
 
 Constructor keywords are the reference's. ``sample`` does not fork Python workers: it drives
 ``LockstepRollout`` over ``num_envs`` env slots of this rank's GPU (``num_threads`` becomes the number of
@@ -747,4 +748,362 @@ class AgentEgo(AgentPPO):
             self.update_policy(c["states"], c["actions"], returns, advantages, c["exps"], counts=counts)
         if dev.type == "cuda":
             torch.cuda.synchronize(dev)
+        return time.time() - t0
+
+
+class AgentVGAIL(AgentEgo):
+    """ego_pose/core/agent_vgail.py:7-88: an AgentEgo whose update also trains a discriminator between the learner's
+    observations and the expert's, both seen through a video net of the discriminator's own.
+
+    Constructor keywords are the reference's (:9-18) plus three whose defaults give the reference's behaviour:
+      discrim_grad_clip      the constant of :70 (clip_grad_norm_ over discrim_net's parameters only)
+      expert_obs             "reference": the expert rows as data_process/gen_expert.py:40-43 wrote them -- `qvel` was never set there,
+                             so their velocity columns are ZERO and a discriminator separates the classes by those columns alone;
+                             "fd": rows derived with the takes' finite-difference velocities (expert.expert_obs_rows)
+      discrim_reward_weight  w > 0: rewards <- (1 - w) rewards + w (-log D(vs(s))) on the device before GAE. No reference code reads
+                             the discriminator (as written the class trains a net nobody uses); 0 keeps that.
+
+    `update_discriminator` has two forms behind `use_fused_discrim`: the plain one is the reference's loop in torch ops on any
+    device and dtype; the fused one (float32 on the GPU, a `nets.Discriminator`, nn.BCELoss with mean reduction, a VideoStateNet,
+    no dropout) sweeps the video net ONCE per step -- in train mode its context rows depend on the CNN features only, so the
+    reference's two calls (:60-61) compute the same rows twice -- and runs one stacked [generated; expert] block through the MLP."""
+
+    def __init__(self, discrim_net=None, discrim_vs_net=None, discrim_criterion=None, optimizer_discrim=None, discrim_num_update=10,
+                 discrim_grad_clip=40.0, expert_obs="reference", discrim_reward_weight=0.0, **kwargs):
+        from .expert import OBS_MODES
+        if expert_obs not in OBS_MODES:
+            raise ValueError("expert_obs must be one of %s, got %r" % (OBS_MODES, expert_obs))
+        if getattr(getattr(kwargs.get("env"), "cfg", None), "obs_phase", False):
+            raise NotImplementedError("AgentVGAIL with cfg.obs_phase: the phase column depends on the episode, not on the take's frame, "
+                                      "so the expert's rows have no such column")
+        self.discrim_net, self.discrim_vs_net = discrim_net, discrim_vs_net          # (before the base classes bind the compute nets)
+        super().__init__(**kwargs)
+        self.discrim_criterion = discrim_criterion
+        self.optimizer_discrim = optimizer_discrim
+        self.discrim_num_update = discrim_num_update
+        self.discrim_grad_clip = discrim_grad_clip
+        self.expert_obs = expert_obs
+        self.discrim_reward_weight = float(discrim_reward_weight)
+        self.use_fused_discrim = True       # A/B handle: one sweep + one stacked block + HIP loss tail per step instead of the reference's loop
+        self._discrim_updater = None        # optim.FlatUpdater of optimizer_discrim once built; False = not eligible
+        self._discrim_sync = None
+        self._expert_rows = None            # host rows of every take (expert.expert_obs_rows)
+        self._expert_table = {}
+        self._gail_batch = None
+        self._prefetch_deferred = False
+        self.discrim_stats = {}             # discrim_net's gradient norm of the last step, before and after the clip
+        self.last_e_loss = None             # what update_params' update_discriminator returned
+
+    def _master_nets(self):
+        nets = super()._master_nets()
+        nets.update(discrim_net=getattr(self, "discrim_net", None), discrim_vs_net=getattr(self, "discrim_vs_net", None))
+        return nets
+
+    def _bind_compute_nets(self):
+        super()._bind_compute_nets()
+        extra = [m for m in (getattr(self.cn, "discrim_net", None), getattr(self.cn, "discrim_vs_net", None)) if m is not None]
+        self.sample_modules = self.sample_modules + extra          # agent_vgail.py:17-18
+        self.update_modules = self.update_modules + extra
+
+    def _params_stepped(self):
+        up = getattr(self, "_discrim_updater", None) or None
+        if up is not None:
+            up.rebind()
+        super()._params_stepped()
+
+    def _epochs_enqueued(self):
+        # inside update_params the next sampling pass is set up behind the DISCRIMINATOR's last step, not behind the PPO epochs:
+        # the set-up puts policy_vs_net into 'test' mode, and discrim_vs_net adopts its train context of this batch first
+        if self._gail_batch is not None:
+            self._prefetch_deferred = True
+            return
+        super()._epochs_enqueued()
+
+    def _discrim_enqueued(self):
+        """Hook: every launch of the discriminator update is on the stream, its loss has not been read yet."""
+        if self._prefetch_deferred:
+            self._prefetch_deferred = False
+            super()._epochs_enqueued()
+
+    def pre_sample(self):
+        super().pre_sample()
+        self.cn.discrim_vs_net.set_mode("test")
+
+    def pre_episode(self):
+        super().pre_episode()
+        self.cn.discrim_vs_net.initialize(torch.as_tensor(self.env.get_episode_cnn_feat()))
+
+    # -- the expert's rows ------------------------------------------------------------------------------
+    def _expert_obs_host(self):
+        if self._expert_rows is None:
+            from .expert import expert_obs_rows
+            arr = self.env.expert_arr
+            derived = self.expert_obs != "reference" or not all("obs" in e for e in arr)
+            obs_dim = getattr(self.env, "obs_dim", None)
+            rows = expert_obs_rows(arr, self._kernel_ctx() if derived else None, self.expert_obs, obs_dim)
+            self._expert_rows = (rows, np.concatenate([[0], np.cumsum([r.shape[0] for r in rows])]).astype(np.int64))
+        return self._expert_rows
+
+    def _expert_obs_table(self, device, dtype):
+        key = (str(device), dtype)
+        if key not in self._expert_table:
+            ex = self._rollout.experts if self._rollout is not None else None
+            if ex is not None and ex.expert_arr is self.env.expert_arr:
+                tab = ex.obs_table(self._kernel_ctx(), device, dtype, self.expert_obs, getattr(self.env, "obs_dim", None))[0]
+            else:
+                tab = torch.as_tensor(np.ascontiguousarray(np.concatenate(self._expert_obs_host()[0], 0)), dtype=dtype, device=device)
+            self._expert_table[key] = tab
+        return self._expert_table[key]
+
+    def _expert_src(self, v_metas, masks):
+        """Table row of every sample (agent_vgail.py:77-85): episode e covers rows [start_ind, start_ind + len_e) of take exp_ind."""
+        rows, offset = self._expert_obs_host()
+        mk = masks.detach().cpu().numpy() if torch.is_tensor(masks) else np.asarray(masks)
+        end = np.where(mk.reshape(-1) == 0)[0]
+        if end.size == 0 or end[-1] != mk.size - 1:
+            raise ValueError("the batch must end with an episode end: the expert's rows are taken per whole episode")
+        meta = np.asarray(v_metas)[end, :].astype(np.int64)
+        lens = np.diff(np.insert(end, 0, -1))
+        e_ind, s_ind = meta[:, 0], meta[:, 1]
+        if e_ind.min() < 0 or e_ind.max() >= len(rows):
+            raise ValueError("take index out of range: [%d, %d] with %d takes" % (e_ind.min(), e_ind.max(), len(rows)))
+        take_len = np.diff(offset)[e_ind]
+        bad = (s_ind < 0) | (s_ind + lens > take_len)
+        if bad.any():
+            k = int(np.nonzero(bad)[0][0])
+            raise ValueError("expert rows [%d, %d) leave take %d (%d frames)" % (s_ind[k], s_ind[k] + lens[k], e_ind[k], take_len[k]))
+        return np.repeat(offset[e_ind] + s_ind, lens) + (np.arange(mk.size) - np.repeat(np.insert(end[:-1] + 1, 0, 0), lens))
+
+    def get_expert_states(self, v_metas, masks):
+        """agent_vgail.py:75-88: the expert's observation of every sample's frame, normalised with the running filter's mean and
+        std (no clip), as a tensor of the agent's dtype on its device. A slice that leaves its take raises ValueError (the
+        reference's numpy slice would silently come up short)."""
+        src = self._expert_src(v_metas, masks)
+        expert_states = np.concatenate(self._expert_obs_host()[0], 0)[src]
+        if self.running_state is not None:
+            rs = self.running_state.rs
+            expert_states = (expert_states - rs.mean[None, :]) / rs.std[None, :]
+        return torch.from_numpy(np.ascontiguousarray(expert_states)).to(self.dtype).to(self.device)
+
+    # -- the discriminator update -------------------------------------------------------------------
+    def _discrim_params(self):
+        return [p for g in self.optimizer_discrim.param_groups for p in g["params"]]
+
+    def _discrim_clip_list(self):
+        c = self.discrim_grad_clip
+        return [(list(self.discrim_net.parameters()), float(c))] if c is not None and c > 0 else []
+
+    def _get_discrim_updater(self):
+        if self._discrim_updater is None:
+            up = None
+            if torch.device(self.device).type == "cuda" and self.use_fused_optim and self.optimizer_discrim is not None:
+                compute_of = {m: c for m, c in self.shadow.pairs} if self.shadow is not None else None
+                up = O.FlatUpdater.build([self.optimizer_discrim], self._discrim_clip_list(), compute_of)
+            self._discrim_updater = up if up is not None else False
+        return self._discrim_updater or None
+
+    def _fused_discrim(self):
+        from .nets import Discriminator, VideoStateNet
+        dn, vs, crit = self.cn.discrim_net, self.cn.discrim_vs_net, self.discrim_criterion
+        return (self.use_fused_discrim and torch.device(self.device).type == "cuda" and self.cdtype == torch.float32
+                and isinstance(dn, Discriminator) and all(p.dtype == torch.float32 for p in dn.parameters())
+                and type(crit) is torch.nn.BCELoss and crit.reduction == "mean" and crit.weight is None
+                and isinstance(vs, VideoStateNet) and not self._dropout_active())
+
+    def _init_discrim_context(self, masks, v_metas, adopt):
+        """discrim_vs_net in train mode on this batch (agent_vgail.py:56-57); inside update_params it adopts the policy net's
+        segmentation of the same batch instead of repeating it."""
+        vs = self.cn.discrim_vs_net
+        if self._rollout is not None and self._rollout.experts is not None and hasattr(vs, "attach_feature_table"):
+            ex = self._rollout.experts
+            vs.attach_feature_table(ex.cnn_table(masks.device, next(vs.parameters()).dtype), ex.cnn_offset)
+        vs.set_mode("train")
+        x_init = (masks, self.env.cnn_feat, v_metas)
+        if adopt and self.share_train_context and hasattr(vs, "adopt_train_context"):
+            vs.adopt_train_context(self.cn.policy_vs_net, x_init)
+        else:
+            vs.initialize(x_init)
+
+    def update_discriminator(self, states, masks, v_metas, _adopt=False):
+        """perform discriminator update (agent_vgail.py:54-73) -> e_loss, the last step's expert loss, as a float."""
+        to_train(self.cn.discrim_net, self.cn.discrim_vs_net)
+        self._params_stepped()              # (a call of its own, after a checkpoint load: the compute copies follow the caller's modules)
+        dev = torch.device(self.device)
+        states, masks = states.to(dev).to(self.cdtype), masks.to(dev).to(self.cdtype)
+        v_metas = np.asarray(v_metas.cpu() if torch.is_tensor(v_metas) else v_metas)
+        src_host = self._expert_src(v_metas, masks)         # (first: a slice that leaves its take is reported as such)
+        self._init_discrim_context(masks, v_metas, _adopt)
+        vs = self.cn.discrim_vs_net
+        if self._fused_discrim() and vs._gather_unique and vs._buckets is None and states.shape[0] > 0:
+            return self._update_discriminator_fused(states, src_host)
+        return self._update_discriminator_plain(states, masks, v_metas)
+
+    def _update_discriminator_plain(self, states, masks, v_metas):
+        dev = states.device
+        expert_states = self.get_expert_states(v_metas, masks).to(self.cdtype)
+        vs, dn, crit, opt = self.cn.discrim_vs_net, self.cn.discrim_net, self.discrim_criterion, self.optimizer_discrim
+        n = states.shape[0]
+        multi = D.world_size() > 1
+        share = n / D.global_count(n, dev) if multi else None          # mean over this rank's rows -> its share of the global mean
+        if multi and self._discrim_sync is None:
+            self._discrim_sync = D.FlatGradSync(self._discrim_params())
+        clip = self.discrim_grad_clip
+        l_e = norm = None
+        for _ in range(self.discrim_num_update):
+            g_vs_out = vs(states)
+            e_vs_out = vs(expert_states)
+            g_o = dn(g_vs_out)
+            e_o = dn(e_vs_out)
+            if multi:
+                self._discrim_sync.attach()
+            else:
+                opt.zero_grad()
+            if self.shadow is not None:
+                self.shadow.zero_grad()
+            l_g = crit(g_o, torch.ones((g_o.size(0), 1), dtype=g_o.dtype, device=dev))
+            l_e = crit(e_o, torch.zeros((e_o.size(0), 1), dtype=e_o.dtype, device=dev))
+            if multi:
+                l_g, l_e = l_g * share, l_e * share
+            discrim_loss = l_g + l_e
+            discrim_loss.backward()
+            if self.shadow is not None:
+                self.shadow.push_grads()
+            if multi:
+                self._discrim_sync.all_reduce()
+            if clip is not None and clip > 0:
+                norm = torch.nn.utils.clip_grad_norm_(self.discrim_net.parameters(), clip)
+            opt.step()
+            if self.shadow is not None:
+                self.shadow.pull()
+        self._discrim_enqueued()
+        if l_e is None:
+            return 0.0
+        l_e = l_e.detach().double()
+        if multi:
+            l_e = l_e.to(D._comm_device(dev))
+            torch.distributed.all_reduce(l_e)
+            D._note()
+        self._record_discrim_norm(norm, clip)
+        return l_e.item()
+
+    def _record_discrim_norm(self, norm, clip):
+        """discrim_stats: discrim_net's gradient norm of the last step, before and after the clip."""
+        if norm is None:
+            self.discrim_stats = {}
+            return
+        norm = float(norm)
+        self.discrim_stats = {"grad_norm": norm, "clipped_norm": norm * min(1.0, float(clip) / (norm + 1e-6))}
+
+    def _update_discriminator_fused(self, states, src_host):
+        """Per step: ONE sweep of discrim_vs_net -> optim.gail_rows (the [generated; expert] block from the context rows, the
+        states and the expert table) -> Discriminator.logits on the 2n rows -> optim.bce_logits (both losses, d loss / d logits)
+        -> autograd from (logits, dz) through the MLP and GailRows into the sweep -> clip + Adam (FlatUpdater; the clip group
+        holds discrim_net's parameters only, :70). The host reads nothing until the last step is queued."""
+        from .nets import grouped_video_context
+        dev = states.device
+        vs, dn = self.cn.discrim_vs_net, self.cn.discrim_net
+        n = states.shape[0]
+        src = torch.as_tensor(src_host, dtype=torch.int64, device=dev)
+        tab = self._expert_obs_table(dev, torch.float32)
+        mean = inv_std = None
+        if self.running_state is not None:
+            rs = self.running_state.rs
+            mean = torch.as_tensor(np.asarray(rs.mean, np.float64), dtype=torch.float32, device=dev).contiguous()
+            inv_std = torch.as_tensor(1.0 / np.asarray(rs.std, np.float64), dtype=torch.float32, device=dev).contiguous()
+        x = states if states.stride(1) == 1 else states.contiguous()
+        n_glob = D.global_count(n, dev)
+        up = self._get_discrim_updater()
+        if up is None and D.world_size() > 1 and self._discrim_sync is None:
+            self._discrim_sync = D.FlatGradSync(self._discrim_params())
+        steps = int(self.discrim_num_update)
+        rec = torch.zeros(max(1, steps), 2, dtype=torch.float64, device=dev)
+        dz = torch.empty(2 * n, 1, dtype=torch.float32, device=dev)
+        clip = self.discrim_grad_clip
+        norm = None
+        for step in range(steps):
+            grouped_video_context([vs])                     # (a bi-LSTM's two directions in one grouped launch; else the net runs itself)
+            ctx2d = vs.context_rows().contiguous()
+            X = O.GailRows.apply(ctx2d, vs._gather_tm, x, tab, src, mean, inv_std)
+            X._egp_ctx_cols = vs.v_hdim                     # the trailing columns are data: no input gradient needed there
+            z = dn.logits(X)
+            if up is not None:
+                up.zero_grad()
+            else:
+                self.optimizer_discrim.zero_grad()
+                if self.shadow is not None:
+                    self.shadow.zero_grad()
+            O.bce_logits(z.detach(), n_glob, n_glob, dz=dz, losses_out=rec[step])
+            torch.autograd.backward([z], [dz])
+            if up is not None:
+                up.collect_grads()
+                up.all_reduce()
+                up.step()
+            else:                                           # not Adam (or use_fused_optim off): the caller's optimizer steps
+                if self.shadow is not None:
+                    self.shadow.push_grads()
+                if self._discrim_sync is not None:
+                    self._discrim_sync.all_reduce()
+                if clip is not None and clip > 0:
+                    norm = torch.nn.utils.clip_grad_norm_(self.discrim_net.parameters(), clip)
+                self.optimizer_discrim.step()
+                if self.shadow is not None:
+                    self.shadow.pull()
+        self._discrim_enqueued()
+        if steps < 1:
+            return 0.0
+        if up is not None and clip is not None and clip > 0:
+            norm = up.norms[1]
+        e_loss = rec[steps - 1, 1]
+        if D.world_size() > 1:
+            e_loss = e_loss.to(D._comm_device(dev))
+            torch.distributed.all_reduce(e_loss)
+            D._note()
+        self._record_discrim_norm(norm, clip)
+        return e_loss.item()
+
+    # -- the discriminator as a reward ----------------------------------------------------------------
+    def discriminator_scores(self, batch):
+        """-log D(vs(s)) of every row of the batch from one no-grad pass of the current discriminator, on the device. D is trained
+        towards 1 on generated rows (agent_vgail.py:66-67), so a row the discriminator takes for the expert's scores high."""
+        c = self._cols if self._gail_batch is batch and getattr(self, "_cols", None) is not None else self._load_batch(batch)
+        v_metas = self._v_metas_of(batch)
+        vs, dn = self.cn.discrim_vs_net, self.cn.discrim_net
+        with to_test(dn, vs):
+            with torch.no_grad():
+                self._init_discrim_context(c["masks"], v_metas, adopt=self._gail_batch is batch)
+                x = vs(c["states"])
+                if hasattr(dn, "logits"):
+                    z = dn.logits(x)
+                    if z.is_cuda and z.dtype == torch.float32:
+                        return O.bce_scores(z)
+                    return torch.nn.functional.softplus(-z).reshape(-1)
+                return -torch.log(dn(x)).reshape(-1)
+
+    @staticmethod
+    def _v_metas_of(batch):
+        v_metas = batch.device_column("v_metas") if hasattr(batch, "device_column") else None
+        return v_metas.cpu().numpy() if v_metas is not None else np.asarray(batch.v_metas)
+
+    def _load_batch(self, batch):
+        self._cols = super()._load_batch(batch)
+        return self._cols
+
+    def _advantages_with_counts(self, rewards, masks, values, counts):
+        w = self.discrim_reward_weight
+        if w > 0 and self._gail_batch is not None:
+            rewards = (1.0 - w) * rewards + w * self.discriminator_scores(self._gail_batch).to(rewards.dtype)
+        return super()._advantages_with_counts(rewards, masks, values, counts)
+
+    def update_params(self, batch):
+        """AgentEgo.update_params followed by update_discriminator (agent_vgail.py:28-52); the returned time covers both."""
+        t0 = time.time()
+        self._gail_batch, self._cols = batch, None
+        try:
+            super().update_params(batch)
+            c = self._cols if self._cols is not None else self._load_batch(batch)
+            self.last_e_loss = self.update_discriminator(c["states"], c["masks"], self._v_metas_of(batch), _adopt=True)
+        finally:
+            self._gail_batch, self._cols, self._prefetch_deferred = None, None, False
+        if torch.device(self.device).type == "cuda":
+            torch.cuda.synchronize(torch.device(self.device))
         return time.time() - t0

@@ -57,8 +57,61 @@ def build_expert_take(ctx, physics, qpos_seq, lb=0, ub=None):
     return take
 
 
+OBS_MODES = ("reference", "fd")
+
+
+def expert_obs_rows(expert_arr, ctx=None, mode="reference", obs_dim=None):
+    """-> [per take: (len, S) float64] the expert's observation rows (what ego_pose/core/agent_vgail.py:83 reads as
+    `expert_arr[i]['obs']`).
+
+    mode "reference": each take's `obs` array as the pickle has it when EVERY take has one; otherwise derived as
+        data_process/gen_expert.py:40-43 does -- `env.get_obs()` after setting `qpos` only, i.e. K3 on (qpos, zeros): the
+        velocity columns of every row are zero (the reference's own quirk, kept as the default).
+    mode "fd": always derived, with the take's finite-difference `qvel` -- rows comparable to the learner's.
+    `ctx` (hip.EgpContext, the agent's own observation options) serves the derivation; `obs_dim` (default ctx.obs_dim): the
+    width the rows must have."""
+    if mode not in OBS_MODES:
+        raise ValueError("expert_obs must be one of %s, got %r" % (OBS_MODES, mode))
+    want = obs_dim if obs_dim is not None else (ctx.obs_dim if ctx is not None else None)
+    if mode == "reference" and all("obs" in e for e in expert_arr):
+        rows = [np.asarray(e["obs"], dtype=np.float64) for e in expert_arr]
+    else:
+        if ctx is None:
+            raise ValueError("expert observation rows (mode %r) are derived on the device: a kernel context is needed" % mode)
+        if getattr(ctx, "obs_phase", False):
+            raise NotImplementedError("expert observation rows with obs_phase: the phase column depends on the episode, not on the take's frame")
+        dev = torch.device("cuda", ctx.device)
+        rows = []
+        for e in expert_arr:
+            qpos = torch.as_tensor(np.ascontiguousarray(e["qpos"], dtype=np.float64), device=dev)
+            if mode == "fd":
+                qvel = torch.as_tensor(np.ascontiguousarray(e["qvel"], dtype=np.float64), device=dev)
+            else:
+                qvel = torch.zeros(qpos.shape[0], ctx.nv, dtype=torch.float64, device=dev)
+            rows.append(ctx.obs(qpos, qvel).cpu().numpy())
+    for i, r in enumerate(rows):
+        if r.ndim != 2 or (want is not None and r.shape[1] != want):
+            raise ValueError("expert take %d has observation rows of width %s, the env's obs_dim is %s" % (i, r.shape[-1], want))
+    return rows
+
+
 class ExpertSet:
     """All training takes, concatenated; host copies feed resets, device copies feed K2 and the LSTM."""
+
+    def obs_table(self, ctx, device, dtype, mode="reference", obs_dim=None):
+        """-> (table [sum of the takes' lengths][S] on `device`, take_offset): the expert's observation rows of every take
+        (`expert_obs_rows`), concatenated; cached per (device, dtype, mode)."""
+        if self.expert_arr is None:
+            raise ValueError("a features-only set has no expert rows")
+        cache = self.__dict__.setdefault("_obs_table", {})
+        key = (str(device), dtype, mode)
+        if key not in cache:
+            rows = expert_obs_rows(self.expert_arr, ctx, mode, obs_dim)
+            for r, n in zip(rows, self.lens):
+                if r.shape[0] != n:
+                    raise ValueError("a take's observation rows (%d) do not match its length (%d)" % (r.shape[0], n))
+            cache[key] = torch.as_tensor(np.ascontiguousarray(np.concatenate(rows, 0)), dtype=dtype, device=device)
+        return cache[key], self.take_offset
 
     def __init__(self, expert_arr, cnn_feat):
         if len(expert_arr) != len(cnn_feat) or not expert_arr:

@@ -211,6 +211,34 @@ class Value(nn.Module):
         return out if n is None else out[:n]
 
 
+class Discriminator(nn.Module):
+    """The discriminator of ego_pose/core/agent_vgail.py:62-67 (the reference ships the agent, not the net): trunk `net`, one
+    logit per row from `logic`, shaped like `Value`. `forward` is the probability the reference's nn.BCELoss takes;
+    `logits` is what the fused loss (optim.bce_logits) takes."""
+
+    def __init__(self, net, net_out_dim=None):
+        super().__init__()
+        self.net = net
+        self.logic = nn.Linear(net.out_dim if net_out_dim is None else net_out_dim, 1)
+        with torch.no_grad():
+            self.logic.weight.mul_(0.1)
+            self.logic.bias.zero_()
+
+    def logits(self, x):
+        if _gemm.mlp_head_available(x, getattr(self.net, "affine_layers", ()), self.logic, getattr(self.net, "activation", None)):
+            if isinstance(x, _gemm.GatheredInput):
+                return _gemm.gather_mlp_head(x, self.net.affine_layers, self.logic)
+            return _gemm.mlp_head(x, self.net.affine_layers, self.logic, getattr(x, "_egp_ctx_cols", None))
+        if isinstance(x, _gemm.GatheredInput):
+            x = x.materialize()
+        x, n = bucket_rows(x)
+        out = self.logic(self.net(x))
+        return out if n is None else out[:n]
+
+    def forward(self, x):
+        return torch.sigmoid(self.logits(x))
+
+
 # ------------------------------------------------------------------------------------------------ temporal nets
 def _lstm_sweep(cell: nn.LSTMCell, x, reverse):
     """(T,B,D) -> (T,B,H) for one direction; zero initial state."""
@@ -540,6 +568,16 @@ class VideoStateNet(nn.Module):
         if self._buckets is not None:
             ctx = self._bucketed_context()[m:-m].transpose(0, 1).reshape(-1, self.v_hdim)
             return tagged(torch.cat((ctx.index_select(0, self._gather_sorted), x), dim=1))
+        ctx2d = self.context_rows()
+        if self._gather_unique and _gemm.gather_concat_available(ctx2d, self._gather_tm, x):
+            if lazy_width and _gemm.fused_gather_available(self.v_hdim, lazy_width, x.shape[1]):
+                return _gemm.GatheredInput(ctx2d, self._gather_tm, x)            # the consumer's first layer gathers (gemm.GatherMlpHead)
+            return tagged(_gemm.GatherConcat.apply(ctx2d, self._gather_tm, x))  # gather + concatenation in one pass
+        return tagged(torch.cat((ctx2d.index_select(0, self._gather_tm), x), dim=1))
+
+    def context_rows(self):
+        """Train mode: the temporal net over the batch's windows as rows in the net's own (time, episode) order,
+        (T * n_ep, v_hdim); `_gather_tm` holds every sample's row. They depend on the CNN features only, not on the states."""
         ctx = None
         if self._v_ctx is not None:          # computed together with another net's (grouped_video_context)
             (ctx, with_grad), self._v_ctx = self._v_ctx, None
@@ -553,12 +591,7 @@ class VideoStateNet(nn.Module):
                 self.v_net.ragged = None
         elif ctx is None:
             ctx = self.forward_v_net(self.cnn_feat_ctx)
-        ctx2d = ctx.reshape(-1, self.v_hdim)
-        if self._gather_unique and _gemm.gather_concat_available(ctx2d, self._gather_tm, x):
-            if lazy_width and _gemm.fused_gather_available(self.v_hdim, lazy_width, x.shape[1]):
-                return _gemm.GatheredInput(ctx2d, self._gather_tm, x)            # the consumer's first layer gathers (gemm.GatherMlpHead)
-            return tagged(_gemm.GatherConcat.apply(ctx2d, self._gather_tm, x))  # gather + concatenation in one pass
-        return tagged(torch.cat((ctx2d.index_select(0, self._gather_tm), x), dim=1))
+        return ctx.reshape(-1, self.v_hdim)
 
 
 class Bf16Shadow:

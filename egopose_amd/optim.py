@@ -7,6 +7,9 @@
                     epoch's permutation into the caller's buffers + the number of exploration rows of every window, on the device
   ppo_losses_mb(...)   ppo_losses for ONE window of those buffers with shapes that do not depend on the data: the rows with
                     exps == 0 are masked (d_mean = 0), the surrogate's mean divides by the window's device-side count
+  gail_rows(...) / GailRows, bce_logits(...)   the GAIL discriminator step (ego_pose/core/agent_vgail.py:54-73, csrc/egp_gail.hip): the
+                    [generated; expert] input block from one set of video-context rows with its adjoint, and nn.BCELoss on the
+                    logits of that block with d loss / d logits and the per-row score -log D
   FlatUpdater       clip_policy_grad (agent_ppo.py:53-56) + optimizer_value.step() + optimizer_policy.step() (agent_ppo.py:24-30)
                     as two launches over flat buffers. The caller's torch.optim.Adam objects stay the source of every
                     hyper-parameter (`set_optimizer_lr` keeps working) and see the moments as their own state; the parameters of
@@ -188,6 +191,118 @@ def ppo_losses_mb(pred, returns, mean, actions, log_std, adv, fixed_logp, exps, 
     d.losses = losses.data_ptr()
     L.check(lib.egp_ppo_loss_mb_f32(C.byref(d), L.current_stream()), "egp_ppo_loss_mb_f32")
     return losses, d_pred, d_mean, d_ls
+
+
+def _gail_rows_desc(n, H, idx, ctx_rows, ld_ctx, ldo):
+    if not (idx.is_cuda and idx.dtype == torch.int64 and idx.is_contiguous() and idx.numel() == n):
+        raise ValueError("idx must be a contiguous int64 HIP tensor with one entry per sample")
+    d = L.GailRowsDesc()
+    d.n, d.H, d.idx, d.ctx_rows, d.ld_ctx, d.ldo = n, H, idx.data_ptr(), ctx_rows, ld_ctx, ldo
+    return d
+
+
+def gail_rows(ctx2d, idx, x, tab, src, mean=None, inv_std=None, out=None, src_host=None):
+    """-> X (2n, H + S) float32: rows [0, n) = [ctx2d[idx[i]] | x[i]], rows [n, 2n) = [ctx2d[idx[i]] | (tab[src[i]] - mean) * inv_std]
+    (`egp_gail_rows_f32`; mean = inv_std = None: the table rows as they are). `src_host`: the values of `src` on the host (a
+    NumPy int64 array), when the caller has them -- an entry that is no row of `tab` then raises ValueError before the launch."""
+    n, H, S = idx.shape[0], ctx2d.shape[1], x.shape[1]
+    _f32_rows("ctx2d", ctx2d, ctx2d.shape[0])
+    _f32_rows("x", x, n)
+    _f32_rows("tab", tab, tab.shape[0], S)
+    if (mean is None) != (inv_std is None):
+        raise ValueError("mean and inv_std go together")
+    for k, t in (("mean", mean), ("inv_std", inv_std)):
+        if t is not None:
+            _f32_vector(k, t, S)
+    if not (src.is_cuda and src.dtype == torch.int64 and src.is_contiguous() and src.numel() == n):
+        raise ValueError("src must be a contiguous int64 HIP tensor with one entry per sample")
+    if out is None:
+        out = torch.empty(2 * n, H + S, dtype=torch.float32, device=x.device)
+    _f32_rows("out", out, 2 * n, H + S)
+    d = _gail_rows_desc(n, H, idx, ctx2d.shape[0], ctx2d.stride(0) if ctx2d.shape[0] > 1 else H, out.stride(0) if n > 0 else H + S)
+    d.S = S
+    d.ctx = ctx2d.data_ptr()
+    d.x, d.ldx = x.data_ptr(), x.stride(0) if n > 1 else S
+    d.tab, d.ld_tab, d.tab_rows = tab.data_ptr(), tab.stride(0) if tab.shape[0] > 1 else S, tab.shape[0]
+    d.src = src.data_ptr()
+    if src_host is not None:
+        import numpy as np
+        src_host = np.ascontiguousarray(src_host, dtype=np.int64)
+        if src_host.shape != (n,):
+            raise ValueError("src_host must hold one entry per sample")
+        d.src_host = src_host.ctypes.data
+    if mean is not None:
+        d.mean, d.inv_std = mean.data_ptr(), inv_std.data_ptr()
+    d.out = out.data_ptr()
+    L.check(L.load().egp_gail_rows_f32(C.byref(d), L.current_stream()), "egp_gail_rows_f32")
+    return out
+
+
+def gail_rows_bwd(dout, idx, ctx_shape):
+    """-> dctx (ctx_shape) float32: zero, except dctx[idx[i]] = dout[i, :H] + dout[n + i, :H] (`egp_gail_rows_bwd_f32`; idx distinct)."""
+    n = idx.shape[0]
+    R, H = ctx_shape
+    _f32_rows("dout", dout, 2 * n)
+    if dout.shape[1] < H:
+        raise ValueError("dout has fewer columns than the context")
+    dctx = torch.zeros(R, H, dtype=torch.float32, device=dout.device)
+    d = _gail_rows_desc(n, H, idx, R, H, dout.stride(0) if n > 0 else dout.shape[1])
+    d.dout, d.dctx = dout.data_ptr(), dctx.data_ptr()
+    L.check(L.load().egp_gail_rows_bwd_f32(C.byref(d), L.current_stream()), "egp_gail_rows_bwd_f32")
+    return dctx
+
+
+class GailRows(torch.autograd.Function):
+    """gail_rows as an autograd node: gradient to the context only (the states and the expert table need none)."""
+
+    @staticmethod
+    def forward(ctx, ctx2d, idx, x, tab, src, mean, inv_std):
+        ctx.save_for_backward(idx)
+        ctx.shape = tuple(ctx2d.shape)
+        return gail_rows(ctx2d, idx, x, tab, src, mean, inv_std)
+
+    @staticmethod
+    def backward(ctx, dout):
+        (idx,) = ctx.saved_tensors
+        if not ctx.needs_input_grad[0]:
+            return (None,) * 7
+        dout = dout if dout.stride(1) == 1 else dout.contiguous()
+        return (gail_rows_bwd(dout, idx, ctx.shape),) + (None,) * 6
+
+
+def bce_logits(z, n_g, n_e, dz=None, want_dz=True, want_score=False, losses_out=None, expert_rows=None):
+    """-> (losses float64[2] on the device = generated, expert; dz (2n, 1) or None; score (n,) or None) for the logits z (2n, 1) of
+    a [generated; expert] block (`egp_bce_logits_f32`). n_g / n_e: the GLOBAL row counts the two means divide by."""
+    lib = L.load()
+    if expert_rows is None and z.numel() % 2:
+        raise ValueError("z holds the logits of n generated rows followed by n expert rows")
+    rows_e = z.numel() // 2 if expert_rows is None else int(expert_rows)
+    n = z.numel() - rows_e
+    z1 = _f32_vector("z", z.reshape(-1), n + rows_e)
+    dev = z.device
+    if want_dz:
+        dz = torch.empty(n + rows_e, 1, dtype=torch.float32, device=dev) if dz is None else dz
+        _f32_vector("dz", dz.reshape(-1), n + rows_e)
+    else:
+        dz = None
+    score = torch.empty(n, dtype=torch.float32, device=dev) if want_score else None
+    losses = losses_out if losses_out is not None else torch.empty(2, dtype=torch.float64, device=dev)
+    if not (losses.is_cuda and losses.dtype == torch.float64 and losses.is_contiguous() and losses.numel() == 2):
+        raise ValueError("losses_out must be a contiguous float64 HIP tensor of 2 elements")
+    ws = _zeroed_workspace("bce_logits", lib.egp_bce_logits_workspace_bytes(n), dev)
+    d = L.BceLogitsDesc()
+    d.n, d.n_e, d.z = n, rows_e, z1.data_ptr()
+    d.inv_n_g, d.inv_n_e = 1.0 / max(float(n_g), 1.0), 1.0 / max(float(n_e), 1.0)
+    d.dz = dz.data_ptr() if dz is not None else None
+    d.score_out = score.data_ptr() if score is not None else None
+    d.losses, d.workspace = losses.data_ptr(), ws.data_ptr()
+    L.check(lib.egp_bce_logits_f32(C.byref(d), L.current_stream()), "egp_bce_logits_f32")
+    return losses, dz, score
+
+
+def bce_scores(z):
+    """-> softplus(-z) = -log sigmoid(z) per row, (n,) float32: a score-only call of `egp_bce_logits_f32` (no expert rows, no dz)."""
+    return bce_logits(z, z.numel(), 1, want_dz=False, want_score=True, expert_rows=0)[2]
 
 
 class FlatUpdater:

@@ -18,11 +18,11 @@ import torch
 
 from . import dist as D
 from . import gemm_tuning
-from .agent import AgentEgo, compute_dtype
+from .agent import AgentEgo, AgentVGAIL, compute_dtype
 from .config import Config, ForecastConfig
 from .env import HumanoidEnv
 from .logging_utils import Logger, create_logger
-from .nets import MLP, PolicyGaussian, Value, VideoForecastNet, VideoStateNet
+from .nets import MLP, Discriminator, PolicyGaussian, Value, VideoForecastNet, VideoStateNet
 from .reward import reward_func
 from .torch_utils import set_optimizer_lr, to_cpu, to_device
 from .zfilter import ZFilter, dump_reference_pickle, load_reference_pickle
@@ -32,8 +32,10 @@ class Trainer:
     """Everything ego_mimic.py builds at module level, as one object."""
 
     def __init__(self, cfg, device, dtype=torch.float32, num_envs=1024, num_threads=None, num_groups=2, seed_offset=0,
-                 plain_optim=False):
-        """`dtype=torch.float64` is the reference driver's set-up (ego_pose/ego_mimic.py:31-32): float64 modules and
+                 plain_optim=False, gail=None):
+        """`gail` (None, or a dict of AgentVGAIL keywords -- `expert_obs`, `discrim_reward_weight`, `discrim_num_update`,
+        `discrim_grad_clip`; {} = the reference's behaviour): train a GAIL discriminator beside the PPO nets (`--gail`).
+        `dtype=torch.float64` is the reference driver's set-up (ego_pose/ego_mimic.py:31-32): float64 modules and
         state_dicts; on a GPU the agent computes with float32 shadow copies (agent.ShadowNets). `plain_optim=True`
         builds the optimizers exactly as the driver does (no fused Adam)."""
         self.cfg, self.device, self.dtype = cfg, torch.device(device), dtype
@@ -73,13 +75,29 @@ class Trainer:
         value_params = list(self.value_net.parameters()) + list(self.value_vs_net.parameters())
         self.optimizer_policy = self._optimizer(cfg.policy_optimizer, policy_params, cfg.policy_lr, cfg.policy_momentum, cfg.policy_weightdecay)
         self.optimizer_value = self._optimizer(cfg.value_optimizer, value_params, cfg.value_lr, cfg.value_momentum, cfg.value_weightdecay)
-        self.agent = AgentEgo(env=env, dtype=dtype, device=self.device, running_state=self.running_state,
-                              custom_reward=reward_func[cfg.reward_id], mean_action=False, render=False,
-                              num_threads=num_threads, num_envs=num_envs, num_groups=num_groups,
-                              policy_net=self.policy_net, policy_vs_net=self.policy_vs_net, value_net=self.value_net,
-                              value_vs_net=self.value_vs_net, optimizer_policy=self.optimizer_policy,
-                              optimizer_value=self.optimizer_value, opt_num_epochs=cfg.num_optim_epoch, gamma=cfg.gamma,
-                              tau=cfg.tau, clip_epsilon=cfg.clip_epsilon, policy_grad_clip=[(policy_params, 40)])
+        agent_cls, extra = AgentEgo, {}
+        if gail is not None:
+            if self.forecast:
+                raise NotImplementedError("--gail goes with the ego_mimic task (the discriminator sees states through a VideoStateNet)")
+            # the discriminator's nets are shaped like the critic's (its video net, an MLP over [context | state], one output)
+            self.discrim_vs_net = mk_vs(cfg.value_v_hdim, cfg.value_v_net, cfg.value_v_net_param)
+            self.discrim_net = Discriminator(MLP(state_dim + cfg.value_v_hdim, cfg.value_hsize, cfg.value_htype))
+            gail_nets = dict(discrim_dict=self.discrim_net, discrim_vs_dict=self.discrim_vs_net)
+            for net in gail_nets.values():
+                net.to(dtype)
+            to_device(self.device, *gail_nets.values())
+            self.nets.update(gail_nets)
+            self.optimizer_discrim = torch.optim.Adam(list(self.discrim_vs_net.parameters()) + list(self.discrim_net.parameters()), lr=cfg.value_lr)
+            agent_cls = AgentVGAIL
+            extra = dict(discrim_net=self.discrim_net, discrim_vs_net=self.discrim_vs_net, discrim_criterion=torch.nn.BCELoss(),
+                         optimizer_discrim=self.optimizer_discrim, **dict(gail))
+        self.agent = agent_cls(env=env, dtype=dtype, device=self.device, running_state=self.running_state,
+                               custom_reward=reward_func[cfg.reward_id], mean_action=False, render=False,
+                               num_threads=num_threads, num_envs=num_envs, num_groups=num_groups,
+                               policy_net=self.policy_net, policy_vs_net=self.policy_vs_net, value_net=self.value_net,
+                               value_vs_net=self.value_vs_net, optimizer_policy=self.optimizer_policy,
+                               optimizer_value=self.optimizer_value, opt_num_epochs=cfg.num_optim_epoch, gamma=cfg.gamma,
+                               tau=cfg.tau, clip_epsilon=cfg.clip_epsilon, policy_grad_clip=[(policy_params, 40)], **extra)
 
     def _optimizer(self, kind, params, lr, momentum, weight_decay):
         if kind == "Adam":
@@ -120,6 +138,8 @@ class Trainer:
         with open(path, "rb") as f:
             cp = load_reference_pickle(f)
         for k, net in self.nets.items():
+            if k in ("discrim_dict", "discrim_vs_dict") and k not in cp:
+                continue                                  # a checkpoint written without --gail: the discriminator keeps its weights
             net.load_state_dict(cp[k])
         self.running_state = cp["running_state"]
         self.agent.running_state = self.running_state
@@ -158,6 +178,7 @@ def main():
     ap.add_argument("--max-iter", type=int, default=None)
     ap.add_argument("--dtype", choices=["float32", "float64"], default="float32")
     ap.add_argument("--task", choices=["egomimic", "egoforecast"], default="egomimic")
+    ap.add_argument("--gail", action="store_true", help="train a video-conditioned GAIL discriminator beside PPO (AgentVGAIL)")
     args = ap.parse_args()
     rank, world, local = D.init_from_env(args.gpu_index)
     gpu = local if args.gpu_index is None else args.gpu_index
@@ -171,7 +192,8 @@ def main():
         torch.distributed.barrier()
     cfg = (ForecastConfig if args.task == "egoforecast" else Config)(args.cfg, create_dirs=(rank == 0 and args.iter == 0))
     tr = Trainer(cfg, torch.device("cuda", gpu), getattr(torch, args.dtype), num_envs=args.num_envs,
-                 num_threads=args.num_threads or None, seed_offset=rank)
+                 num_threads=args.num_threads or None, seed_offset=rank,
+                 gail={} if args.gail else None)
     logger = create_logger(os.path.join(cfg.log_dir, "log.txt"), file_handle=rank == 0)
     tb = Logger(cfg.tb_dir) if rank == 0 else None
     if args.iter > 0:

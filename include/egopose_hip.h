@@ -411,6 +411,67 @@ int egp_scatter_rows_f32(const float *dout, int64_t ldd, const int64_t *idx, int
 int64_t egp_gemm_workspace_floats(int32_t M, int32_t N, int32_t ones_col, int32_t splits);
 int egp_gemm_f32(const egp_gemm_desc *desc, void *stream);
 
+/* ------------------------------------------------------------------------------------ GAIL: the discriminator update
+ * (csrc/egp_gail.hip) What ego_pose/core/agent_vgail.py:54-88 needs beside the recurrent sweeps and the matrix products. All
+ * float32, all pointers device memory (except src_host), strides in elements.
+ *
+ * egp_gail_rows_f32 -- the discriminator's input block X[2n][H + S] in one launch. agent_vgail.py:60-61 calls the video net
+ * twice, on the batch's states and on the expert's; in train mode its context rows depend on the CNN features only, so one
+ * context serves both halves:
+ *     out[i]     = [ ctx[idx[i]][0:H] | x[i][0:S] ]                                   i < n   (generated)
+ *     out[n + i] = [ ctx[idx[i]][0:H] | (tab[src[i]][0:S] - mean) * inv_std ]                 (expert, agent_vgail.py:83-87)
+ * ctx / idx: the video net's output rows in (time, episode) order and one row index per sample (what egp_gather_concat_f32
+ * takes). x: the batch's (already normalised) states. tab: the expert observation table, all takes concatenated; src[i]: the
+ * table row of sample i. mean / inv_std (float32 [S], both NULL or both set): the observation filter; NULL = the table row as
+ * it is. No clip: agent_vgail.py:86-87 has none. A src[i] outside [0, tab_rows) (an idx[i] outside [0, ctx_rows)) is skipped
+ * on the device -- nothing is read out of range, the row's columns keep their content; src_host (or NULL), a HOST copy of src,
+ * lets the call see the values: an entry out of range then returns EGP_E_INVALID before anything is launched. 16-byte moves
+ * where widths, strides and bases allow, scalar moves otherwise.
+ *
+ * egp_gail_rows_bwd_f32 -- the adjoint for the context: dctx[idx[i]][0:H] = dout[i][0:H] + dout[n + i][0:H] (dout: the block's
+ * gradient, row stride ldo; idx must not repeat; dctx, row stride ld_ctx, is zero-filled by the caller as for
+ * egp_scatter_rows_f32). x and tab get no gradient. Reads n, H, idx, ctx_rows, ld_ctx, ldo, dout, dctx only. */
+struct egp_gail_rows_desc {
+    int32_t n, H, S;
+    const float *ctx; int64_t ld_ctx; int64_t ctx_rows;
+    const int64_t *idx;
+    const float *x; int64_t ldx;
+    const float *tab; int64_t ld_tab; int64_t tab_rows;
+    const int64_t *src;
+    const int64_t *src_host;
+    const float *mean; const float *inv_std;
+    float *out; int64_t ldo;
+    const float *dout; float *dctx;
+};
+typedef struct egp_gail_rows_desc egp_gail_rows_desc;
+int egp_gail_rows_f32(const egp_gail_rows_desc *desc, void *stream);
+int egp_gail_rows_bwd_f32(const egp_gail_rows_desc *desc, void *stream);
+
+/* egp_bce_logits_f32 -- the loss of agent_vgail.py:62-68 on the logits z[n + n_e] of that block: rows [0, n) carry label 1
+ * (generated, :66), rows [n, n + n_e) label 0 (expert, :67) -- the update passes n_e = n, z[2n]; a score-only call over a
+ * batch's generated rows passes n_e = 0. inv_n_g / inv_n_e carry the GLOBAL row counts (as inv_n_val does):
+ *     losses[0] = inv_n_g * sum_{i < n}  softplus(-z_i)          softplus(t) = max(t, 0) + log1p(exp(-|t|))
+ *     losses[1] = inv_n_e * sum_{i >= n} softplus( z_i)
+ *     dz_i      = (sigmoid(z_i) - y_i) * inv_n_{g|e}             (dz may be NULL: a score-only call)
+ *     score_i   = softplus(-z_i) = -log D(row i)   for i < n     (score_out may be NULL)
+ * losses: float64 [2]; sums in float64, per-workgroup partials then one final launch, fixed order (two runs are bit-identical).
+ * Where this differs from nn.BCELoss()(sigmoid(z), y): in float32 sigmoid(z) rounds to exactly 0 or 1 beyond |z| ~ 16.6 (88 on
+ * the side that underflows) and torch clamps the logarithm at -100, so the reference's per-row loss jumps to 100 (and its
+ * gradient to 0) there; this kernel returns ~|z| and the gradient of magnitude ~1. Inside that range the two agree to
+ * rounding. */
+struct egp_bce_logits_desc {
+    int32_t n, n_e;
+    const float *z;
+    double inv_n_g, inv_n_e;
+    float *dz;
+    float *score_out;
+    double *losses;
+    void *workspace;
+};
+typedef struct egp_bce_logits_desc egp_bce_logits_desc;
+int64_t egp_bce_logits_workspace_bytes(int32_t n);
+int egp_bce_logits_f32(const egp_bce_logits_desc *desc, void *stream);
+
 /* ---------------------------------------------------------------------------------------- TCN
  * Dilated temporal convolution of the TCN video net (models/tcn.py:15-70) on a time-major batch (csrc/egp_tcn.hip). In the
  * (T*B, C) matrix of a (T, B, C) batch a tap is the matrix shifted by whole rows, so forward pass and data gradient are both
