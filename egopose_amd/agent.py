@@ -19,6 +19,13 @@ on a GPU a float64 agent keeps the caller's float64 modules as MASTER weights (s
 optimizers step them) and computes with float32 SHADOW copies (``ShadowNets``): shadow gradients are copied up into
 the masters' ``.grad`` before the all-reduce / clip / optimizer steps, the stepped masters are copied down again.
 ``EGP_NET_DTYPE=float64`` keeps a float64 agent on the float64 torch paths (parity runs at 1e-9).
+
+The update step. Every optimizer step of every agent is one protocol on a stepper -- ``optim.FlatUpdater`` (fused clip + Adam
+over flat buffers) when the set-up is the one its kernels implement, else ``optim.TorchUpdater`` (the caller's optimizers step
+themselves): ``zero_grad()``, the caller's forward and backward, then ``collect_grads`` (shadow gradients -> masters),
+``all_reduce``, ``step`` (value step, clip, policy step; compute copies refreshed). ``AgentPG`` builds one stepper for
+(optimizer_value, optimizer_policy) on first use, ``AgentVGAIL`` another for (optimizer_discrim,) -- and a ``TorchUpdater`` of
+its own for the plain form of the discriminator update, the reference's loop in torch ops that the fused form is tested against.
 """
 from __future__ import annotations
 
@@ -118,6 +125,7 @@ class Agent:
         self.traj_cls = TrajBatch
         self.logger_cls = LoggerRL
         self._rollout = None
+        self._steppers = []         # every update stepper built so far (see the module docstring)
         self._bind_compute_nets()
         if self.cdtype != self.dtype and os.environ.get("EGP_QUIET", "0") != "1":
             #  a float64 driver gets float32 arithmetic on the GPU: say so once, where the agent is built
@@ -143,27 +151,8 @@ class Agent:
         self.sample_modules = [self.cn.policy_net]
         self.update_modules = [self.cn.policy_net, self.cn.value_net]
 
-    def _zero_grads(self):
-        up = self._get_updater() if hasattr(self, "_updater") else None
-        if up is not None:
-            up.zero_grad()
-            return
-        if getattr(self, "_grad_sync", None) is not None:
-            self._grad_sync.attach()            # gradients accumulate inside the all-reduce buffer (p.grad = its views)
-        else:
-            self.optimizer_value.zero_grad()
-            self.optimizer_policy.zero_grad()
-        if self.shadow is not None:
-            self.shadow.zero_grad()
-
-    def _grads_ready(self):
-        """Called after backward: hand the gradients to the parameters the optimizers own."""
-        if self.shadow is not None:
-            self.shadow.push_grads()
-
     def _params_stepped(self):
-        up = getattr(self, "_updater", None) or None
-        if up is not None:
+        for up in self._steppers:
             up.rebind()          # (a caller may have moved its modules: `with to_cpu(...)` around a checkpoint)
         if self.shadow is not None:
             self.shadow.pull()
@@ -238,8 +227,7 @@ class AgentPG(Agent):
         self.gamma, self.tau = gamma, tau
         self.optimizer_policy, self.optimizer_value = optimizer_policy, optimizer_value
         self.opt_num_epochs, self.value_opt_niter = opt_num_epochs, value_opt_niter
-        self._grad_sync = None
-        self._updater = None            # optim.FlatUpdater (fused clip + Adam over flat buffers) once built; False = not eligible
+        self._stepper = None            # the stepper of (optimizer_value, optimizer_policy), built on first use
         # A/B handles of the update's fused forms (the tests run both sides; all on by default, no environment switches):
         self.use_fused_optim = True     # clip + both Adam steps over flat buffers (optim.FlatUpdater) instead of the torch optimizers
         self.use_fused_loss = True      # both losses and their output gradients in one launch (optim.ppo_losses)
@@ -271,49 +259,45 @@ class AgentPG(Agent):
     def _kernel_ctx(self):
         return self._get_rollout().sim.ctx
 
-    def _value_params(self):
-        return [p for g in self.optimizer_value.param_groups for p in g["params"]]
-
     def _policy_params(self):
         return [p for g in self.optimizer_policy.param_groups for p in g["params"]]
-
-    def _sync_grads(self):
-        if D.world_size() > 1:
-            if self._grad_sync is None:
-                self._grad_sync = D.FlatGradSync(self._value_params() + self._policy_params())
-            self._grad_sync.all_reduce()
 
     def _clip_list(self):
         return []
 
+    def _build_stepper(self, optimizers, clip, pre_step, flat=True):
+        """The stepper of `optimizers`: optim.FlatUpdater (`clip` = its clip groups) when `flat`, on the GPU with use_fused_optim
+        and a set-up its kernels implement, else optim.TorchUpdater (`pre_step` = its clip callables)."""
+        up = None
+        if flat and torch.device(self.device).type == "cuda" and self.use_fused_optim and all(o is not None for o in optimizers):
+            compute_of = {m: c for m, c in self.shadow.pairs} if self.shadow is not None else None
+            up = O.FlatUpdater.build(optimizers, clip, compute_of)
+        if up is None:
+            up = O.TorchUpdater(optimizers, self.shadow, pre_step)
+        self._steppers.append(up)
+        return up
+
+    def _get_stepper(self):
+        if self._stepper is None:
+            self._stepper = self._build_stepper([self.optimizer_value, self.optimizer_policy], self._clip_list(),
+                                                {1: lambda: self.clip_policy_grad()})
+        return self._stepper
+
     def _get_updater(self):
         """optim.FlatUpdater for this agent's two optimizers, or None (CPU device, non-Adam optimizers, use_fused_optim = False, ...)."""
-        if self._updater is None:
-            up = None
-            if torch.device(self.device).type == "cuda" and self.use_fused_optim and \
-                    self.optimizer_value is not None and self.optimizer_policy is not None:
-                compute_of = {m: c for m, c in self.shadow.pairs} if self.shadow is not None else None
-                up = O.FlatUpdater.build([self.optimizer_value, self.optimizer_policy], self._clip_list(), compute_of)
-            self._updater = up if up is not None else False
-        return self._updater or None
+        up = self._get_stepper()
+        return up if isinstance(up, O.FlatUpdater) else None
+
+    def _zero_grads(self):
+        self._get_stepper().zero_grad()
 
     def _optim_step(self, which=(0, 1)):
         """After backward: gradient exchange, clip, optimizer steps (0 = value, 1 = policy; the reference steps the critic
         first, agents/agent_ppo.py:24-30), compute copies refreshed."""
-        up = self._get_updater()
-        if up is not None:
-            up.collect_grads(which)
-            up.all_reduce(which)
-            up.step(which)
-            return
-        self._grads_ready()
-        self._sync_grads()
-        if 0 in which:
-            self.optimizer_value.step()
-        if 1 in which:
-            self.clip_policy_grad()
-            self.optimizer_policy.step()
-        self._params_stepped()
+        up = self._get_stepper()
+        up.collect_grads(which)
+        up.all_reduce(which)
+        up.step(which)
 
     def clip_policy_grad(self):
         return
@@ -404,18 +388,10 @@ class AgentPPO(AgentPG):
 
     def ppo_loss(self, states, actions, advantages, fixed_log_probs, ind, n_exp=None):
         """`ind` = rows with exps == 1 (agents/agent_ppo.py:45-51), or None when that is every row (no gather copies)."""
-        if ind is None:
-            n_exp = states.shape[0] if n_exp is None else n_exp
-            logp = self.cn.policy_net.get_log_prob(self.trans_policy(states), actions)
-            ratio = torch.exp(logp - fixed_log_probs)
-            adv = advantages
-        else:
-            n_exp = ind.shape[0] if n_exp is None else n_exp
-            logp = self.cn.policy_net.get_log_prob(self.trans_policy(states)[ind], actions[ind])
-            ratio = torch.exp(logp - fixed_log_probs[ind])
-            adv = advantages[ind]
-        clipped = torch.clamp(ratio, 1.0 - self.clip_epsilon, 1.0 + self.clip_epsilon) * adv
-        return -torch.min(ratio * adv, clipped).sum() / n_exp
+        logp = self._policy_head(states, actions, ind, False)
+        if ind is not None:
+            advantages, fixed_log_probs = advantages[ind], fixed_log_probs[ind]
+        return self._surrogate(logp, advantages, fixed_log_probs, logp.shape[0] if n_exp is None else n_exp)
 
     def _exploration_rows(self, exps, n):
         """Rows with exps == 1 (agents/agent_ppo.py:45-46), or None when that is every row (no gather copies)."""
@@ -426,6 +402,23 @@ class AgentPPO(AgentPG):
         ratio = torch.exp(logp - fixed)
         clipped = torch.clamp(ratio, 1.0 - self.clip_epsilon, 1.0 + self.clip_epsilon) * adv
         return -torch.min(ratio * adv, clipped).sum() / n_exp
+
+    def _policy_head(self, states, actions, ind, fused):
+        """The policy's half of `_epoch_forward`: the action mean (`fused`) or the log-probabilities of the rows `ind`."""
+        x = self.trans_policy(states)
+        if ind is not None:
+            x = x[ind]
+        if fused:
+            return self._policy_mean(x)
+        return self.cn.policy_net.get_log_prob(x, actions if ind is None else actions[ind])
+
+    def _epoch_forward(self, states, actions, ind, fused):
+        """One epoch's forward pass -> (pred, head): both video contexts (grouped where the nets allow it), the critic's
+        values of every row, and of the rows `ind` the policy's action mean when the loss kernel runs (`fused`: it forms
+        the log-probabilities itself), else their log-probabilities."""
+        self._group_contexts(states)
+        pred = self.cn.value_net(self.trans_value(states))
+        return pred, self._policy_head(states, actions, ind, fused)
 
     def update_policy(self, states, actions, returns, advantages, exps, first_pass=None, counts=None):
         """`first_pass` = (pred, head, ind) of a forward pass ALREADY made with the current weights and autograd on
@@ -448,49 +441,27 @@ class AgentPPO(AgentPG):
             n_val, n_exp = counts
         if fused:
             return self._update_policy_fused(states, actions, returns, advantages, ind, n_ind, n_val, n_exp, first_pass)
+        if self.value_opt_niter != 1:
+            raise NotImplementedError("value_opt_niter != 1 is not on the ego_mimic path")
         if first_pass is None:
             with to_test(*self.update_modules):
                 with torch.no_grad():
-                    fixed_log_probs = self.cn.policy_net.get_log_prob(self.trans_policy(states), actions)
+                    fixed = self._policy_head(states, actions, None, False)
+            fixed = fixed if ind is None else fixed[ind]
         else:
-            pred0, logp0, _ = first_pass
-            fixed_sel = logp0.detach()
-            fixed_log_probs = None
+            fixed = first_pass[1].detach()
+        adv = advantages if ind is None else advantages[ind]
         losses = []
         for epoch in range(self.opt_num_epochs):
-            # critic and actor have disjoint parameters: both backward passes run before the single gradient
-            # exchange; the value step precedes the policy step as in the reference. (Running the two passes on two
-            # HIP streams was faster and hung the GPU intermittently -- concurrent library GEMMs, docs/DESIGN_TRAIL.md section 2.)
-            if first_pass is not None and epoch == 0:
-                v_loss = (pred0 - returns).pow(2).sum() / n_val
-                adv = advantages if ind is None else advantages[ind]
-                s_loss = self._surrogate(logp0, adv, fixed_sel, n_exp)
-                self._zero_grads()
-                (v_loss + s_loss).backward()
-            elif first_pass is not None:
-                self._group_contexts(states)
-                pred = self.cn.value_net(self.trans_value(states))
-                v_loss = (pred - returns).pow(2).sum() / n_val
-                x = self.trans_policy(states)
-                logp = self.cn.policy_net.get_log_prob(x if ind is None else x[ind], actions if ind is None else actions[ind])
-                s_loss = self._surrogate(logp, advantages if ind is None else advantages[ind], fixed_sel, n_exp)
-                self._zero_grads()
-                (v_loss + s_loss).backward()
-            elif self._group_contexts(states):
-                # both video nets' recurrences in one grouped launch each way; disjoint parameters, so one backward
-                # over the sum of the two losses yields exactly the two separate gradients
-                if self.value_opt_niter != 1:
-                    raise NotImplementedError("value_opt_niter != 1 is not on the ego_mimic path")
-                pred = self.cn.value_net(self.trans_value(states))
-                v_loss = (pred - returns).pow(2).sum() / n_val
-                s_loss = self.ppo_loss(states, actions, advantages, fixed_log_probs, ind, n_exp)
-                self._zero_grads()
-                (v_loss + s_loss).backward()
-            else:
-                self._zero_grads()
-                v_loss = self._value_backward(states, returns, n_val)
-                s_loss = self.ppo_loss(states, actions, advantages, fixed_log_probs, ind, n_exp)
-                s_loss.backward()
+            # critic and actor have disjoint parameters: one backward over the sum of the two losses yields exactly the two
+            # separate gradients, before the single gradient exchange; the value step precedes the policy step as in the
+            # reference. (Running two backward passes on two HIP streams was faster and hung the GPU intermittently --
+            # concurrent library GEMMs, docs/DESIGN_TRAIL.md section 2.)
+            pred, logp = first_pass[:2] if first_pass is not None and epoch == 0 else self._epoch_forward(states, actions, ind, False)
+            v_loss = (pred - returns).pow(2).sum() / n_val
+            s_loss = self._surrogate(logp, adv, fixed, n_exp)
+            self._zero_grads()
+            (v_loss + s_loss).backward()
             self._optim_step()
             losses.append((v_loss.detach(), s_loss.detach()))
         self.update_stats = {"value_loss": [float(v) for v, _ in losses], "surr_loss": [float(s) for _, s in losses]}
@@ -603,19 +574,12 @@ class AgentPPO(AgentPG):
         if eval_fixed:
             with to_test(*self.update_modules):
                 with torch.no_grad():
-                    x = self.trans_policy(states)
-                    mean = self._policy_mean(x if ind is None else x[ind])
+                    mean = self._policy_head(states, actions, ind, True)
             # (only `fixed` is kept of this launch: the value columns are placeholders, epoch 0 rewrites rec[0] and the gradients)
             O.ppo_losses(returns.reshape(-1, 1), returns, mean, act, log_std.detach(), advantages, fixed, True, self.clip_epsilon, n_val, n_exp,
                          rows=ind, d_pred=d_pred, d_mean=d_mean, losses_out=rec[0])
         for epoch in range(self.opt_num_epochs):
-            if first_pass is not None and epoch == 0:
-                pred, mean = first_pass[0], first_pass[1]
-            else:
-                self._group_contexts(states)
-                pred = self.cn.value_net(self.trans_value(states))
-                x = self.trans_policy(states)
-                mean = self._policy_mean(x if ind is None else x[ind])
+            pred, mean = first_pass[:2] if first_pass is not None and epoch == 0 else self._epoch_forward(states, actions, ind, True)
             self._zero_grads()
             _, _, _, d_ls = O.ppo_losses(pred.detach(), returns, mean.detach(), act, log_std.detach(), advantages, fixed, epoch == 0 and not eval_fixed,
                                          self.clip_epsilon, n_val, n_exp, rows=ind, d_pred=d_pred, d_mean=d_mean,
@@ -702,41 +666,41 @@ class AgentEgo(AgentPPO):
         w = getattr(self, "_lazy_width", {}).get("value", 0)
         return self.cn.value_vs_net(states, lazy_width=w) if w else self.cn.value_vs_net(states)
 
+    @staticmethod
+    def _v_metas_of(batch):
+        v_metas = batch.device_column("v_metas") if hasattr(batch, "device_column") else None
+        return v_metas.cpu().numpy() if v_metas is not None else np.asarray(batch.v_metas)
+
+    def _train_context(self, net, masks, v_metas, adopt_from=None):
+        """The video net `net` in train mode on this batch (ego_pose/core/agent_ego.py:34-41): the rollout's feature table
+        attached when there is one, then the batch's segmentation adopted from `adopt_from` (a net initialised on the same
+        batch and table: segment and gather once) or made by `initialize`."""
+        ex = self._rollout.experts if self._rollout is not None else None
+        if ex is not None and hasattr(net, "attach_feature_table"):
+            net.attach_feature_table(ex.cnn_table(masks.device, next(net.parameters()).dtype), ex.cnn_offset)
+        net.set_mode("train")
+        x_init = (masks, self.env.cnn_feat, v_metas)
+        if adopt_from is not None and self.share_train_context and hasattr(net, "adopt_train_context"):
+            net.adopt_train_context(adopt_from, x_init)
+        else:
+            net.initialize(x_init)
+
     def update_params(self, batch):
         t0 = time.time()
         to_train(*self.update_modules)
         self._params_stepped()
         c = self._load_batch(batch)
         dev = c["states"].device
-        vs_nets = (self.cn.policy_vs_net, self.cn.value_vs_net)
-        v_metas = batch.device_column("v_metas") if hasattr(batch, "device_column") else None
-        v_metas = v_metas.cpu().numpy() if v_metas is not None else batch.v_metas
-        if self._rollout is not None and self._rollout.experts is not None:
-            ex = self._rollout.experts
-            pdt = next(vs_nets[0].parameters()).dtype
-            for net in vs_nets:
-                net.attach_feature_table(ex.cnn_table(dev, pdt), ex.cnn_offset)
-        x_init = (c["masks"], self.env.cnn_feat, v_metas)
-        for i, net in enumerate(vs_nets):
-            net.set_mode("train")
-            if i > 0 and hasattr(net, "adopt_train_context") and self.share_train_context:
-                net.adopt_train_context(vs_nets[0], x_init)      # same batch, same feature table: segment and gather once
-            else:
-                net.initialize(x_init)
+        v_metas = self._v_metas_of(batch)
+        self._train_context(self.cn.policy_vs_net, c["masks"], v_metas)
+        self._train_context(self.cn.value_vs_net, c["masks"], v_metas, adopt_from=self.cn.policy_vs_net)
         n_rows = c["states"].shape[0]
         ind, n_ind = self._exploration_rows(c["exps"], n_rows)
         if self.value_opt_niter == 1 and self.reuse_first_pass and not self._dropout_active():
             # ONE forward pass with autograd on serves three purposes: the values that GAE consumes, the fixed log-probs of
             # the surrogate, and epoch 0's forward (nothing has stepped in between, and no net draws dropout masks: with a
             # TCN video net and dropout > 0 a train-mode pass is not the eval-mode one, and the branch below runs instead)
-            self._group_contexts(c["states"])
-            pred0 = self.cn.value_net(self.trans_value(c["states"]))
-            x = self.trans_policy(c["states"])
-            xs = x if ind is None else x[ind]
-            if self._fused_losses():
-                head0 = self._policy_mean(xs)           # the loss kernel forms the log-probabilities itself
-            else:
-                head0 = self.cn.policy_net.get_log_prob(xs, c["actions"] if ind is None else c["actions"][ind])
+            pred0, head0 = self._epoch_forward(c["states"], c["actions"], ind, self._fused_losses())
             advantages, returns, counts = self._advantages_with_counts(c["rewards"], c["masks"], pred0.detach(), (n_rows, n_ind))
             self.update_policy(c["states"], c["actions"], returns, advantages, c["exps"], first_pass=(pred0, head0, ind), counts=counts)
         else:
@@ -785,8 +749,7 @@ class AgentVGAIL(AgentEgo):
         self.expert_obs = expert_obs
         self.discrim_reward_weight = float(discrim_reward_weight)
         self.use_fused_discrim = True       # A/B handle: one sweep + one stacked block + HIP loss tail per step instead of the reference's loop
-        self._discrim_updater = None        # optim.FlatUpdater of optimizer_discrim once built; False = not eligible
-        self._discrim_sync = None
+        self._discrim_stepper = {}          # the steppers of (optimizer_discrim,), built on first use (`_get_discrim_stepper`)
         self._expert_rows = None            # host rows of every take (expert.expert_obs_rows)
         self._expert_table = {}
         self._gail_batch = None
@@ -804,12 +767,6 @@ class AgentVGAIL(AgentEgo):
         extra = [m for m in (getattr(self.cn, "discrim_net", None), getattr(self.cn, "discrim_vs_net", None)) if m is not None]
         self.sample_modules = self.sample_modules + extra          # agent_vgail.py:17-18
         self.update_modules = self.update_modules + extra
-
-    def _params_stepped(self):
-        up = getattr(self, "_discrim_updater", None) or None
-        if up is not None:
-            up.rebind()
-        super()._params_stepped()
 
     def _epochs_enqueued(self):
         # inside update_params the next sampling pass is set up behind the DISCRIMINATOR's last step, not behind the PPO epochs:
@@ -886,21 +843,27 @@ class AgentVGAIL(AgentEgo):
         return torch.from_numpy(np.ascontiguousarray(expert_states)).to(self.dtype).to(self.device)
 
     # -- the discriminator update -------------------------------------------------------------------
-    def _discrim_params(self):
-        return [p for g in self.optimizer_discrim.param_groups for p in g["params"]]
-
     def _discrim_clip_list(self):
         c = self.discrim_grad_clip
         return [(list(self.discrim_net.parameters()), float(c))] if c is not None and c > 0 else []
 
+    def _clip_discrim_grad(self):
+        """agent_vgail.py:70 -> discrim_net's gradient norm before the clip, or None without a clip."""
+        c = self.discrim_grad_clip
+        return torch.nn.utils.clip_grad_norm_(self.discrim_net.parameters(), c) if c is not None and c > 0 else None
+
+    def _get_discrim_stepper(self, flat=True):
+        """The stepper of (optimizer_discrim,). `flat` False: the plain form's, whose optimizer always steps itself (the
+        reference's loop in torch ops is what the fused form is measured against)."""
+        if flat not in self._discrim_stepper:
+            self._discrim_stepper[flat] = self._build_stepper([self.optimizer_discrim], self._discrim_clip_list(),
+                                                              {0: self._clip_discrim_grad}, flat)
+        return self._discrim_stepper[flat]
+
     def _get_discrim_updater(self):
-        if self._discrim_updater is None:
-            up = None
-            if torch.device(self.device).type == "cuda" and self.use_fused_optim and self.optimizer_discrim is not None:
-                compute_of = {m: c for m, c in self.shadow.pairs} if self.shadow is not None else None
-                up = O.FlatUpdater.build([self.optimizer_discrim], self._discrim_clip_list(), compute_of)
-            self._discrim_updater = up if up is not None else False
-        return self._discrim_updater or None
+        """optim.FlatUpdater of optimizer_discrim, or None (as `_get_updater`)."""
+        up = self._get_discrim_stepper()
+        return up if isinstance(up, O.FlatUpdater) else None
 
     def _fused_discrim(self):
         from .nets import Discriminator, VideoStateNet
@@ -913,16 +876,7 @@ class AgentVGAIL(AgentEgo):
     def _init_discrim_context(self, masks, v_metas, adopt):
         """discrim_vs_net in train mode on this batch (agent_vgail.py:56-57); inside update_params it adopts the policy net's
         segmentation of the same batch instead of repeating it."""
-        vs = self.cn.discrim_vs_net
-        if self._rollout is not None and self._rollout.experts is not None and hasattr(vs, "attach_feature_table"):
-            ex = self._rollout.experts
-            vs.attach_feature_table(ex.cnn_table(masks.device, next(vs.parameters()).dtype), ex.cnn_offset)
-        vs.set_mode("train")
-        x_init = (masks, self.env.cnn_feat, v_metas)
-        if adopt and self.share_train_context and hasattr(vs, "adopt_train_context"):
-            vs.adopt_train_context(self.cn.policy_vs_net, x_init)
-        else:
-            vs.initialize(x_init)
+        self._train_context(self.cn.discrim_vs_net, masks, v_metas, adopt_from=self.cn.policy_vs_net if adopt else None)
 
     def update_discriminator(self, states, masks, v_metas, _adopt=False):
         """perform discriminator update (agent_vgail.py:54-73) -> e_loss, the last step's expert loss, as a float."""
@@ -941,40 +895,27 @@ class AgentVGAIL(AgentEgo):
     def _update_discriminator_plain(self, states, masks, v_metas):
         dev = states.device
         expert_states = self.get_expert_states(v_metas, masks).to(self.cdtype)
-        vs, dn, crit, opt = self.cn.discrim_vs_net, self.cn.discrim_net, self.discrim_criterion, self.optimizer_discrim
+        vs, dn, crit = self.cn.discrim_vs_net, self.cn.discrim_net, self.discrim_criterion
         n = states.shape[0]
         multi = D.world_size() > 1
         share = n / D.global_count(n, dev) if multi else None          # mean over this rank's rows -> its share of the global mean
-        if multi and self._discrim_sync is None:
-            self._discrim_sync = D.FlatGradSync(self._discrim_params())
-        clip = self.discrim_grad_clip
-        l_e = norm = None
+        up = self._get_discrim_stepper(flat=False)
+        l_e = None
         for _ in range(self.discrim_num_update):
             g_vs_out = vs(states)
             e_vs_out = vs(expert_states)
             g_o = dn(g_vs_out)
             e_o = dn(e_vs_out)
-            if multi:
-                self._discrim_sync.attach()
-            else:
-                opt.zero_grad()
-            if self.shadow is not None:
-                self.shadow.zero_grad()
+            up.zero_grad()
             l_g = crit(g_o, torch.ones((g_o.size(0), 1), dtype=g_o.dtype, device=dev))
             l_e = crit(e_o, torch.zeros((e_o.size(0), 1), dtype=e_o.dtype, device=dev))
             if multi:
                 l_g, l_e = l_g * share, l_e * share
             discrim_loss = l_g + l_e
             discrim_loss.backward()
-            if self.shadow is not None:
-                self.shadow.push_grads()
-            if multi:
-                self._discrim_sync.all_reduce()
-            if clip is not None and clip > 0:
-                norm = torch.nn.utils.clip_grad_norm_(self.discrim_net.parameters(), clip)
-            opt.step()
-            if self.shadow is not None:
-                self.shadow.pull()
+            up.collect_grads()
+            up.all_reduce()
+            up.step()
         self._discrim_enqueued()
         if l_e is None:
             return 0.0
@@ -983,16 +924,18 @@ class AgentVGAIL(AgentEgo):
             l_e = l_e.to(D._comm_device(dev))
             torch.distributed.all_reduce(l_e)
             D._note()
-        self._record_discrim_norm(norm, clip)
+        self._record_discrim_norm(up)
         return l_e.item()
 
-    def _record_discrim_norm(self, norm, clip):
-        """discrim_stats: discrim_net's gradient norm of the last step, before and after the clip."""
+    def _record_discrim_norm(self, up):
+        """discrim_stats: discrim_net's gradient norm of the last step, before and after the clip (read once, after the last
+        step is queued)."""
+        norm = up.grad_norm(1)
         if norm is None:
             self.discrim_stats = {}
             return
         norm = float(norm)
-        self.discrim_stats = {"grad_norm": norm, "clipped_norm": norm * min(1.0, float(clip) / (norm + 1e-6))}
+        self.discrim_stats = {"grad_norm": norm, "clipped_norm": norm * min(1.0, float(self.discrim_grad_clip) / (norm + 1e-6))}
 
     def _update_discriminator_fused(self, states, src_host):
         """Per step: ONE sweep of discrim_vs_net -> optim.gail_rows (the [generated; expert] block from the context rows, the
@@ -1012,53 +955,31 @@ class AgentVGAIL(AgentEgo):
             inv_std = torch.as_tensor(1.0 / np.asarray(rs.std, np.float64), dtype=torch.float32, device=dev).contiguous()
         x = states if states.stride(1) == 1 else states.contiguous()
         n_glob = D.global_count(n, dev)
-        up = self._get_discrim_updater()
-        if up is None and D.world_size() > 1 and self._discrim_sync is None:
-            self._discrim_sync = D.FlatGradSync(self._discrim_params())
+        up = self._get_discrim_stepper()
         steps = int(self.discrim_num_update)
         rec = torch.zeros(max(1, steps), 2, dtype=torch.float64, device=dev)
         dz = torch.empty(2 * n, 1, dtype=torch.float32, device=dev)
-        clip = self.discrim_grad_clip
-        norm = None
         for step in range(steps):
             grouped_video_context([vs])                     # (a bi-LSTM's two directions in one grouped launch; else the net runs itself)
             ctx2d = vs.context_rows().contiguous()
             X = O.GailRows.apply(ctx2d, vs._gather_tm, x, tab, src, mean, inv_std)
             X._egp_ctx_cols = vs.v_hdim                     # the trailing columns are data: no input gradient needed there
             z = dn.logits(X)
-            if up is not None:
-                up.zero_grad()
-            else:
-                self.optimizer_discrim.zero_grad()
-                if self.shadow is not None:
-                    self.shadow.zero_grad()
+            up.zero_grad()
             O.bce_logits(z.detach(), n_glob, n_glob, dz=dz, losses_out=rec[step])
             torch.autograd.backward([z], [dz])
-            if up is not None:
-                up.collect_grads()
-                up.all_reduce()
-                up.step()
-            else:                                           # not Adam (or use_fused_optim off): the caller's optimizer steps
-                if self.shadow is not None:
-                    self.shadow.push_grads()
-                if self._discrim_sync is not None:
-                    self._discrim_sync.all_reduce()
-                if clip is not None and clip > 0:
-                    norm = torch.nn.utils.clip_grad_norm_(self.discrim_net.parameters(), clip)
-                self.optimizer_discrim.step()
-                if self.shadow is not None:
-                    self.shadow.pull()
+            up.collect_grads()
+            up.all_reduce()
+            up.step()
         self._discrim_enqueued()
         if steps < 1:
             return 0.0
-        if up is not None and clip is not None and clip > 0:
-            norm = up.norms[1]
         e_loss = rec[steps - 1, 1]
         if D.world_size() > 1:
             e_loss = e_loss.to(D._comm_device(dev))
             torch.distributed.all_reduce(e_loss)
             D._note()
-        self._record_discrim_norm(norm, clip)
+        self._record_discrim_norm(up)
         return e_loss.item()
 
     # -- the discriminator as a reward ----------------------------------------------------------------
@@ -1078,11 +999,6 @@ class AgentVGAIL(AgentEgo):
                         return O.bce_scores(z)
                     return torch.nn.functional.softplus(-z).reshape(-1)
                 return -torch.log(dn(x)).reshape(-1)
-
-    @staticmethod
-    def _v_metas_of(batch):
-        v_metas = batch.device_column("v_metas") if hasattr(batch, "device_column") else None
-        return v_metas.cpu().numpy() if v_metas is not None else np.asarray(batch.v_metas)
 
     def _load_batch(self, batch):
         self._cols = super()._load_batch(batch)

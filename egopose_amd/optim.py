@@ -10,14 +10,18 @@
   gail_rows(...) / GailRows, bce_logits(...)   the GAIL discriminator step (ego_pose/core/agent_vgail.py:54-73, csrc/egp_gail.hip): the
                     [generated; expert] input block from one set of video-context rows with its adjoint, and nn.BCELoss on the
                     logits of that block with d loss / d logits and the per-row score -log D
-  FlatUpdater       clip_policy_grad (agent_ppo.py:53-56) + optimizer_value.step() + optimizer_policy.step() (agent_ppo.py:24-30)
-                    as two launches over flat buffers. The caller's torch.optim.Adam objects stay the source of every
-                    hyper-parameter (`set_optimizer_lr` keeps working) and see the moments as their own state; the parameters of
-                    the caller's modules become views of one flat buffer, the gradient buffer doubles as the all-reduce buffer
-                    (no copies in or out), and with float64 master modules (the unmodified driver) the float32 compute copies
-                    are refreshed by the same launch.
+  FlatUpdater / TorchUpdater   the update step after backward, one protocol in two forms:
+                        zero_grad()  ...forward, backward...  collect_grads(which); all_reduce(which); step(which)
+                    (`which` = indices of the optimizers to step, None = all; `rebind()` after a caller moved its modules;
+                    `grad_norm(group)` = the last step's pre-clip norm). FlatUpdater is clip_policy_grad (agent_ppo.py:53-56) +
+                    optimizer_value.step() + optimizer_policy.step() (agent_ppo.py:24-30) as two launches over flat buffers. The
+                    caller's torch.optim.Adam objects stay the source of every hyper-parameter (`set_optimizer_lr` keeps working)
+                    and see the moments as their own state; the parameters of the caller's modules become views of one flat
+                    buffer, the gradient buffer doubles as the all-reduce buffer (no copies in or out), and with float64 master
+                    modules (the unmodified driver) the float32 compute copies are refreshed by the same launch. TorchUpdater is
+                    the same sequence with the caller's optimizers stepping themselves (any device, dtype and optimizer class).
 
-Neither has a CPU form: on a CPU device (the oracle-side parity tests) the agent runs the plain torch formulation.
+The kernels have no CPU form: on a CPU device (the oracle-side parity tests) the agent runs the plain torch formulation.
 """
 from __future__ import annotations
 
@@ -323,6 +327,7 @@ class FlatUpdater:
         self.optimizers = list(optimizers)
         self.lib = L.load()
         clip = list(clip or [])
+        self.n_clip = len(clip)
         clip_of = {}
         for gi, (params, max_norm) in enumerate(clip, start=1):
             for p in params:
@@ -510,6 +515,68 @@ class FlatUpdater:
             if oi in which:
                 self.step_tensors[k].fill_(float(self.steps[oi]))
 
+    def grad_norm(self, group):
+        """Gradient norm of clip group `group` (1 = the first entry of `clip`) at the last step, before the clip: a 0-d device
+        tensor (no host read), or None when there is no such group."""
+        return self.norms[group] if 1 <= group <= self.n_clip else None
+
 
 class _NotEligible(Exception):
     pass
+
+
+class TorchUpdater:
+    """FlatUpdater's calls over the caller's own optimizers, which step themselves (any device, dtype and optimizer class).
+
+    `shadow`: agent.ShadowNets when the optimizers own float64 masters of float32 compute copies, else None. `pre_step`:
+    {optimizer index: callable run immediately before that optimizer's step()} -- the gradient clip; what it returned last is
+    `grad_norm(k)` for the k-th entry (from 1, as FlatUpdater numbers its clip groups). With more than one rank the gradients of
+    all the optimizers' parameters live in one dist.FlatGradSync buffer, built by the first zero_grad() (so before the first
+    step), which from then on attaches that buffer instead of clearing the gradients."""
+
+    def __init__(self, optimizers, shadow=None, pre_step=None):
+        self.optimizers, self.shadow, self.pre_step = list(optimizers), shadow, dict(pre_step or {})
+        self.sync = None
+        self.returned = {}
+
+    def _get_sync(self):
+        if self.sync is None and D.world_size() > 1:
+            self.sync = D.FlatGradSync([p for opt in self.optimizers for g in opt.param_groups for p in g["params"]])
+        return self.sync
+
+    def zero_grad(self):
+        sync = self._get_sync()
+        if sync is not None:
+            sync.attach()            # gradients accumulate inside the all-reduce buffer (p.grad = its views)
+        else:
+            for opt in self.optimizers:
+                opt.zero_grad()
+        if self.shadow is not None:
+            self.shadow.zero_grad()
+
+    def collect_grads(self, which=None):
+        """The compute copies' gradients -> the .grad of the parameters the optimizers own."""
+        if self.shadow is not None:
+            self.shadow.push_grads()
+
+    def all_reduce(self, which=None):
+        """SUM over ranks of the whole buffer, whatever `which` says (each rank divided its losses by the GLOBAL counts)."""
+        sync = self._get_sync()
+        if sync is not None:
+            sync.all_reduce()
+
+    def step(self, which=None):
+        for oi, opt in enumerate(self.optimizers):
+            if which is None or oi in which:
+                if oi in self.pre_step:
+                    self.returned[oi] = self.pre_step[oi]()
+                opt.step()
+        if self.shadow is not None:
+            self.shadow.pull()
+
+    def rebind(self):
+        return
+
+    def grad_norm(self, group):
+        keys = list(self.pre_step)
+        return self.returned.get(keys[group - 1]) if 1 <= group <= len(keys) else None

@@ -32,7 +32,7 @@ timed(ag.value_vs_net, "initialize", "vs_net.initialize x2")
 timed(ag, "_advantages", "advantages (GAE)")
 timed(ag, "update_policy", "update_policy (log-probs + 10 epochs)")
 timed(ag, "ppo_loss", "  of which ppo_loss forward x10")
-timed(ag, "_sync_grads", "  grad sync")
+timed(ag._get_stepper(), "all_reduce", "  grad sync")
 timed(ag.optimizer_policy, "step", "  optimizer steps")
 timed(ag.optimizer_value, "step", "  optimizer steps")
 for it in range(4):
