@@ -13,6 +13,7 @@ LIB_PATH = os.path.join(HERE, "libegopose_hip.so")
 
 EGP_OK = 0
 EGP_EXPERT_ROW = 168
+EGP_LSTM_GATES_UNIT_MAJOR = 1
 
 c_int_p = C.POINTER(C.c_int32)
 c_dbl_p = C.POINTER(C.c_double)
@@ -84,6 +85,21 @@ class PolicyDesc(C.Structure):
                 ("vlayers", C.POINTER(MlpLayer)), ("n_vlayers", C.c_int32), ("vactivation", C.c_int32),
                 ("value_out", vp),
                 ("stage_src", vp), ("stage_dst", vp), ("stage_bytes", C.c_int64)]
+
+
+class LstmDesc(C.Structure):
+    """egp_lstm_desc (include/egopose_hip.h)."""
+    _fields_ = [("T", C.c_int32), ("B", C.c_int32), ("hidden", C.c_int32), ("n_problems", C.c_int32), ("reverse_mask", C.c_int32),
+                ("w_hh", vp),
+                ("gates_x", vp), ("ld_g", C.c_int32),
+                ("h_out", vp * 4), ("ld_h", C.c_int32),
+                ("gates_save", vp), ("cells_save", vp),
+                ("last_only", C.c_int32),
+                ("seq_base", vp),
+                ("dh_out", vp * 4), ("ld_dh", C.c_int32),
+                ("d_pre", vp),
+                ("d_bias", vp), ("d_bias_rows", C.c_int32),
+                ("seq_order", vp), ("seq_steps", vp), ("leave_skipped", C.c_int32)]
 
 
 class GemmDesc(C.Structure):
@@ -283,10 +299,8 @@ SIGNATURES = {
     "egp_adam_step_f32": (C.c_int, [_i32, C.POINTER(AdamSegment), vp, vp, vp, vp, vp, vp, vp]),
     "egp_adam_step_f64": (C.c_int, [_i32, C.POINTER(AdamSegment), vp, vp, vp, vp, vp, vp, vp, vp]),
     "egp_adam_step_f64g": (C.c_int, [_i32, C.POINTER(AdamSegment), vp, vp, vp, vp, vp, vp, vp]),
-    "egp_lstm_fwd_f32": (C.c_int, [vp, vp, _i32, _i32, _i32, _i32, vp, vp, vp, vp]),
-    "egp_lstm_bwd_f32": (C.c_int, [vp, vp, vp, vp, _i32, _i32, _i32, _i32, vp, vp]),
-    "egp_lstm_group_fwd_f32": (C.c_int, [vp, vp, _i32, _i32, _i32, _i32, _i32, C.POINTER(C.c_void_p), _i32, vp, vp, vp]),
-    "egp_lstm_group_bwd_f32": (C.c_int, [C.POINTER(C.c_void_p), _i32, vp, vp, vp, _i32, _i32, _i32, _i32, _i32, vp, vp, vp]),
+    "egp_lstm_fwd_f32": (C.c_int, [C.POINTER(LstmDesc), vp]),
+    "egp_lstm_bwd_f32": (C.c_int, [C.POINTER(LstmDesc), vp]),
     "egp_rollout_tick_pre": (C.c_int, [vp, _i32, _i32, _i32, _i32, vp, _i32, vp, vp]),
     "egp_rollout_tick_apply": (C.c_int, [vp, _i32, _i32, _i32, _i32, vp, vp]),
     "egp_obs_zfilter_split_max_rows": (C.c_int32, []),
@@ -296,10 +310,6 @@ SIGNATURES = {
     "egp_rollout_reset": (C.c_int, [vp, _i32, _i32, _i32, _i32, vp, _i32, vp, vp, vp, vp, vp, vp, vp, vp, vp]),
     "egp_engine_group_stream": (vp, [vp, _i32]),
     "egp_debug_burn": (C.c_int, [C.c_int64, _i32, vp, vp]),
-    "egp_lstm_group_fwd_len_f32": (C.c_int, [vp, vp, _i32, _i32, _i32, _i32, _i32, C.POINTER(C.c_void_p), _i32, vp, vp, vp, vp, _i32, vp, vp]),
-    "egp_lstm_group_bwd_len_f32": (C.c_int, [C.POINTER(C.c_void_p), _i32, vp, vp, vp, _i32, _i32, _i32, _i32, _i32, vp, vp, vp, vp, _i32, vp]),
-    "egp_lstm_group_bwd_rows_f32": (C.c_int, [C.POINTER(C.c_void_p), _i32, vp, vp, vp, _i32, _i32, _i32, _i32, _i32, vp, vp, vp, vp, _i32, vp]),
-    "egp_lstm_window_last_f32": (C.c_int, [vp, _i32, vp, vp, _i32, _i32, _i32, _i32, vp, _i32, vp]),
     "egp_set_dynamics_model": (C.c_int, [vp, C.POINTER(DynamicsDesc)]),
     "egp_dynamics_f64": (C.c_int, [vp, vp, vp, _i32, vp, C.c_int64, vp, vp, vp]),
     "egp_set_pose2d_bodies": (C.c_int, [vp, c_int_p, c_int_p]),

@@ -82,7 +82,7 @@ struct LstmGroup {
     const float *dh[4];     // backward: d h_out per problem
     float *db;              // backward, optional: [P][4H] accumulates sum_t,b d_pre (atomics; zeroed by the caller), or with
     int db_rows;            // db_rows: [P][B][4H], row b = sum_t d_pre of row b, stored (the caller sums over b in a fixed order)
-    // optional (egp_lstm_group_*_len_f32): ragged batches. order[p] = sequence (column b of the [T][B] layout) at position p,
+    // optional (egp_lstm_desc.seq_order / seq_steps): ragged batches. order[p] = sequence (column b of the [T][B] layout) at position p,
     // workgroups take ROWS consecutive positions; steps[p] = time steps the sequence at position p needs FROM THE START
     // (its outputs at t >= steps[p] are never read). A problem that runs forward in time stops at the longest of its rows
     // (h_out / d_pre of the skipped steps are written as zeros); problems that run backward in time go through all T
@@ -142,7 +142,7 @@ __device__ long long g_lstm_trace[8];
 #endif
 // STORE = what a step leaves in memory. LSTM_ST_STEP: h_out at every step (inference). LSTM_ST_TRAIN: h_out and the save-set
 // (activated gates, cell states). LSTM_ST_LAST: nothing per step -- only the hidden state after the last step, one row per
-// sequence at h_out + b * ld_h (egp_lstm_window_last_f32: inference over windows of a frame table). The step itself is the same
+// sequence at h_out + b * ld_h (egp_lstm_desc.last_only: inference over windows of a frame table). The step itself is the same
 // code. (One parameter with three values, in the place `bool TRAIN` had: what parses k_lstm_fwd_mfma<NQ, LH, FULL, x> in a
 // profiler's kernel names -- tests/test_lstm_reference_gpu.py -- still finds four arguments, x = 0 / 1 for the per-step sweeps.)
 constexpr int LSTM_ST_STEP = 0, LSTM_ST_TRAIN = 1, LSTM_ST_LAST = 2;
@@ -521,124 +521,58 @@ static void launch_bwd_mfma(int hidden, int P, const float *gates_save, const fl
     else launch_bwd_mfma_t<1, 64>(full, P, gates_save, cells_save, w_hh, T, B, g, d_pre, s);
 }
 
-// the grouped backward behind egp_lstm_group_bwd_len_f32 (d_bias: [P][4H], atomics) and egp_lstm_group_bwd_rows_f32 ([P][B][4H])
-static int lstm_group_bwd(const float *const *dh_out, int32_t ld_dh, const float *gates_save, const float *cells_save, const float *w_hh,
-                          int32_t T, int32_t B, int32_t hidden, int32_t n_problems, int32_t reverse_mask, float *d_pre, float *d_bias,
-                          int db_rows, const int32_t *seq_order, const int32_t *seq_steps, int32_t leave_skipped, void *stream) {
-    EGP_REQUIRE((seq_order == nullptr) == (seq_steps == nullptr), "seq_order and seq_steps go together");
-    EGP_REQUIRE(hidden == 64 || hidden == 128, "egp_lstm kernels are built for hidden size 64 and 128");
-    EGP_REQUIRE(n_problems >= 1 && n_problems <= 4, "1..4 problems per group");
+// Both entry points: every rule of egp_lstm_desc once, the one filling of LstmGroup, the launch. `bwd` picks the sweep and with it
+// the descriptor's group that is read (forward: gates_x .. seq_base, backward: dh_out .. d_bias_rows).
+static int lstm_sweep(const egp_lstm_desc *d, bool bwd, void *stream) {
+    EGP_REQUIRE(d, "desc is NULL");
+    const int T = d->T, B = d->B, H = d->hidden, P = d->n_problems;
+    const bool last = !bwd && d->last_only, db_rows = bwd && d->d_bias_rows;
     EGP_REQUIRE(T >= 0 && B >= 0, "negative size");
-    if (T == 0 || B == 0) return EGP_OK;
-    EGP_REQUIRE(dh_out && gates_save && cells_save && w_hh && d_pre && ld_dh >= hidden, "NULL pointer / d h_out row stride below the hidden size");
-    LstmGroup g = {};
-    g.ld_g = 4 * hidden * n_problems; g.rev_mask = reverse_mask; g.ld_dh = ld_dh; g.c_stride = (long)T * B * hidden; g.db = d_bias; g.db_rows = db_rows;
-    for (int p = 0; p < n_problems; ++p) {
-        EGP_REQUIRE(dh_out[p], "NULL d h_out");
-        g.dh[p] = dh_out[p];
+    EGP_REQUIRE(!last || T >= 1, "a window has at least one step");
+    if (B == 0 || (T == 0 && !db_rows)) return EGP_OK;
+    EGP_REQUIRE(H == 64 || H == 128, "egp_lstm kernels are built for hidden size 64 and 128");
+    EGP_REQUIRE(P >= 1 && P <= 4, "1..4 problems per group");
+    EGP_REQUIRE(!db_rows || d->d_bias, "d_bias_rows without d_bias");
+    if (T == 0) {                         // nothing to sweep: every row's sum is zero
+        EGP_HIP_CHECK(hipMemsetAsync(d->d_bias, 0, sizeof(float) * (size_t)P * B * 4 * H, (hipStream_t)stream));
+        return EGP_OK;
     }
-    g.order = seq_order; g.steps = seq_steps; g.leave_skipped = seq_steps && leave_skipped;
-    launch_bwd_mfma(hidden, n_problems, gates_save, cells_save, w_hh, T, B, g, d_pre, (hipStream_t)stream);
-    return lstm_launch_check("k_lstm_bwd_mfma (group)");
+    const int ld_g = d->ld_g ? d->ld_g : 4 * H * P, ld_io = bwd ? d->ld_dh : d->ld_h;
+    EGP_REQUIRE(ld_g >= 4 * H * P && ld_g % 4 == 0, "gate row stride below n_problems * 4H or not a multiple of 4");
+    EGP_REQUIRE(ld_io == 0 || ld_io >= H, "h_out / dh_out row stride below the hidden size");
+    EGP_REQUIRE((d->seq_order == nullptr) == (d->seq_steps == nullptr), "seq_order and seq_steps go together");
+    EGP_REQUIRE((d->gates_save == nullptr) == (d->cells_save == nullptr), "gates_save and cells_save go together");
+    EGP_REQUIRE(d->w_hh && (bwd ? d->gates_save && d->d_pre : d->gates_x != nullptr), "NULL pointer");
+    if (!bwd) {
+        EGP_REQUIRE(!d->seq_base || !d->gates_save || d->gates_save != d->gates_x,
+                    "a frame table cannot double as the saved gates (rows are shared between sequences)");
+        EGP_REQUIRE(!last || P == 1, "last_only sweeps one problem");
+        EGP_REQUIRE(!last || !d->gates_save, "last_only saves nothing (inference)");
+        EGP_REQUIRE(!last || !d->seq_order, "last_only takes no seq_order / seq_steps");
+        EGP_REQUIRE(!last || d->seq_base, "last_only needs seq_base (windows of a frame table)");
+    }
+    LstmGroup g = {};
+    g.ld_g = ld_g; g.rev_mask = d->reverse_mask; g.c_stride = (long)T * B * H;
+    g.order = d->seq_order; g.steps = d->seq_steps; g.leave_skipped = d->seq_steps && d->leave_skipped;
+    (bwd ? g.ld_dh : g.ld_h) = ld_io ? ld_io : H;
+    for (int p = 0; p < P; ++p) {
+        EGP_REQUIRE(bwd ? d->dh_out[p] != nullptr : d->h_out[p] != nullptr, "NULL h_out / dh_out of a problem");
+        if (bwd) g.dh[p] = d->dh_out[p]; else g.h[p] = d->h_out[p];
+    }
+    if (bwd) {
+        g.db = d->d_bias; g.db_rows = db_rows;
+        launch_bwd_mfma(H, P, d->gates_save, d->cells_save, d->w_hh, T, B, g, d->d_pre, (hipStream_t)stream);
+    } else {
+        g.seq_base = d->seq_base;
+        launch_fwd_mfma(H, P, d->gates_x, d->w_hh, T, B, g, d->gates_save, d->cells_save, (hipStream_t)stream, last);
+    }
+    return lstm_launch_check(bwd ? "k_lstm_bwd_mfma" : "k_lstm_fwd_mfma");
 }
 
 extern "C" {
 
 int32_t egp_lstm_gate_layout(void) { return EGP_LSTM_GATES_UNIT_MAJOR; }
-
-int egp_lstm_fwd_f32(const float *gates_x, const float *w_hh, int32_t T, int32_t B, int32_t hidden, int32_t reverse,
-                     float *h_out, float *gates_save, float *cells_save, void *stream) {
-    EGP_REQUIRE(hidden == 64 || hidden == 128, "egp_lstm kernels are built for hidden size 64 and 128");
-    EGP_REQUIRE(T >= 0 && B >= 0, "negative size");
-    if (T == 0 || B == 0) return EGP_OK;
-    EGP_REQUIRE(gates_x && w_hh && h_out, "NULL pointer");
-    EGP_REQUIRE((gates_save == nullptr) == (cells_save == nullptr), "gates_save and cells_save go together");
-    hipStream_t s = (hipStream_t)stream;
-    LstmGroup g = {};
-    g.ld_g = 4 * hidden; g.rev_mask = reverse ? 1 : 0; g.ld_h = hidden; g.h[0] = h_out;
-    launch_fwd_mfma(hidden, 1, gates_x, w_hh, T, B, g, gates_save, cells_save, s);
-    return lstm_launch_check("k_lstm_fwd");
-}
-
-int egp_lstm_bwd_f32(const float *dh_out, const float *gates_save, const float *cells_save, const float *w_hh, int32_t T, int32_t B,
-                     int32_t hidden, int32_t reverse, float *d_pre, void *stream) {
-    EGP_REQUIRE(hidden == 64 || hidden == 128, "egp_lstm kernels are built for hidden size 64 and 128");
-    EGP_REQUIRE(T >= 0 && B >= 0, "negative size");
-    if (T == 0 || B == 0) return EGP_OK;
-    EGP_REQUIRE(dh_out && gates_save && cells_save && w_hh && d_pre, "NULL pointer");
-    hipStream_t s = (hipStream_t)stream;
-    LstmGroup g = {};
-    g.ld_g = 4 * hidden; g.rev_mask = reverse ? 1 : 0; g.ld_dh = hidden; g.dh[0] = dh_out;
-    launch_bwd_mfma(hidden, 1, gates_save, cells_save, w_hh, T, B, g, d_pre, s);
-    return lstm_launch_check("k_lstm_bwd");
-}
-
-int egp_lstm_group_fwd_f32(const float *gates_x, const float *w_hh, int32_t T, int32_t B, int32_t hidden, int32_t n_problems,
-                           int32_t reverse_mask, float *const *h_out, int32_t ld_h, float *gates_save, float *cells_save, void *stream) {
-    return egp_lstm_group_fwd_len_f32(gates_x, w_hh, T, B, hidden, n_problems, reverse_mask, h_out, ld_h, gates_save, cells_save, nullptr, nullptr, 0,
-                                      nullptr, stream);
-}
-
-int egp_lstm_group_fwd_len_f32(const float *gates_x, const float *w_hh, int32_t T, int32_t B, int32_t hidden, int32_t n_problems,
-                               int32_t reverse_mask, float *const *h_out, int32_t ld_h, float *gates_save, float *cells_save,
-                               const int32_t *seq_order, const int32_t *seq_steps, int32_t leave_skipped, const int32_t *seq_base,
-                               void *stream) {
-    EGP_REQUIRE((seq_order == nullptr) == (seq_steps == nullptr), "seq_order and seq_steps go together");
-    EGP_REQUIRE(!seq_base || !gates_save || gates_save != gates_x, "a frame table cannot double as the saved gates (rows are shared between sequences)");
-    EGP_REQUIRE(hidden == 64 || hidden == 128, "egp_lstm kernels are built for hidden size 64 and 128");
-    EGP_REQUIRE(n_problems >= 1 && n_problems <= 4, "1..4 problems per group");
-    EGP_REQUIRE(T >= 0 && B >= 0, "negative size");
-    if (T == 0 || B == 0) return EGP_OK;
-    EGP_REQUIRE(gates_x && w_hh && h_out && ld_h >= hidden, "NULL pointer / h_out row stride below the hidden size");
-    EGP_REQUIRE((gates_save == nullptr) == (cells_save == nullptr), "gates_save and cells_save go together");
-    LstmGroup g = {};
-    g.ld_g = 4 * hidden * n_problems; g.rev_mask = reverse_mask; g.ld_h = ld_h; g.c_stride = (long)T * B * hidden;
-    for (int p = 0; p < n_problems; ++p) {
-        EGP_REQUIRE(h_out[p], "NULL h_out");
-        g.h[p] = h_out[p];
-    }
-    g.order = seq_order; g.steps = seq_steps; g.leave_skipped = seq_steps && leave_skipped; g.seq_base = seq_base;
-    launch_fwd_mfma(hidden, n_problems, gates_x, w_hh, T, B, g, gates_save, cells_save, (hipStream_t)stream);
-    return lstm_launch_check("k_lstm_fwd_mfma (group)");
-}
-
-int egp_lstm_window_last_f32(const float *gates_x, int32_t ld_g, const float *w_hh, const int32_t *seq_base, int32_t steps, int32_t B,
-                             int32_t hidden, int32_t reverse, float *out, int32_t ld_out, void *stream) {
-    EGP_REQUIRE(hidden == 64 || hidden == 128, "egp_lstm kernels are built for hidden size 64 and 128");
-    EGP_REQUIRE(steps >= 1 && B >= 0, "a window has at least one step, and no negative batch");
-    EGP_REQUIRE(ld_out >= hidden && ld_g >= 4 * hidden && ld_g % 4 == 0, "out row stride below the hidden size / projection row stride below 4H or unaligned");
-    if (B == 0) return EGP_OK;
-    EGP_REQUIRE(gates_x && w_hh && seq_base && out, "NULL pointer");
-    LstmGroup g = {};
-    g.ld_g = ld_g; g.rev_mask = reverse ? 1 : 0; g.ld_h = ld_out; g.h[0] = out; g.seq_base = seq_base;
-    launch_fwd_mfma(hidden, 1, gates_x, w_hh, steps, B, g, nullptr, nullptr, (hipStream_t)stream, true);
-    return lstm_launch_check("k_lstm_fwd_mfma (windows, last state)");
-}
-
-int egp_lstm_group_bwd_f32(const float *const *dh_out, int32_t ld_dh, const float *gates_save, const float *cells_save, const float *w_hh,
-                           int32_t T, int32_t B, int32_t hidden, int32_t n_problems, int32_t reverse_mask, float *d_pre, float *d_bias,
-                           void *stream) {
-    return egp_lstm_group_bwd_len_f32(dh_out, ld_dh, gates_save, cells_save, w_hh, T, B, hidden, n_problems, reverse_mask, d_pre, d_bias, nullptr,
-                                      nullptr, 0, stream);
-}
-
-int egp_lstm_group_bwd_len_f32(const float *const *dh_out, int32_t ld_dh, const float *gates_save, const float *cells_save, const float *w_hh,
-                               int32_t T, int32_t B, int32_t hidden, int32_t n_problems, int32_t reverse_mask, float *d_pre, float *d_bias,
-                               const int32_t *seq_order, const int32_t *seq_steps, int32_t leave_skipped, void *stream) {
-    return lstm_group_bwd(dh_out, ld_dh, gates_save, cells_save, w_hh, T, B, hidden, n_problems, reverse_mask, d_pre, d_bias, 0, seq_order,
-                          seq_steps, leave_skipped, stream);
-}
-
-int egp_lstm_group_bwd_rows_f32(const float *const *dh_out, int32_t ld_dh, const float *gates_save, const float *cells_save, const float *w_hh,
-                                int32_t T, int32_t B, int32_t hidden, int32_t n_problems, int32_t reverse_mask, float *d_pre, float *d_bias_rows,
-                                const int32_t *seq_order, const int32_t *seq_steps, int32_t leave_skipped, void *stream) {
-    EGP_REQUIRE(d_bias_rows, "NULL d_bias_rows");
-    if (T == 0 && B > 0 && n_problems >= 1 && n_problems <= 4) {     // nothing to sweep: every row's sum is zero
-        EGP_HIP_CHECK(hipMemsetAsync(d_bias_rows, 0, sizeof(float) * (size_t)n_problems * B * 4 * hidden, (hipStream_t)stream));
-        return EGP_OK;
-    }
-    return lstm_group_bwd(dh_out, ld_dh, gates_save, cells_save, w_hh, T, B, hidden, n_problems, reverse_mask, d_pre, d_bias_rows, 1, seq_order,
-                          seq_steps, leave_skipped, stream);
-}
+int egp_lstm_fwd_f32(const egp_lstm_desc *desc, void *stream) { return lstm_sweep(desc, false, stream); }
+int egp_lstm_bwd_f32(const egp_lstm_desc *desc, void *stream) { return lstm_sweep(desc, true, stream); }
 
 }  // extern "C"

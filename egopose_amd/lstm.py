@@ -11,7 +11,6 @@ float32, zero initial state: exactly what ``RNN.batch_forward`` of the reference
 from __future__ import annotations
 
 import ctypes as C
-import os
 
 import numpy as np
 import torch
@@ -31,18 +30,39 @@ def _s():
     return L.current_stream()
 
 
-def _p(t):
-    return C.c_void_p(t.data_ptr()) if t is not None else C.c_void_p(0)
+_LAYOUT_CHECKED = False
+
+
+def _lib():
+    """The library; on this module's first use of it the gate layout is checked: everything here permutes for the unit-major one."""
+    global _LAYOUT_CHECKED
+    lib = L.load()
+    if not _LAYOUT_CHECKED:
+        if lib.egp_lstm_gate_layout() != L.EGP_LSTM_GATES_UNIT_MAJOR:
+            raise L.EgpError("egopose_amd.lstm needs the unit-major gate layout (EGP_LSTM_GATES_UNIT_MAJOR)")
+        _LAYOUT_CHECKED = True
+    return lib
+
+
+def _desc(T, B, H, P, mask, w_hh, **fields):
+    """An egp_lstm_desc (include/egopose_hip.h) with the problem fields set; `fields`: the others, tensors as their addresses."""
+    d = L.LstmDesc(T=T, B=B, hidden=H, n_problems=P, reverse_mask=mask, w_hh=w_hh.data_ptr())
+    for k, v in fields.items():
+        setattr(d, k, v.data_ptr() if torch.is_tensor(v) else v)
+    return d
+
+
+def _slabs(addresses):
+    """h_out / dh_out of a descriptor from the problems' addresses."""
+    return (C.c_void_p * 4)(*addresses)
 
 
 _PERM = {}
 
 
 def _gate_perm(hidden, device):
-    """Row permutation W_ih -> the kernels' gate layout (include/egopose_hip.h): unit-major column n = 4*u + g
-    takes torch row g*H + u; None when the build uses torch's own order."""
-    if L.load().egp_lstm_gate_layout() == 0:
-        return None
+    """Row permutation W_ih -> the kernels' gate layout (include/egopose_hip.h) and its inverse: unit-major column
+    n = 4*u + g takes torch row g*H + u."""
     key = (hidden, str(device))
     if key not in _PERM:
         n = torch.arange(4 * hidden, device=device)
@@ -65,15 +85,12 @@ class LstmDirection(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, x, w_ih, w_hh, b_ih, b_hh, reverse, train):
-        lib = L.load()
+        lib = _lib()
         T, B, D = x.shape
         HIDDEN = w_hh.shape[1]
         x2 = x.reshape(T * B, D)
-        pp = _gate_perm(HIDDEN, x.device)
-        bias = b_ih + b_hh
-        w_in = w_ih
-        if pp is not None:
-            w_in, bias = w_ih.index_select(0, pp[0]), bias.index_select(0, pp[0])
+        perm, _ = _gate_perm(HIDDEN, x.device)
+        w_in, bias = w_ih.index_select(0, perm), (b_ih + b_hh).index_select(0, perm)
         if G.enabled():                     # bf16 matrix cores, split operands (csrc/egp_gemm.hip)
             gx = G.linear_fwd(x2, w_in.contiguous(), bias).view(T, B, 4 * HIDDEN)
         else:
@@ -89,8 +106,9 @@ class LstmDirection(torch.autograd.Function):
         w_hh_c = w_hh.contiguous()
         # the activated gates overwrite the pre-activations in place (a thread reads its part of gx[t] before it
         # writes the same addresses)
-        L.check(lib.egp_lstm_fwd_f32(_p(gx), _p(w_hh_c), T, B, HIDDEN, 1 if reverse else 0, _p(h),
-                                     _p(gx if train else None), _p(cells), _s()), "egp_lstm_fwd_f32")
+        d = _desc(T, B, HIDDEN, 1, 1 if reverse else 0, w_hh_c, gates_x=gx, h_out=_slabs([h.data_ptr()]),
+                  gates_save=gx if train else None, cells_save=cells)
+        L.check(lib.egp_lstm_fwd_f32(d, _s()), "egp_lstm_fwd_f32")
         if train:
             ctx.save_for_backward(x2, w_in, w_hh_c, h_buf, gx, cells)
             ctx.reverse = bool(reverse)
@@ -99,34 +117,33 @@ class LstmDirection(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, dh):
-        lib = L.load()
+        lib = _lib()
         x2, w_in, w_hh, h_buf, gates, cells = ctx.saved_tensors
         T, B, D = ctx.shape
         HIDDEN = w_hh.shape[1]
         h = h_buf
         dpre = torch.empty(T, B, 4 * HIDDEN, dtype=h.dtype, device=h.device)
-        L.check(lib.egp_lstm_bwd_f32(_p(dh.contiguous()), _p(gates), _p(cells), _p(w_hh), T, B, HIDDEN,
-                                     1 if ctx.reverse else 0, _p(dpre), _s()), "egp_lstm_bwd_f32")
+        dh = dh.contiguous()
+        d = _desc(T, B, HIDDEN, 1, 1 if ctx.reverse else 0, w_hh, gates_save=gates, cells_save=cells,
+                  dh_out=_slabs([dh.data_ptr()]), d_pre=dpre)
+        L.check(lib.egp_lstm_bwd_f32(d, _s()), "egp_lstm_bwd_f32")
         h_prev = h_buf[1:] if ctx.reverse else h_buf[:T]
         # dW_ih | dW_hh | db in ONE batched GEMM over the time axis + a reduction: [dPre_t^T (x_t | h_prev_t | 1)]
         # (a single (4H x T*B) @ (T*B x D) product runs 3x slower in rocBLAS than T independent ones; separate
         # products per operand would read dPre three times)
-        pp = _gate_perm(HIDDEN, h.device)
+        _, inv = _gate_perm(HIDDEN, h.device)
         if G.enabled():
             # two split-K products over the (time, sequence) rows; the first also returns the bias gradient
             d2 = dpre.view(T * B, 4 * HIDDEN)
             dw_ih, dbias = G.linear_wgrad(d2, x2, want_bias=True)
             dw_hh = G.linear_wgrad(d2, h_prev.reshape(T * B, HIDDEN), want_bias=False)
-            if pp is not None:
-                dw_ih, dw_hh, dbias = dw_ih.index_select(0, pp[1]), dw_hh.index_select(0, pp[1]), dbias.index_select(0, pp[1])
+            dw_ih, dw_hh, dbias = dw_ih.index_select(0, inv), dw_hh.index_select(0, inv), dbias.index_select(0, inv)
             d_w_ih = dw_ih if ctx.needs_input_grad[1] else None
             d_w_hh = dw_hh if ctx.needs_input_grad[2] else None
             d_b = dbias if (ctx.needs_input_grad[3] or ctx.needs_input_grad[4]) else None
         else:
             xh1 = torch.cat((x2.view(T, B, D), h_prev, h.new_ones(T, B, 1)), 2)
-            dw = torch.bmm(dpre.transpose(1, 2), xh1).sum(0)                   # (4H, D + H + 1), rows in the kernels' gate layout
-            if pp is not None:
-                dw = dw.index_select(0, pp[1])
+            dw = torch.bmm(dpre.transpose(1, 2), xh1).sum(0).index_select(0, inv)      # (4H, D + H + 1), rows back in torch's gate order
             d_w_ih = dw[:, :D].contiguous() if ctx.needs_input_grad[1] else None
             d_w_hh = dw[:, D:D + HIDDEN].contiguous() if ctx.needs_input_grad[2] else None
             d_b = dw[:, D + HIDDEN].contiguous() if (ctx.needs_input_grad[3] or ctx.needs_input_grad[4]) else None
@@ -145,15 +162,14 @@ class LstmGroup(torch.autograd.Function):
     @staticmethod
     def forward(ctx, x, reverse_mask, P, width, train, ragged, frames, *params):
         """`ragged` = None or (order, steps): int32 device tensors of B entries (include/egopose_hip.h,
-        egp_lstm_group_fwd_len_f32) -- forward-running problems stop at the longest sequence of their workgroup.
+        egp_lstm_desc.seq_order / seq_steps) -- forward-running problems stop at the longest sequence of their workgroup.
         `frames` = None or (table (F, D), base int32 (B,)) with x[t, b] == table[base[b] + t]: the input projection then runs over
         the table's F rows once and the sweeps read row base[b] + t of it (the reference evaluates W_ih x_t per window row,
         models/rnn.py:45-61; windows of one take overlap, so most of those rows repeat)."""
-        lib = L.load()
+        lib = _lib()
         T, B, D = x.shape
         w_ih, w_hh, b_ih, b_hh = params[0::4], params[1::4], params[2::4], params[3::4]
         H = w_hh[0].shape[1]
-        perm, inv = _gate_perm(H, x.device)
         x2 = x.reshape(T * B, D)
         # problems that run forward in time first: their gate columns are one block (a ragged batch visits fewer rows for them)
         pord = [p for p in range(P) if not (reverse_mask >> p) & 1] + [p for p in range(P) if (reverse_mask >> p) & 1]
@@ -192,14 +208,15 @@ class LstmGroup(torch.autograd.Function):
         h_buf[:, T + 1].zero_()
         cells = torch.empty(P, T, B, H, dtype=x.dtype, device=x.device) if train else None
         base, esz = h_buf.data_ptr(), h_buf.element_size()
-        ptrs = (C.c_void_p * P)(*[base + esz * (((p // width) * (T + 2) + 1) * B * W + (p % width) * H) for p in pord])
+        ptrs = _slabs([base + esz * (((p // width) * (T + 2) + 1) * B * W + (p % width) * H) for p in pord])
         order, steps = (ragged.order, ragged.steps) if ragged is not None else (None, None)
         # with row lists every later product visits only the rows the workgroups stepped through: the skipped steps of the
         # sweeps (3.6-3.9 TB/s of HBM traffic) need not be filled with zeros
         leave = int(rows is not None and train)
         gates = gates_buf if seq_base is not None else (gx if train else None)             # (a dense projection doubles as the saved gates)
-        L.check(lib.egp_lstm_group_fwd_len_f32(_p(gx), _p(w_hh_all), T, B, H, P, kmask, ptrs, W,
-                                               _p(gates), _p(cells), _p(order), _p(steps), leave, _p(seq_base), _s()), "egp_lstm_group_fwd_len_f32")
+        d = _desc(T, B, H, P, kmask, w_hh_all, gates_x=gx, h_out=ptrs, ld_h=W, gates_save=gates, cells_save=cells, seq_base=seq_base,
+                  seq_order=order, seq_steps=steps, leave_skipped=leave)
+        L.check(lib.egp_lstm_fwd_f32(d, _s()), "egp_lstm_fwd_f32")
         outs = tuple(h_buf[i, 1:T + 1] for i in range(n_out))
         if train:
             ctx.save_for_backward(x2, w_in, w_hh_all, h_buf, gates, cells)
@@ -209,21 +226,22 @@ class LstmGroup(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, *douts):
-        lib = L.load()
+        lib = _lib()
         x2, w_in, w_hh_all, h_buf, gates, cells = ctx.saved_tensors
         T, B, D, H, P, width, reverse_mask = ctx.meta
         W = width * H
-        perm, inv = _gate_perm(H, x2.device)
+        _, inv = _gate_perm(H, x2.device)
         douts = [d.contiguous() if d is not None else h_buf.new_zeros(T, B, W) for d in douts]
         ragged, rows, pord, nf, kmask = ctx.ragged, ctx.rows, ctx.pord, ctx.nf, ctx.kmask
         esz = h_buf.element_size()
-        ptrs = (C.c_void_p * P)(*[douts[p // width].data_ptr() + esz * (p % width) * H for p in pord])
+        ptrs = _slabs([douts[p // width].data_ptr() + esz * (p % width) * H for p in pord])
         dpre = torch.empty(T * B, P * 4 * H, dtype=x2.dtype, device=x2.device)
         db_rows = torch.empty(P, B, 4 * H, dtype=x2.dtype, device=x2.device)      # every row written: sums over t, reduced below in a fixed order
         order, steps = (ragged.order, ragged.steps) if ragged is not None else (None, None)
         leave = int(bool(ctx.leave) and not ctx.needs_input_grad[0])     # (d_x = d_pre W_in reads every row)
-        L.check(lib.egp_lstm_group_bwd_rows_f32(ptrs, W, _p(gates), _p(cells), _p(w_hh_all), T, B, H, P, kmask, _p(dpre), _p(db_rows),
-                                                _p(order), _p(steps), leave, _s()), "egp_lstm_group_bwd_rows_f32")
+        d = _desc(T, B, H, P, kmask, w_hh_all, gates_save=gates, cells_save=cells, dh_out=ptrs, ld_dh=W, d_pre=dpre,
+                  d_bias=db_rows, d_bias_rows=1, seq_order=order, seq_steps=steps, leave_skipped=leave)
+        L.check(lib.egp_lstm_bwd_f32(d, _s()), "egp_lstm_bwd_f32")
         db = db_rows.sum(1)
         d3 = dpre.view(T, B, P * 4 * H)
         use_g = G.enabled()
@@ -269,7 +287,7 @@ def _wants_grad(x, params):
 
 def group_available(x, cells):
     """Grouped sweeps need the matrix-core kernels, at most four problems and identical cell shapes."""
-    if not cells or len(cells) > 4 or L.load().egp_lstm_gate_layout() == 0:
+    if not cells or len(cells) > 4:
         return False
     c0 = cells[0]
     return all(available(x, c) and c.hidden_size == c0.hidden_size and c.input_size == c0.input_size for c in cells)
@@ -325,19 +343,19 @@ def lstm_group(x, cells, reverses, pairs=False, ragged=None, frames=None):
     return list(LstmGroup.apply(x.contiguous(), mask, len(cells), 2 if pairs else 1, _wants_grad(x, params), ragged, frames, *params))
 
 
-WINDOW_CALLS = 0              # launches of egp_lstm_window_last_f32 so far (tests assert which path ran)
+WINDOW_CALLS = 0              # last_only launches of egp_lstm_fwd_f32 so far (tests assert which path ran)
 
 
 def window_available(table, cell):
-    """The windowed last-state kernel serves what the sweeps serve, in the unit-major gate layout."""
-    return available(table, cell) and L.load().egp_lstm_gate_layout() != 0
+    """The windowed last-state kernel serves what the sweeps serve."""
+    return available(table, cell)
 
 
 @torch.no_grad()
 def window_last(cell, table, seq_base, steps, reverse, out):
     """Hidden state of `cell` after `steps` steps from zero over each window of consecutive frames of `table` (F, D): window b =
     frames seq_base[b] .. seq_base[b] + steps - 1, walked from its last frame to its first when `reverse`
-    (egp_lstm_window_last_f32, include/egopose_hip.h). The input projection runs over the table's F rows once, whatever the
+    (egp_lstm_desc.last_only, include/egopose_hip.h). The input projection runs over the table's F rows once, whatever the
     windows share. `out`: (B, H) float32 rows to write, row stride free (a column block of a wider table). Inference only."""
     global WINDOW_CALLS
     H, B = cell.hidden_size, seq_base.shape[0]
@@ -358,9 +376,10 @@ def window_last(cell, table, seq_base, steps, reverse, out):
     perm, _ = _gate_perm(H, table.device)
     w_in, bias = cell.weight_ih.index_select(0, perm), (cell.bias_ih + cell.bias_hh).index_select(0, perm)
     gx = G.linear_fwd(table, w_in.contiguous(), bias) if G.enabled() else torch.addmm(bias, table, w_in.t())      # (F, 4H)
-    L.check(L.load().egp_lstm_window_last_f32(_p(gx), 4 * H, _p(cell.weight_hh.contiguous()), _p(seq_base), int(steps), B, H,
-                                              1 if reverse else 0, _p(out), out.stride(0) if B > 1 else max(out.stride(0), H), _s()),
-            "egp_lstm_window_last_f32")
+    w_hh = cell.weight_hh.contiguous()
+    d = _desc(int(steps), B, H, 1, 1 if reverse else 0, w_hh, gates_x=gx, h_out=_slabs([out.data_ptr()]),
+              ld_h=out.stride(0) if B > 1 else max(out.stride(0), H), last_only=1, seq_base=seq_base)
+    L.check(_lib().egp_lstm_fwd_f32(d, _s()), "egp_lstm_fwd_f32")
     WINDOW_CALLS += 1
     return out
 

@@ -500,10 +500,11 @@ typedef struct egp_tcn_desc egp_tcn_desc;
 int egp_tcn_conv_f32(const egp_tcn_desc *desc, void *stream);
 
 /* ---------------------------------------------------------------------------------------- LSTM
- * Recurrent sweep of ONE direction of the video-context LSTM (hidden size 64 or 128, float32, zero initial state):
- * the t-loop of RNN.batch_forward (models/rnn.py:45-61) in one launch.
- *   gates_x [T][B][4H] = x_t W_ih^T + b_ih + b_hh;  w_hh [4H][H] (torch.nn.LSTMCell order: rows i, f, g, o)
- *   h_out [T][B][H];  gates_save [T][B][4H] (may alias gates_x) / cells_save [T][B][H]: both NULL for inference
+ * Recurrent sweeps of the video-context / state LSTMs (hidden size 64 or 128, float32, zero initial state): the t-loop of
+ * RNN.batch_forward (models/rnn.py:45-61) in one launch, for 1..4 problems at once. One descriptor serves the forward sweep
+ * (egp_lstm_fwd_f32) and backward-through-time (egp_lstm_bwd_f32); each reads the problem and ragged fields and its own group,
+ * so a descriptor filled for a training forward can be handed to the backward as it stands. A zeroed descriptor with the fields
+ * one needs filled in is valid. T == 0 or B == 0: nothing to do, EGP_OK before any pointer is looked at.
  * gates_x, gates_save and d_pre use the layout egp_lstm_gate_layout() reports: EGP_LSTM_GATES_TORCH = [gate][unit] as
  * torch (column g*H + u), EGP_LSTM_GATES_UNIT_MAJOR = [unit][gate] (column 4*u + g; what the matrix-core kernels use:
  * the four gates of a unit are one 16-byte access). The caller permutes the rows of W_ih and of the bias accordingly
@@ -511,66 +512,54 @@ int egp_tcn_conv_f32(const egp_tcn_desc *desc, void *stream);
 #define EGP_LSTM_GATES_TORCH 0
 #define EGP_LSTM_GATES_UNIT_MAJOR 1
 int32_t egp_lstm_gate_layout(void);
-int egp_lstm_fwd_f32(const float *gates_x, const float *w_hh, int32_t T, int32_t B, int32_t hidden, int32_t reverse,
-                     float *h_out, float *gates_save, float *cells_save, void *stream);
-/* backward-through-time of the same sweep: d_pre [T][B][256] = gradient w.r.t. the pre-activation gates; the
- * caller forms dW_ih = d_pre^T X, dW_hh = d_pre^T H_prev, db = sum d_pre with library GEMMs */
-int egp_lstm_bwd_f32(const float *dh_out, const float *gates_save, const float *cells_save, const float *w_hh,
-                     int32_t T, int32_t B, int32_t hidden, int32_t reverse, float *d_pre, void *stream);
-/* n_problems (1..4) sweeps over the same (T, B) in ONE launch -- the two directions of a bi-LSTM and/or the LSTMs of several
- * nets reading the same windows (a sweep is latency-bound: grouped problems fill the CUs a single one leaves idle).
- * Needs the unit-major layout (egp_lstm_gate_layout() == EGP_LSTM_GATES_UNIT_MAJOR).
- *   gates_x / gates_save / d_pre [T*B][n_problems*4H]: columns p*4H .. (p+1)*4H-1 belong to problem p (what one
- *   projection GEMM against the row-stacked W_ih of all problems produces);  w_hh [n_problems][4H][H];
- *   reverse_mask bit p: problem p runs backwards in time;  h_out[p] -> problem p's hidden states, row (t, b) at
- *   h_out[p] + (t*B + b)*ld_h (ld_h = H for a dense [T][B][H]; 2H when the two directions of a bi-LSTM fill the halves of
- *   one [T][B][2H] buffer);  cells_save [n_problems][T][B][H];  dh_out[p] / ld_dh likewise;  d_bias (optional)
- *   [n_problems][4H], zeroed by the caller, receives sum over (t, b) of d_pre (float atomics). */
-int egp_lstm_group_fwd_f32(const float *gates_x, const float *w_hh, int32_t T, int32_t B, int32_t hidden, int32_t n_problems,
-                           int32_t reverse_mask, float *const *h_out, int32_t ld_h, float *gates_save, float *cells_save, void *stream);
-int egp_lstm_group_bwd_f32(const float *const *dh_out, int32_t ld_dh, const float *gates_save, const float *cells_save, const float *w_hh,
-                           int32_t T, int32_t B, int32_t hidden, int32_t n_problems, int32_t reverse_mask, float *d_pre, float *d_bias,
-                           void *stream);
-
-/* The same for a RAGGED batch (the update's video contexts: episodes of 1..200 steps padded to one window length, as
- * VideoStateNet.initialize('train') pads them, models/video_state_net.py:40-59). seq_order[p] (device, B entries, a
- * permutation of 0..B-1): the sequence at position p -- workgroups take consecutive positions, sort them by length;
- * seq_steps[p]: the time steps the sequence at position p needs counted from t = 0 (its outputs at t >= seq_steps[p] are
- * never read and receive no gradient). Problems that run forward in time stop there (h_out / d_pre of the skipped steps are
- * written as zeros; with leave_skipped != 0 only up to the longest sequence of the ALIGNED GROUP OF 8 POSITIONS and not at
- * all beyond: the sweeps move 3.6-3.9 TB/s, and a caller whose products visit only the rows t < that maximum of each group
- * of 8 -- row lists, egp_gemm_desc.a_rows / a_krows -- saves a tenth of their bytes);
- * problems that run backward in time go through all T steps. NULL / NULL = the plain functions.
- * seq_base (forward, optional; device, B entries): the sequences are windows of consecutive FRAMES of one table -- x[t][b] = frame
- * seq_base[b] + t, as VideoStateNet's windows cnn_feat[take][start - m : start + len + m] are (models/video_state_net.py:52-55) --
- * and gates_x is the projection of that table, [frames][P * 4H]: row seq_base[b] + t is read for (t, b). The projection then runs
- * once per unique frame instead of once per window row. gates_save must be a buffer of its own ([T * B][P * 4H]) in that case. */
-int egp_lstm_group_fwd_len_f32(const float *gates_x, const float *w_hh, int32_t T, int32_t B, int32_t hidden, int32_t n_problems,
-                               int32_t reverse_mask, float *const *h_out, int32_t ld_h, float *gates_save, float *cells_save,
-                               const int32_t *seq_order, const int32_t *seq_steps, int32_t leave_skipped, const int32_t *seq_base,
-                               void *stream);
-int egp_lstm_group_bwd_len_f32(const float *const *dh_out, int32_t ld_dh, const float *gates_save, const float *cells_save, const float *w_hh,
-                               int32_t T, int32_t B, int32_t hidden, int32_t n_problems, int32_t reverse_mask, float *d_pre, float *d_bias,
-                               const int32_t *seq_order, const int32_t *seq_steps, int32_t leave_skipped, void *stream);
-/* egp_lstm_group_bwd_len_f32 with the bias gradient left per row: d_bias_rows [n_problems][B][4H] (required, every element is
- * written, no zeroing needed) receives, for each row b, the sum over t of d_pre. The caller sums over b in an order of its
- * choosing; no float atomics, so the same inputs give the same bits on every run. */
-int egp_lstm_group_bwd_rows_f32(const float *const *dh_out, int32_t ld_dh, const float *gates_save, const float *cells_save, const float *w_hh,
-                                int32_t T, int32_t B, int32_t hidden, int32_t n_problems, int32_t reverse_mask, float *d_pre, float *d_bias_rows,
-                                const int32_t *seq_order, const int32_t *seq_steps, int32_t leave_skipped, void *stream);
-
-/* Windowed recurrence, last state only (inference): B windows of `steps` consecutive frames of one table, each swept from zero
- * state, and only the hidden state after the last step is kept. This is the backward direction of the ONLINE evaluation
- * (ego_pose/ego_mimic_eval.py:143-145 re-initialises the policy's video net on cnn_feat[:t + 2*fr_margin + 1] at every tick t;
- * row t + fr_margin of rnn_b's sweep over that prefix, models/rnn.py:45-61, is its state after fr_margin + 1 steps from the
- * prefix's end): one launch for all ticks of a take instead of a sweep per tick.
- *   gates_x [n_frames][ld_g]: per-FRAME input projection + both biases, unit-major gate layout, ld_g >= 4H (a multiple of 4);
- *   w_hh [4H][H];  seq_base (device, B entries): window b = frames seq_base[b] .. seq_base[b] + steps - 1 (windows may overlap;
- *   the caller keeps them inside the table);  reverse: walked from the last frame of the window to the first;
- *   out[b * ld_out + u] (u < H, ld_out >= H) = h of window b after `steps` (>= 1) steps -- nothing else is written, so `out` may
- *   point into a wider table (the right half of a [T][2H] bi-LSTM context).  B == 0: nothing to do. */
-int egp_lstm_window_last_f32(const float *gates_x, int32_t ld_g, const float *w_hh, const int32_t *seq_base, int32_t steps, int32_t B,
-                             int32_t hidden, int32_t reverse, float *out, int32_t ld_out, void *stream);
+typedef struct egp_lstm_desc {
+    /* Problem: n_problems (1..4) sweeps over the same (T, B) in ONE launch -- the two directions of a bi-LSTM and/or the LSTMs of
+     * several nets reading the same windows (a sweep is latency-bound: grouped problems fill the CUs a single one leaves idle).
+     * reverse_mask bit p: problem p runs t = T-1 .. 0;  w_hh [n_problems][4H][H] (torch.nn.LSTMCell order: rows i, f, g, o). */
+    int32_t T, B, hidden, n_problems, reverse_mask;
+    const float *w_hh;
+    /* Forward. gates_x [T*B][ld_g] = x_t W_ih^T + b_ih + b_hh: columns p*4H .. (p+1)*4H-1 belong to problem p (what one projection
+     * GEMM against the row-stacked W_ih of all problems produces). ld_g (a multiple of 4; 0 = dense, n_problems*4H) is also the row
+     * stride of gates_save and d_pre.  h_out[p] -> problem p's hidden states, row (t, b) at h_out[p] + (t*B + b)*ld_h (ld_h 0 = H,
+     * a dense [T][B][H]; 2H when the two directions of a bi-LSTM fill the halves of one [T][B][2H] buffer).
+     * gates_save [T*B][ld_g] (activated gates; may alias gates_x) / cells_save [n_problems][T][B][H]: both NULL for inference.
+     *   seq_base (optional; device, B entries): the sequences are windows of consecutive FRAMES of one table -- x[t][b] = frame
+     *     seq_base[b] + t, as VideoStateNet's windows cnn_feat[take][start - m : start + len + m] are (models/video_state_net.py:52-55)
+     *     -- and gates_x is the projection of that table, [frames][ld_g]: row seq_base[b] + t is read for (t, b). The projection then
+     *     runs once per unique frame instead of once per window row. gates_save must be a buffer of its own in that case.
+     *   last_only (inference): only the hidden state after the last of the T (>= 1) steps is kept, h_out[0][b*ld_h + u] -- nothing
+     *     else is written, so h_out[0] may point into a wider table (the right half of a [T][2H] bi-LSTM context). One problem over
+     *     a frame table (seq_base required; windows may overlap, the caller keeps them inside the table), no saves, no ragged lists.
+     *     This is the backward direction of the ONLINE evaluation (ego_pose/ego_mimic_eval.py:143-145 re-initialises the policy's
+     *     video net on cnn_feat[:t + 2*fr_margin + 1] at every tick t; row t + fr_margin of rnn_b's sweep over that prefix,
+     *     models/rnn.py:45-61, is its state after fr_margin + 1 steps from the prefix's end): one launch for all ticks of a take. */
+    const float *gates_x; int32_t ld_g;
+    float *h_out[4]; int32_t ld_h;
+    float *gates_save; float *cells_save;
+    int32_t last_only;
+    const int32_t *seq_base;
+    /* Backward-through-time of the same sweep, from gates_save / cells_save: d_pre [T*B][ld_g] = gradient w.r.t. the pre-activation
+     * gates; the caller forms dW_ih = d_pre^T X, dW_hh = d_pre^T H_prev with GEMMs. dh_out[p] / ld_dh as h_out[p] / ld_h.
+     * d_bias (optional): d_bias_rows == 0 -> [n_problems][4H], zeroed by the caller, receives the sum over (t, b) of d_pre (float
+     * atomics); d_bias_rows != 0 -> [n_problems][B][4H] (required then; every element is written, no zeroing needed) receives, for
+     * each row b, the sum over t of d_pre: the caller sums over b in an order of its choosing, and the same inputs give the same
+     * bits on every run (T == 0: zeros). */
+    const float *dh_out[4]; int32_t ld_dh;
+    float *d_pre;
+    float *d_bias; int32_t d_bias_rows;
+    /* Ragged batches, both ways (the update's video contexts: episodes of 1..200 steps padded to one window length, as
+     * VideoStateNet.initialize('train') pads them, models/video_state_net.py:40-59). seq_order[p] (device, B entries, a
+     * permutation of 0..B-1): the sequence at position p -- workgroups take consecutive positions, sort them by length;
+     * seq_steps[p]: the time steps the sequence at position p needs counted from t = 0 (its outputs at t >= seq_steps[p] are
+     * never read and receive no gradient). Problems that run forward in time stop there (h_out / d_pre of the skipped steps are
+     * written as zeros; with leave_skipped != 0 only up to the longest sequence of the ALIGNED GROUP OF 8 POSITIONS and not at
+     * all beyond: the sweeps move 3.6-3.9 TB/s, and a caller whose products visit only the rows t < that maximum of each group
+     * of 8 -- row lists, egp_gemm_desc.a_rows / a_krows -- saves a tenth of their bytes);
+     * problems that run backward in time go through all T steps. Both NULL: every sequence runs T steps. */
+    const int32_t *seq_order; const int32_t *seq_steps; int32_t leave_skipped;
+} egp_lstm_desc;
+int egp_lstm_fwd_f32(const egp_lstm_desc *desc, void *stream);
+int egp_lstm_bwd_f32(const egp_lstm_desc *desc, void *stream);
 
 /* ----------------------------------------------------------------------------------------
  * K8: dynamics terms on the GPU. From (qpos, qvel) per env: body frame positions (mjData.xpos[1:]),

@@ -38,7 +38,7 @@ def test_ctypes_mirrors_have_the_library_s_struct_sizes():
                "egp_surrogate_desc": _lib.SurrogateDesc, "egp_engine_desc": _lib.EngineDesc,
                "egp_rollout_tick": _lib.RolloutTick, "egp_ppo_loss_desc": _lib.PpoLossDesc,
                "egp_adam_segment": _lib.AdamSegment, "egp_host_probe_result": _lib.HostProbeResult,
-               "egp_policy_desc": _lib.PolicyDesc}
+               "egp_policy_desc": _lib.PolicyDesc, "egp_lstm_desc": _lib.LstmDesc}
     header = open(os.path.join(REPO, "include", "egopose_hip.h")).read()
     declared = set(re.findall(r"^\} (egp_[a-z_]+);", header, flags=re.M))
     assert declared == set(mirrors), "a struct in include/egopose_hip.h has no ctypes mirror (or the reverse)"

@@ -273,13 +273,12 @@ def test_no_grad_passes_take_the_inference_kernels(monkeypatch):
 
         def __getattr__(self, name):
             fn = getattr(self._lib, name)
-            if name not in ("egp_lstm_fwd_f32", "egp_lstm_group_fwd_len_f32"):
+            if name != "egp_lstm_fwd_f32":
                 return fn
-            k = 7 if name == "egp_lstm_fwd_f32" else 9            # gates_out, cells_out follow (include/egopose_hip.h)
 
-            def wrapped(*a):
-                self.saves.append((name, a[k].value, a[k + 1].value))
-                return fn(*a)
+            def wrapped(desc, stream):
+                self.saves.append((name, desc.gates_save, desc.cells_save))      # egp_lstm_desc (include/egopose_hip.h)
+                return fn(desc, stream)
             return wrapped
 
     spy = Spy(lstm.L.load())
@@ -299,6 +298,71 @@ def test_no_grad_passes_take_the_inference_kernels(monkeypatch):
     torch.testing.assert_close(b2.detach(), b)
     (a2.sum() + b2.sum()).backward()
     assert all(c.weight_hh.grad is not None for c in cells)
+
+
+@pytest.mark.parametrize("ragged", [False, True])
+@pytest.mark.parametrize("H,B,P", [(64, 5, 2), (128, 8, 1)])
+def test_hand_filled_descriptor_equals_lstm_group(H, B, P, ragged):
+    """An egp_lstm_desc filled in here, field by field, handed to egp_lstm_fwd_f32 and egp_lstm_bwd_f32 as it stands: the same
+    kernels with the same arguments as lstm.lstm_group's, so its outputs and the gradients formed from d_pre and the bias rows
+    as lstm.LstmGroup.backward forms them are the module's bit for bit. H = 64: two problems, the second reversed, filling the
+    halves of one (T, B, 2H) buffer (ld_h = 2H), a ragged last workgroup; H = 128: one problem, full workgroups, ld_h left 0."""
+    from egopose_amd import _lib as L
+    from egopose_amd import gemm as G
+    from egopose_amd import lstm as hl
+    T, D, dev = 9, 24, torch.device("cuda", 0)
+    W, n_out, mask = (2 * H, 1, 0b10) if P == 2 else (H, 1, 0)
+    torch.manual_seed(H + B)
+    cells = [torch.nn.LSTMCell(D, H).to(dev) for _ in range(P)]
+    x = torch.randn(T, B, D, device=dev)
+    steps = np.array([T, 0, 4, 7, 2, 9, 1, 5][:B])
+    rg = hl.ragged_order(steps, dev) if ragged else None
+    inside = (torch.arange(T).unsqueeze(1) < torch.as_tensor(steps if ragged else np.full(B, T)).unsqueeze(0)).unsqueeze(2).to(dev)
+    dy = torch.randn(T, B, W, device=dev) * inside
+    xx = x.clone().requires_grad_(True)
+    outs = hl.lstm_group(xx, cells, [False, True][:P], pairs=P == 2, ragged=rg)
+    torch.autograd.backward(outs, [dy])
+
+    def wgrad(dq, hq):                                   # (T*B, n), (T*B, k) -> (n, k)
+        if G.enabled():
+            return G.linear_wgrad(dq, hq, want_bias=False)
+        return torch.bmm(dq.view(T, B, -1).transpose(1, 2), hq.view(T, B, -1)).sum(0)
+
+    n = torch.arange(4 * H, device=dev)
+    perm = (n % 4) * H + n // 4                          # kernel column 4u + gate <- torch row gate * H + u
+    inv = torch.argsort(perm)
+    with torch.no_grad():
+        x2 = x.reshape(T * B, D)
+        w_in = torch.cat([c.weight_ih[perm] for c in cells], 0)
+        bias = torch.cat([(c.bias_ih + c.bias_hh)[perm] for c in cells])
+        gx = G.linear_fwd(x2, w_in, bias) if G.enabled() else torch.addmm(bias, x2, w_in.t())
+        w_hh = torch.stack([c.weight_hh for c in cells]).contiguous()
+        h_buf = torch.zeros(n_out, T + 2, B, W, device=dev)           # zero | h_0 .. h_{T-1} | zero, as the module lays it out
+        cells_save = torch.empty(P, T, B, H, device=dev)
+        d_pre = torch.empty(T * B, P * 4 * H, device=dev)
+        db_rows = torch.empty(P, B, 4 * H, device=dev)
+        d = L.LstmDesc(T=T, B=B, hidden=H, n_problems=P, reverse_mask=mask, w_hh=w_hh.data_ptr())
+        d.gates_x, d.gates_save, d.cells_save = gx.data_ptr(), gx.data_ptr(), cells_save.data_ptr()
+        d.ld_h = d.ld_dh = W if P == 2 else 0
+        for p in range(P):
+            d.h_out[p] = h_buf[0, 1:, :, p * H:].data_ptr()
+            d.dh_out[p] = dy[:, :, p * H:].data_ptr()
+        d.d_pre, d.d_bias, d.d_bias_rows = d_pre.data_ptr(), db_rows.data_ptr(), 1
+        if ragged:
+            d.seq_order, d.seq_steps = rg.order.data_ptr(), rg.steps.data_ptr()
+        L.check(L.load().egp_lstm_fwd_f32(d, L.current_stream()), "egp_lstm_fwd_f32")
+        L.check(L.load().egp_lstm_bwd_f32(d, L.current_stream()), "egp_lstm_bwd_f32")
+        assert torch.equal(h_buf[0, 1:T + 1], outs[0].detach())
+        assert torch.equal(d_pre.mm(w_in).view(T, B, D), xx.grad)
+        dw_ih, db = wgrad(d_pre, x2), db_rows.sum(1)
+        for p, c in enumerate(cells):
+            rows, cols = slice(p * 4 * H, (p + 1) * 4 * H), slice(p * H, (p + 1) * H)
+            slab = h_buf[0, 2:] if (mask >> p) & 1 else h_buf[0, :T]       # h_prev: the buffer shifted by one slot
+            dw_hh = wgrad(d_pre[:, rows], slab.reshape(T * B, W)[:, cols])
+            assert torch.equal(dw_ih[rows][inv], c.weight_ih.grad)
+            assert torch.equal(dw_hh[inv], c.weight_hh.grad)
+            assert torch.equal(db[p][inv], c.bias_ih.grad) and torch.equal(db[p][inv], c.bias_hh.grad)
+        assert float(xx.grad.abs().max()) > 0 and all(float(c.weight_hh.grad.abs().max()) > 0 for c in cells)
 
 
 def test_video_reg_net_with_encoder_matches_float64_cpu_forward():
@@ -366,7 +430,7 @@ def test_bf16_encoder_keeps_float32_master_weights():
 @pytest.mark.parametrize("with_rows", [False, True])
 @pytest.mark.parametrize("T,B", [(40, 37), (220, 70), (9, 4), (150, 200)])
 def test_ragged_grouped_sweeps_match_the_full_ones_where_it_counts(T, B, with_rows):
-    """lstm.ragged_order / egp_lstm_group_*_len_f32: with per-sequence step counts the forward-running direction stops
+    """lstm.ragged_order / egp_lstm_desc.seq_order, seq_steps: with per-sequence step counts the forward-running direction stops
     early. Outputs inside every sequence's own steps (both directions) and ALL parameter gradients must equal the full
     sweeps' when the loss only looks at those outputs -- which is how the update uses the video context (rows beyond an
     episode are never gathered); the skipped outputs are zeros, or -- when row lists make every later product visit only the

@@ -19,7 +19,6 @@ Each case also shows that the tolerance tells a wrong answer: with the float64 r
 lost split term) and the outputs of one sequence shifted by one time step must each miss it by at least SELF_MARGIN.
 Measured: at least 16x (bf16 W_hh; d_x of the saturated case) and 25 000x (shift).
 """
-import ctypes as C
 import re
 
 import numpy as np
@@ -356,10 +355,10 @@ def test_saturated_gates_over_a_long_sequence_match_float64():
 
 
 def test_group_bwd_len_bias_gradient_contract():
-    """egp_lstm_group_bwd_len_f32 (still exported; tools/epoch_trace.py calls it) through ctypes: its d_bias is [P][4H],
+    """egp_lstm_bwd_f32 with d_bias_rows = 0 (nothing in lstm.py asks for it) through ctypes: its d_bias is [P][4H],
     summed over every (t, b) row with float atomics into a buffer the caller zeroed. It must equal the float64 sum of its
-    own d_pre, the fixed-order sum of egp_lstm_group_bwd_rows_f32's [P][B][4H] rows (to tolerance, not bits) and the
-    float64 reference's bias gradient; the two entry points' d_pre must be bit-identical. B = 4100 with ragged steps:
+    own d_pre, the fixed-order sum of the [P][B][4H] rows that d_bias_rows = 1 gives (to tolerance, not bits) and the
+    float64 reference's bias gradient; the two forms' d_pre must be bit-identical. B = 4100 with ragged steps:
     8-row workgroups whose last one has a dead quad."""
     from egopose_amd import _lib as L
     T, B, D, H, P = 60, 4100, 64, 64, 4
@@ -375,7 +374,7 @@ def test_group_bwd_len_bias_gradient_contract():
     inside = (torch.arange(T).unsqueeze(1) < torch.as_tensor(steps).unsqueeze(0)).unsqueeze(2).cuda()
     dys = [torch.randn(T, B, H, device="cuda", generator=g) * inside for _ in range(P)]
     ref = _Ref(x, cells, revs, [dys])
-    case = _Case("egp_lstm_group_bwd_len_f32, B=4100: %s" % _instantiation(H, B))
+    case = _Case("egp_lstm_bwd_f32 with d_bias [P][4H], B=4100: %s" % _instantiation(H, B))
     _set_tolerances(case, ref, False, inside)
 
     n = torch.arange(4 * H, device="cuda")
@@ -391,23 +390,24 @@ def test_group_bwd_len_bias_gradient_contract():
     h = torch.empty(P, T, B, H, device="cuda")
     gates = torch.empty(T * B, P * 4 * H, device="cuda")
     cells_save = torch.empty(P, T, B, H, device="cuda")
-    ptr = lambda t: C.c_void_p(t.data_ptr())
     s = L.current_stream()
-    L.check(lib.egp_lstm_group_fwd_len_f32(ptr(gx), ptr(w_hh), T, B, H, P, kmask, (C.c_void_p * P)(*[h[p].data_ptr() for p in range(P)]), H,
-                                           ptr(gates), ptr(cells_save), ptr(order), ptr(steps_sorted), 0, None, s), "fwd_len")
     dh = torch.stack(dys).contiguous()
-    dh_ptrs = (C.c_void_p * P)(*[dh[p].data_ptr() for p in range(P)])
     d_pre = torch.empty(T * B, P * 4 * H, device="cuda")
     d_bias = torch.zeros(P, 4 * H, device="cuda")
-    L.check(lib.egp_lstm_group_bwd_len_f32(dh_ptrs, H, ptr(gates), ptr(cells_save), ptr(w_hh), T, B, H, P, kmask, ptr(d_pre), ptr(d_bias),
-                                           ptr(order), ptr(steps_sorted), 0, s), "bwd_len")
+    d = L.LstmDesc(T=T, B=B, hidden=H, n_problems=P, reverse_mask=kmask, w_hh=w_hh.data_ptr(), gates_x=gx.data_ptr(), ld_h=H,
+                   gates_save=gates.data_ptr(), cells_save=cells_save.data_ptr(), ld_dh=H, d_pre=d_pre.data_ptr(),
+                   d_bias=d_bias.data_ptr(), d_bias_rows=0, seq_order=order.data_ptr(), seq_steps=steps_sorted.data_ptr())
+    for p in range(P):
+        d.h_out[p], d.dh_out[p] = h[p].data_ptr(), dh[p].data_ptr()
+    L.check(lib.egp_lstm_fwd_f32(d, s), "fwd")
+    L.check(lib.egp_lstm_bwd_f32(d, s), "bwd, d_bias [P][4H]")
     d_pre2 = torch.empty_like(d_pre)
     db_rows = torch.empty(P, B, 4 * H, device="cuda")
-    L.check(lib.egp_lstm_group_bwd_rows_f32(dh_ptrs, H, ptr(gates), ptr(cells_save), ptr(w_hh), T, B, H, P, kmask, ptr(d_pre2), ptr(db_rows),
-                                            ptr(order), ptr(steps_sorted), 0, s), "bwd_rows")
+    d.d_pre, d.d_bias, d.d_bias_rows = d_pre2.data_ptr(), db_rows.data_ptr(), 1
+    L.check(lib.egp_lstm_bwd_f32(d, s), "bwd, d_bias [P][B][4H]")
     torch.cuda.synchronize()
     assert torch.equal(d_pre, d_pre2)
-    _check_run(case, "fwd_len", ref, list(h), None, False, 0, mask=inside)
+    _check_run(case, "fwd", ref, list(h), None, False, 0, mask=inside)
     # the atomic [P][4H] sum against the float64 sum of the same d_pre and the rows form's fixed-order sum: float32 rounding of
     # the partial sums only, bounded by the sum of the magnitudes
     d64 = d_pre.double().view(T * B, P, 4 * H)

@@ -1,9 +1,8 @@
-"""egp_lstm_window_last_f32 (csrc/egp_lstm.hip: B windows of `steps` consecutive frames of one projection table, last hidden state
+"""egp_lstm_fwd_f32 with last_only (csrc/egp_lstm.hip: B windows of `steps` consecutive frames of one projection table, last hidden state
 only) against a float64 nn.LSTMCell loop on the CPU over the gathered windows (models/rnn.py:45-61), against the grouped forward
 sweep it shares its step with, its argument checks, and VideoStateNet.online_contexts on the device against its float64 definition
 (ego_pose/ego_mimic_eval.py:143-145)."""
 import copy
-import ctypes as C
 
 import numpy as np
 import pytest
@@ -54,21 +53,21 @@ def _bases(kind, B, rng):
     return b
 
 
-def _window_call(pr, H, base_dev, steps, reverse, B, out_ptr, ld_out, hidden=None, ld_g=None):
+def _window_call(pr, H, base_dev, steps, reverse, B, out_ptr, ld_out, hidden=None, ld_g=None, last_only=1):
+    """egp_lstm_fwd_f32 over the windows of the frame table, one problem; last_only: the state after `steps` steps alone."""
     from egopose_amd import _lib as L
-    lib = L.load()
-    return lib.egp_lstm_window_last_f32(pr["gx"].data_ptr(), 4 * H if ld_g is None else ld_g, pr["w_hh"].data_ptr(), base_dev.data_ptr(), steps,
-                                        B, H if hidden is None else hidden, reverse, out_ptr, ld_out, L.current_stream())
+    d = L.LstmDesc(T=steps, B=B, hidden=H if hidden is None else hidden, n_problems=1, reverse_mask=1 if reverse else 0,
+                   w_hh=pr["w_hh"].data_ptr(), gates_x=pr["gx"].data_ptr(), ld_g=4 * H if ld_g is None else ld_g, ld_h=ld_out,
+                   last_only=last_only, seq_base=base_dev.data_ptr())
+    d.h_out[0] = out_ptr
+    return L.load().egp_lstm_fwd_f32(d, L.current_stream())
 
 
 def _group_last(pr, H, base_dev, steps, reverse, B):
-    """The last state of egp_lstm_group_fwd_len_f32 over the same windows (one problem, frame table)."""
+    """The last state of the full sweep (every step's state stored) over the same windows."""
     from egopose_amd import _lib as L
-    lib = L.load()
     h = torch.full((steps, B, H), CANARY, device="cuda")
-    ptrs = (C.c_void_p * 1)(h.data_ptr())
-    L.check(lib.egp_lstm_group_fwd_len_f32(pr["gx"].data_ptr(), pr["w_hh"].data_ptr(), steps, B, H, 1, 1 if reverse else 0, ptrs, H, None, None,
-                                           None, None, 0, base_dev.data_ptr(), L.current_stream()), "egp_lstm_group_fwd_len_f32")
+    L.check(_window_call(pr, H, base_dev, steps, reverse, B, h.data_ptr(), H, last_only=0), "egp_lstm_fwd_f32")
     return h[0 if reverse else steps - 1]
 
 
@@ -86,7 +85,7 @@ def test_window_last_against_float64_and_the_grouped_sweep(H, B, reverse, kind):
     for steps in STEPS:
         buf = torch.full((B + 3, ld_out), CANARY, device="cuda")
         out = buf[:B, col0:col0 + H]
-        L.check(_window_call(pr, H, base_dev, steps, reverse, B, out.data_ptr(), ld_out), "egp_lstm_window_last_f32")
+        L.check(_window_call(pr, H, base_dev, steps, reverse, B, out.data_ptr(), ld_out), "egp_lstm_fwd_f32")
         got = out.cpu().numpy()
         want = _reference(pr, base, steps, reverse)
         err = np.abs(got - want).max()
@@ -111,7 +110,7 @@ def test_argument_errors_return_without_a_launch():
         rc = _window_call(pr, H, base_dev, **dict(ok, **bad))
         assert rc != 0, bad
         with pytest.raises(ValueError):
-            L.check(rc, "egp_lstm_window_last_f32")
+            L.check(rc, "egp_lstm_fwd_f32")
     assert _window_call(pr, H, base_dev, **dict(ok, B=0)) == 0                  # no window: a no-op
     assert _window_call(pr, H, base_dev, 3, 1, 0, None, H + 8) == 0
     torch.cuda.synchronize()

@@ -71,20 +71,18 @@ class LibProxy:
 
     def __getattr__(self, name):
         fn = getattr(self._lib, name)
-        if name in ("egp_lstm_group_fwd_len_f32", "egp_lstm_group_bwd_len_f32"):
-            def wrap(*a):
-                if name.endswith("fwd_len_f32"):
-                    T, B, H, P = a[2], a[3], a[4], a[5]
-                else:
-                    T, B, H, P = a[5], a[6], a[7], a[8]
-                return bracket("%s T=%d B=%d H=%d P=%d" % (name[4:], T, B, H, P), 0, 2.0 * T * B * P * 4 * H * H, lambda: fn(*a))
+        if name in ("egp_lstm_fwd_f32", "egp_lstm_bwd_f32"):
+            def wrap(d, stream):                         # d: egp_lstm_desc
+                T, B, H, P = d.T, d.B, d.hidden, d.n_problems
+                return bracket("%s T=%d B=%d H=%d P=%d" % (name[4:], T, B, H, P), 0, 2.0 * T * B * P * 4 * H * H, lambda: fn(d, stream))
             return wrap
         return fn
 
 
 proxy = LibProxy(lib)
 import egopose_amd.lstm as LS
-LS.L = type("Lmod", (), {"load": staticmethod(lambda: proxy), "check": staticmethod(L.check), "current_stream": staticmethod(L.current_stream)})
+LS._lib()                                                # (its first use of the library: the gate layout is checked)
+LS._lib = lambda: proxy
 _losses = O.ppo_losses
 
 

@@ -17,12 +17,14 @@ int main(int argc, char **argv) {
     hipMemcpy(gx, hv.data(), ng * 4, hipMemcpyHostToDevice);
     hipMemcpy(w, hv.data(), (size_t)P * 4 * H * H * 4, hipMemcpyHostToDevice);
     hipMemset(h, 0, (size_t)P * (T + 2) * B * H * 4);
-    float *hp[4];
-    for (int p = 0; p < P; ++p) hp[p] = h + ((size_t)p * (T + 2) + 1) * B * H;
+    egp_lstm_desc d = {};
+    d.T = T; d.B = B; d.hidden = H; d.n_problems = P; d.reverse_mask = 0xC; d.w_hh = w; d.gates_x = gx;
+    if (train) { d.gates_save = gx; d.cells_save = cells; }
+    for (int p = 0; p < P; ++p) d.h_out[p] = h + ((size_t)p * (T + 2) + 1) * B * H;
     hipEvent_t e0, e1; hipEventCreate(&e0); hipEventCreate(&e1);
     for (int rep = 0; rep < 3; ++rep) {
         hipEventRecord(e0);
-        if (egp_lstm_group_fwd_f32(gx, w, T, B, H, P, 0xC, hp, H, train ? gx : nullptr, train ? cells : nullptr, nullptr) != 0) return 1;
+        if (egp_lstm_fwd_f32(&d, nullptr) != 0) return 1;
         hipEventRecord(e1); hipEventSynchronize(e1);
         float ms; hipEventElapsedTime(&ms, e0, e1);
         printf("launch %d: %.1f us (%d workgroups)\n", rep, ms * 1e3, (B / 4) * P);

@@ -1,6 +1,6 @@
 """Can an LSTM sweep and an MLP GEMM of the update share the GPU? Each alone, then both enqueued on two streams.
 (The question behind running the value net's and the policy net's update on two streams.)"""
-import sys, os, ctypes as C
+import sys, os
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__)))))
 import torch
 from egopose_amd import _lib as L, gemm as G
@@ -14,18 +14,20 @@ dh = torch.randn(T, B, H, device=dev); dpre = torch.empty(T, B, 4 * H, device=de
 x = torch.randn(131072, 300, device=dev); W = torch.randn(200, 300, device=dev) * 0.05; b = torch.zeros(200, device=dev)
 out = torch.empty(131072, 200, device=dev)
 dy = torch.randn(131072, 200, device=dev)
-p = lambda t: C.c_void_p(t.data_ptr())
+d = L.LstmDesc(T=T, B=B, hidden=H, n_problems=1, w_hh=w.data_ptr(), gates_x=gx.data_ptr(), gates_save=gates.data_ptr(),
+               cells_save=cells.data_ptr(), d_pre=dpre.data_ptr())
+d.h_out[0], d.dh_out[0] = h.data_ptr(), dh.data_ptr()
 s1, s2 = torch.cuda.Stream(), torch.cuda.Stream()
 
 
 def lstm(stream):
     with torch.cuda.stream(stream):
-        L.check(lib.egp_lstm_fwd_f32(p(gx), p(w), T, B, H, 0, p(h), p(gates), p(cells), L.current_stream()), "fwd")
+        L.check(lib.egp_lstm_fwd_f32(d, L.current_stream()), "fwd")
 
 
 def lstm_b(stream):
     with torch.cuda.stream(stream):
-        L.check(lib.egp_lstm_bwd_f32(p(dh), p(gates), p(cells), p(w), T, B, H, 0, p(dpre), L.current_stream()), "bwd")
+        L.check(lib.egp_lstm_bwd_f32(d, L.current_stream()), "bwd")
 
 
 def gemm(stream, n=4):
