@@ -11,6 +11,8 @@
 //   C[M][N] = A[M][K] * B[K][N]      A given as [m][k] (k contiguous) or [k][m] (m contiguous),
 //                                    B given as [n][k] (k contiguous) or [k][n] (n contiguous)
 //   epilogue: + bias[n], ReLU, * (mask[m][n] > 0)       (bias + activation forward, dReLU in a data gradient)
+//             act_kind: tanh / sigmoid in place of ReLU; mask_kind: * (1 - m^2) / * m (1 - m) in place of the gate -- the
+//             derivatives of tanh / sigmoid from the layer's saved OUTPUT m (egp_act_dev.hpp), so `mask` stays that output
 //   split-K:  partial sums go to a workspace, a second launch reduces them in a fixed order (deterministic); used by
 //             the weight gradients (K = batch rows). A virtual column of ones appended to B yields the bias gradient
 //             (column sums of A^T) from the same launch.
@@ -21,6 +23,7 @@
 // operands whose memory is not k-contiguous the transpose is in the register naming (a wave reads 64 consecutive rows of
 // one k-row per load). The loads of tile s+2 are issued before tile s is multiplied; one barrier per k-tile.
 #include "egp_internal.hpp"
+#include "egp_act_dev.hpp"
 
 #include <type_traits>
 
@@ -83,6 +86,7 @@ struct GemmArgs {
     float *C; long ldc;
     const float *bias; int relu;
     const float *mask; long ldmask;
+    int act, mkind;                           // egp_gemm_desc.act_kind / mask_kind (0: `relu` / the gate mask > 0 decide, as ever)
     int ones_col;                             // B has a virtual column N of ones (its result: column N of the workspace)
     int k_per_split;                          // multiple of BK; gridDim.z splits
     float *ws; int ldws;                      // [splits][M][ldws] when there are k splits or a ones column; ldws = N + ones_col rounded up to 4
@@ -96,6 +100,19 @@ struct GemmArgs {
     int partial;                              // results go to the workspace (k splits and / or the ones column), reduced by k_gemm_reduce
     int grid_tiles, n_items, zs;              // k_gemm_ws: tile slots (the XCD order pads tiles_m to a multiple of 8), slots x k splits, k splits
 };
+
+// The epilogue's two element-wise steps with the kinds of egp_gemm_desc. `act` / `kind` are kernel arguments: the branches
+// are wave-uniform. v = product + bias; m = the mask operand's element.
+__device__ __forceinline__ float epi_act(float v, int act, float floor_v) {
+    if (act == 1) return egp_act_tanh(v);
+    if (act == 2) return egp_act_sigmoid(v);
+    return fmaxf(v, floor_v);
+}
+__device__ __forceinline__ float epi_gate(float x, float m, int kind) {
+    if (kind == 1) return x * egp_dact_tanh(m);
+    if (kind == 2) return x * egp_dact_sigmoid(m);
+    return m > 0.f ? x : 0.f;
+}
 
 // LDS image of an operand tile (R rows x 32 k, bf16): four k-panels of [R][8] (+ 64 bytes between panels), element
 // (row, k) at (k >> 3) * PANEL(R) + row * 8 + (k & 7). An MFMA fragment read (32 consecutive rows x 8 k per half-wave) is
@@ -378,43 +395,50 @@ __global__ __launch_bounds__(256, 2) void k_gemm_bf16x(GemmArgs g) {
     const float floor_v = g.relu ? 0.f : -__builtin_inff();
     float *dst = partial ? g.ws + (long)blockIdx.z * g.M * g.ldws : g.C;
     const long ldd = partial ? g.ldws : g.ldc;
+    // (KINDS: the tanh / sigmoid kinds of egp_gemm_desc, a body of its own behind one wave-uniform branch -- the relu / gate
+    //  body is the code it always was; the KINDS body has no separate interior form: one copy of tanhf / expf per element)
+    auto tile_out = [&](auto kinds_c) __attribute__((always_inline)) {
+        constexpr bool KINDS = decltype(kinds_c)::value;
 #pragma unroll
-    for (int i = 0; i < MI; ++i)
+        for (int i = 0; i < MI; ++i)
 #pragma unroll
-        for (int j = 0; j < NJ; ++j) {
-            const int col = n0 + wn * 64 + 32 * j + (lane & 31);
-            const int rbase = m0 + wm * WROWS + 32 * i + 4 * (lane >> 5);
-            const int colc = min(col, n_out - 1);
-            const float bv = (!partial && g.bias) ? g.bias[min(colc, g.N - 1)] : 0.f;
-            float keep[16];
-            if (!partial && g.mask) {
+            for (int j = 0; j < NJ; ++j) {
+                const int col = n0 + wn * 64 + 32 * j + (lane & 31);
+                const int rbase = m0 + wm * WROWS + 32 * i + 4 * (lane >> 5);
+                const int colc = min(col, n_out - 1);
+                const float bv = (!partial && g.bias) ? g.bias[min(colc, g.N - 1)] : 0.f;
+                float keep[16];
+                if (!partial && g.mask) {
 #pragma unroll
-                for (int r = 0; r < 16; ++r) {
-                    const int row = min(rbase + (r & 3) + 8 * (r >> 2), g.M - 1);
-                    keep[r] = g.mask[(long)row * g.ldmask + min(colc, g.N - 1)];
+                    for (int r = 0; r < 16; ++r) {
+                        const int row = min(rbase + (r & 3) + 8 * (r >> 2), g.M - 1);
+                        keep[r] = g.mask[(long)row * g.ldmask + min(colc, g.N - 1)];
+                    }
+                } else {
+#pragma unroll
+                    for (int r = 0; r < 16; ++r) keep[r] = 1.f;
                 }
-            } else {
+                if (!KINDS && interior) {
 #pragma unroll
-                for (int r = 0; r < 16; ++r) keep[r] = 1.f;
+                    for (int r = 0; r < 16; ++r) {
+                        const int row = rbase + (r & 3) + 8 * (r >> 2);
+                        float x = partial ? acc[i][j][r] : fmaxf(acc[i][j][r] + bv, floor_v);
+                        x = keep[r] > 0.f ? x : 0.f;
+                        dst[(long)row * ldd + col] = x;
+                    }
+                } else {
+#pragma unroll
+                    for (int r = 0; r < 16; ++r) {
+                        const int row = rbase + (r & 3) + 8 * (r >> 2);
+                        float x = partial ? acc[i][j][r] : (KINDS ? epi_act(acc[i][j][r] + bv, g.act, floor_v) : fmaxf(acc[i][j][r] + bv, floor_v));
+                        x = KINDS ? epi_gate(x, keep[r], g.mkind) : (keep[r] > 0.f ? x : 0.f);
+                        if (row < g.M && col < n_out) dst[(long)row * ldd + col] = x;
+                    }
+                }
             }
-            if (interior) {
-#pragma unroll
-                for (int r = 0; r < 16; ++r) {
-                    const int row = rbase + (r & 3) + 8 * (r >> 2);
-                    float x = partial ? acc[i][j][r] : fmaxf(acc[i][j][r] + bv, floor_v);
-                    x = keep[r] > 0.f ? x : 0.f;
-                    dst[(long)row * ldd + col] = x;
-                }
-            } else {
-#pragma unroll
-                for (int r = 0; r < 16; ++r) {
-                    const int row = rbase + (r & 3) + 8 * (r >> 2);
-                    float x = partial ? acc[i][j][r] : fmaxf(acc[i][j][r] + bv, floor_v);
-                    x = keep[r] > 0.f ? x : 0.f;
-                    if (row < g.M && col < n_out) dst[(long)row * ldd + col] = x;
-                }
-            }
-        }
+    };
+    if (g.act | g.mkind) tile_out(std::true_type{});
+    else tile_out(std::false_type{});
     EGP_TR(21);
 }
 
@@ -950,8 +974,47 @@ __global__ __launch_bounds__(512) void k_gemm_ws(GemmArgs g) {
             __builtin_amdgcn_wave_barrier();
         }
     };
+    // The tanh / sigmoid kinds of egp_gemm_desc (act_kind / mask_kind; never a split-K launch) take an epilogue of their own
+    // behind one wave-uniform branch, so the bodies above stay what they were. Same patch, same addresses and clamps; the row
+    // loop is not unrolled (the values come from the patch, not from named registers: one copy of tanhf / expf per element of
+    // the float4 instead of 32), a row's mask and scatter index are loaded when its turn comes.
+    auto epilogue_kinds = [&]() __attribute__((always_inline)) {
+        const int col = cur.n0 + wn * 64 + 4 * (lane & 15);
+        const int colc = min(col, ncols - 4);
+        const bool col_ok = col < ncols;
+        const int row0 = cur.m0 + wm * WROWS + (lane >> 4);
+        f32x4u bv = {0.f, 0.f, 0.f, 0.f};
+        if (g.bias) bv = *(const f32x4u *)(g.bias + colc);
+#pragma unroll
+        for (int i = 0; i < MI; ++i) {
+#pragma unroll
+            for (int j = 0; j < NJ; ++j)
+#pragma unroll
+                for (int rq = 0; rq < 4; ++rq)
+                    *(float4 *)(patch + (lane & 31) * EP_LD + 32 * j + 8 * rq + 4 * (lane >> 5)) =
+                        make_float4(acc[i][j][4 * rq], acc[i][j][4 * rq + 1], acc[i][j][4 * rq + 2], acc[i][j][4 * rq + 3]);
+            __builtin_amdgcn_wave_barrier();
+#pragma unroll 1
+            for (int it = 0; it < 8; ++it) {
+                const int row = row0 + 32 * i + 4 * it, rowc = min(row, g.M - 1);
+                const float4 p4 = *(const float4 *)(patch + ((lane >> 4) + 4 * it) * EP_LD + 4 * (lane & 15));
+                f32x4u x = {p4.x, p4.y, p4.z, p4.w};
+#pragma unroll
+                for (int e = 0; e < 4; ++e) x[e] = epi_act(x[e] + bv[e], g.act, floor_v);
+                if (g.mask) {
+                    const f32x4u keep = *(const f32x4u *)(g.mask + (long)rowc * g.ldmask + colc);
+#pragma unroll
+                    for (int e = 0; e < 4; ++e) x[e] = epi_gate(x[e], keep[e], g.mkind);
+                }
+                const long drow = (FUSED && g.c_rows) ? (long)g.c_rows[rowc] : (long)row;
+                if (row < g.M && col_ok) *(f32x4u *)(g.C + drow * ldd + col) = x;
+            }
+            __builtin_amdgcn_wave_barrier();
+        }
+    };
     auto epilogue = [&]() __attribute__((always_inline)) {
         if (partial) epilogue_body(std::true_type{}, std::false_type{});
+        else if (g.act | g.mkind) epilogue_kinds();
         else if (g.mask) epilogue_body(std::false_type{}, std::true_type{});
         else epilogue_body(std::false_type{}, std::false_type{});
     };
@@ -990,8 +1053,8 @@ __global__ __launch_bounds__(256) void k_gemv_rows(GemmArgs g) {         // N ==
 #pragma unroll
         for (int off = 32; off > 0; off >>= 1) acc += __shfl_down(acc, off, 64);
         if (lane == 0) {
-            float x = fmaxf(acc + (g.bias ? g.bias[0] : 0.f), floor_v);
-            if (g.mask && !(g.mask[m * g.ldmask] > 0.f)) x = 0.f;
+            float x = epi_act(acc + (g.bias ? g.bias[0] : 0.f), g.act, floor_v);
+            if (g.mask) x = epi_gate(x, g.mask[m * g.ldmask], g.mkind);
             g.C[m * g.ldc] = x;
         }
     }
@@ -1004,8 +1067,8 @@ __global__ __launch_bounds__(256) void k_rank1(GemmArgs g) {             // K ==
     for (long id = (long)blockIdx.x * 256 + threadIdx.x; id < total; id += (long)gridDim.x * 256) {
         const long m = id / g.N;
         const int n = (int)(id - m * g.N);
-        float x = fmaxf(fmaf(g.A[m * as], g.B[n * bs], g.bias ? g.bias[n] : 0.f), floor_v);
-        if (g.mask && !(g.mask[m * g.ldmask + n] > 0.f)) x = 0.f;
+        float x = epi_act(fmaf(g.A[m * as], g.B[n * bs], g.bias ? g.bias[n] : 0.f), g.act, floor_v);
+        if (g.mask) x = epi_gate(x, g.mask[m * g.ldmask + n], g.mkind);
         g.C[m * g.ldc + n] = x;
     }
 }
@@ -1190,7 +1253,11 @@ int egp_gemm_f32(const egp_gemm_desc *d, void *stream) {
     const int splits = d->splits < 1 ? 1 : d->splits;
     const bool partial = splits > 1 || ones;
     EGP_REQUIRE(!partial || d->workspace, "split-K / bias-gradient launches need a workspace (egp_gemm_workspace_floats)");
-    EGP_REQUIRE(!partial || (!d->bias && !d->relu && !d->mask), "no epilogue on split-K launches");
+    EGP_REQUIRE(d->act_kind >= 0 && d->act_kind <= 2, "act_kind must be 0 (the relu field decides), 1 (tanh) or 2 (sigmoid)");
+    EGP_REQUIRE(d->mask_kind >= 0 && d->mask_kind <= 2, "mask_kind must be 0 (mask > 0), 1 (1 - mask^2) or 2 (mask (1 - mask))");
+    EGP_REQUIRE(!(d->relu && d->act_kind), "relu and act_kind name two activations: set one");
+    EGP_REQUIRE(!d->mask_kind || d->mask, "mask_kind needs a mask");
+    EGP_REQUIRE(!partial || (!d->bias && !d->relu && !d->mask && !d->act_kind && !d->mask_kind), "no epilogue on split-K launches");
     EGP_REQUIRE(!d->accumulate || partial, "accumulate goes with split-K / bias-gradient launches only (a plain product would overwrite C)");
     EGP_REQUIRE(!ones || !d->b_kcontig, "the ones column (bias gradient) goes with B given as [k][n]");
     // (Round 3, measured and not kept: launching the column remainder of N = 300 as a 64-column-tile product of its own
@@ -1203,6 +1270,7 @@ int egp_gemm_f32(const egp_gemm_desc *d, void *stream) {
     g.B = d->B; g.ldb = d->ldb; g.b_kc = d->b_kcontig;
     g.C = d->C; g.ldc = d->ldc;
     g.bias = d->bias; g.relu = d->relu; g.mask = d->mask; g.ldmask = d->ldmask;
+    g.act = d->act_kind; g.mkind = d->mask_kind;
     g.ones_col = ones; g.ws = d->workspace; g.ldws = (d->N + ones + 3) & ~3; g.partial = partial ? 1 : 0;
     g.a_rows = (const long long *)d->a_rows; g.A2 = d->A2; g.lda2 = d->lda2; g.a_split = d->a_split;
     g.b_krows = (const long long *)d->b_krows; g.B2 = d->B2; g.ldb2 = d->ldb2; g.b_split = d->b_split;

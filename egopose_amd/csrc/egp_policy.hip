@@ -28,6 +28,7 @@
 
 #include "egp_internal.hpp"
 #include "egp_filter_dev.hpp"
+#include "egp_act_dev.hpp"
 
 namespace {
 
@@ -94,8 +95,8 @@ struct PolLayers {
 
 __device__ __forceinline__ float pol_act(float v, int kind) {
     if (kind == 1) return fmaxf(v, 0.0f);                 // relu
-    if (kind == 2) return 1.0f / (1.0f + expf(-v));       // sigmoid
-    return tanhf(v);                                      // tanh
+    if (kind == 2) return egp_act_sigmoid(v);             // sigmoid
+    return egp_act_tanh(v);                               // tanh  (egp_act_dev.hpp: the formulas the update's epilogues use)
 }
 
 // nn.Linear weight W[out][in] (row stride ldw) -> packed[(g * nkq + kq) * 64 + lane][kk] = W[64 g + lane][4 kq + kk], zero outside

@@ -1,12 +1,14 @@
 """float32 matrix products of the PPO update through `egp_gemm_f32` (csrc/egp_gemm.hip): bf16 matrix cores with split
-operands (every float32 value as a sum of bf16 pieces, float32-class products), bias / ReLU / dReLU fused into
-the epilogues, deterministic split-K weight gradients that also return the bias gradient.
+operands (every float32 value as a sum of bf16 pieces, float32-class products), bias / activation / activation derivative
+(relu, tanh, sigmoid: the three of models/mlp.py:12-17) fused into the epilogues, deterministic split-K weight gradients that
+also return the bias gradient.
 
-  linear_fwd(x, W, b, relu)          y = x W^T + b        (nn.Linear of models/mlp.py:22-25, core/policy_gaussian.py:19-24)
-  linear_dgrad(dy, W, mask)          dx = (dy W) * (mask > 0)
+  linear_fwd(x, W, b, relu | act)    y = act(x W^T + b)   (nn.Linear of models/mlp.py:22-25, core/policy_gaussian.py:19-24)
+  linear_dgrad(dy, W, mask, act)     dx = (dy W) * act'(mask): mask > 0 for relu, 1 - mask^2 for tanh, mask (1 - mask) for sigmoid
   linear_wgrad(dy, x)                dW = dy^T x, db = sum_rows dy
   mlp_head(x, hidden_layers, head)   the reference's `head(MLP(x))` as ONE autograd node: activations saved once, every
-                                     ReLU derivative applied inside the producing data-gradient product
+                                     activation derivative applied inside the producing data-gradient product (from the
+                                     saved OUTPUT of the layer: no pre-activation is kept for tanh / sigmoid either)
 
 `EGP_GEMM=torch` keeps every product on the library path (rocBLAS / hipBLASLt through torch); `EGP_GEMM_TERMS` picks the
 operand split: 6 (default: three bf16 pieces, float32-class products), 3 (two pieces, ~16 mantissa bits) or 1 (plain bf16).
@@ -96,14 +98,35 @@ def _index(t, name):
     return t
 
 
+ACT_KIND = {"tanh": 1, "sigmoid": 2}           # egp_gemm_desc.act_kind / mask_kind (0: the `relu` field / the gate mask > 0)
+
+
+def _kind(act, what):
+    """An activation (None, "relu", "tanh", "sigmoid", or torch.relu / torch.tanh / torch.sigmoid) as ("relu" | "tanh" | "sigmoid" | None)."""
+    if act is None:
+        return None
+    for name, fn in (("relu", torch.relu), ("tanh", torch.tanh), ("sigmoid", torch.sigmoid)):
+        if act == name or act is fn:
+            return name
+    raise ValueError("%s must be None, relu, tanh or sigmoid, got %r" % (what, act))
+
+
 def gemm(A, B, a_kcontig=True, b_kcontig=True, bias=None, relu=False, mask=None, terms=None, splits=1, want_bias_grad=False,
-         out=None, bias_grad_out=None, accumulate=False, a_rows=None, a2=None, b_krows=None, b2=None, c_rows=None, a_krows=None):
+         out=None, bias_grad_out=None, accumulate=False, a_rows=None, a2=None, b_krows=None, b2=None, c_rows=None, a_krows=None,
+         act=None, mask_kind=None):
     """C = A B with the operand forms of include/egopose_hip.h (`egp_gemm_desc`). A: (M, K) if a_kcontig else (K, M);
     B: (N, K) if b_kcontig else (K, N). Returns C, or (C, bias_grad) with want_bias_grad.
     Fused gather / scatter (three-piece products only): `a_rows` (int64, M entries) -- operand row m is A[a_rows[m]], and with
     `a2` (M, K2) its columns continue with a2[m] (K = A.shape[1] + K2); `b_krows` / `b2` the same for B given as (K, N) along
     k and n; `c_rows` -- result row m goes to out[c_rows[m]] (`out` required, rows nobody writes keep their content);
-    `a_krows` -- A given as (K, M): k-row k is A[a_krows[k]] (with `b_krows`: a weight gradient over a subset of the rows)."""
+    `a_krows` -- A given as (K, M): k-row k is A[a_krows[k]] (with `b_krows`: a weight gradient over a subset of the rows).
+    Epilogue: + bias, then `relu=True` or `act` ("relu" / "tanh" / "sigmoid" or the torch function), then the mask: the gate
+    mask > 0, or with `mask_kind` "tanh" / "sigmoid" the factor 1 - mask^2 / mask (1 - mask) ("relu" = the gate)."""
+    act, mask_kind = _kind(act, "act"), _kind(mask_kind, "mask_kind")
+    if relu and act not in (None, "relu"):
+        raise ValueError("relu=True and act=%r name two activations" % act)
+    if mask_kind is not None and mask is None:
+        raise ValueError("mask_kind needs a mask")
     A, B = _mat(A, "A"), _mat(B, "B")
     if accumulate and not (splits > 1 or want_bias_grad):
         raise ValueError("accumulate goes with splits > 1 or want_bias_grad (a plain product overwrites `out`)")
@@ -161,7 +184,8 @@ def gemm(A, B, a_kcontig=True, b_kcontig=True, bias=None, relu=False, mask=None,
     d.B, d.ldb, d.b_kcontig = B.data_ptr(), _ld(B), 1 if b_kcontig else 0
     d.C, d.ldc = out.data_ptr(), _ld(out)
     d.bias = bias.data_ptr() if bias is not None else None
-    d.relu = 1 if relu else 0
+    d.relu = 1 if relu or act == "relu" else 0
+    d.act_kind, d.mask_kind = ACT_KIND.get(act, 0), ACT_KIND.get(mask_kind, 0)
     if mask is not None:
         _mat(mask, "mask")
         d.mask, d.ldmask = mask.data_ptr(), _ld(mask)
@@ -179,14 +203,15 @@ def gemm(A, B, a_kcontig=True, b_kcontig=True, bias=None, relu=False, mask=None,
     return (out, bg) if want_bias_grad else out
 
 
-def linear_fwd(x, W, b=None, relu=False, terms=None):
-    return gemm(x, W, True, True, bias=b, relu=relu, terms=terms)
+def linear_fwd(x, W, b=None, relu=False, terms=None, act=None):
+    return gemm(x, W, True, True, bias=b, relu=relu, terms=terms, act=act)
 
 
-def linear_dgrad(dy, W, mask=None, n_cols=None, terms=None):
-    """dx[:, :n_cols] = (dy W[:, :n_cols]) * (mask > 0)."""
+def linear_dgrad(dy, W, mask=None, n_cols=None, terms=None, act=None):
+    """dx[:, :n_cols] = (dy W[:, :n_cols]) * act'(mask), `mask` the output of the `act` layer: mask > 0 (relu, the default),
+    1 - mask^2 (tanh), mask (1 - mask) (sigmoid)."""
     Wv = W if n_cols is None else W[:, :n_cols]
-    return gemm(dy, Wv, True, False, mask=mask, terms=terms)
+    return gemm(dy, Wv, True, False, mask=mask, terms=terms, mask_kind=act if mask is not None else None)
 
 
 def linear_wgrad(dy, x, want_bias=True, terms=None):
@@ -198,18 +223,18 @@ def linear_wgrad(dy, x, want_bias=True, terms=None):
 
 
 class MlpHead(torch.autograd.Function):
-    """out = head(relu-MLP(x)): apply(x, n_grad_cols, W1, b1, ..., Wh, bh). Gradient w.r.t. x only for its first
-    n_grad_cols columns (the video context; the state columns of the reference's concatenated input need none),
-    zeros elsewhere."""
+    """out = head(MLP(x)): apply(x, n_grad_cols, act, W1, b1, ..., Wh, bh), `act` the hidden layers' activation ("relu",
+    "tanh" or "sigmoid"). Gradient w.r.t. x only for its first n_grad_cols columns (the video context; the state columns of
+    the reference's concatenated input need none), zeros elsewhere."""
 
     @staticmethod
-    def forward(ctx, x, n_grad_cols, *params):
+    def forward(ctx, x, n_grad_cols, act, *params):
         Ws, bs = params[0::2], params[1::2]
         hs = [x.contiguous()]
         for i, (W, b) in enumerate(zip(Ws, bs)):
-            hs.append(linear_fwd(hs[-1], W.contiguous(), b, relu=i < len(Ws) - 1))
+            hs.append(linear_fwd(hs[-1], W.contiguous(), b, act=act if i < len(Ws) - 1 else None))
         ctx.save_for_backward(*hs[:-1], *Ws)
-        ctx.n_layers, ctx.n_grad_cols = len(Ws), int(n_grad_cols)
+        ctx.n_layers, ctx.n_grad_cols, ctx.act = len(Ws), int(n_grad_cols), act
         return hs[-1]
 
     @staticmethod
@@ -220,12 +245,12 @@ class MlpHead(torch.autograd.Function):
         grads = [None] * (2 * nl)
         dx = None
         for i in range(nl - 1, -1, -1):
-            need_w, need_b = ctx.needs_input_grad[2 + 2 * i], ctx.needs_input_grad[3 + 2 * i]
+            need_w, need_b = ctx.needs_input_grad[3 + 2 * i], ctx.needs_input_grad[4 + 2 * i]
             if need_w or need_b:
                 dW, db = linear_wgrad(dz, hs[i], want_bias=True)
                 grads[2 * i], grads[2 * i + 1] = (dW if need_w else None), (db if need_b else None)
             if i > 0:
-                dz = linear_dgrad(dz, Ws[i].contiguous(), mask=hs[i])         # hs[i] = relu output feeding layer i
+                dz = linear_dgrad(dz, Ws[i].contiguous(), mask=hs[i], act=ctx.act)         # hs[i] = activation output feeding layer i
             elif ctx.needs_input_grad[0]:
                 nc = ctx.n_grad_cols
                 W0 = Ws[0].contiguous()
@@ -234,23 +259,24 @@ class MlpHead(torch.autograd.Function):
                 else:
                     dx = torch.zeros(dz.shape[0], W0.shape[1], dtype=dz.dtype, device=dz.device)
                     gemm(dz, W0[:, :nc], True, False, out=dx[:, :nc])
-        return (dx, None, *grads)
+        return (dx, None, None, *grads)
 
 
 def mlp_head_available(x, layers, head, activation):
     if isinstance(x, GatheredInput):
         x = x.x
-    if not (enabled() and x.is_cuda and x.dtype == torch.float32 and x.dim() == 2 and activation is torch.relu):
+    if not (enabled() and x.is_cuda and x.dtype == torch.float32 and x.dim() == 2
+            and any(activation is f for f in (torch.relu, torch.tanh, torch.sigmoid))):
         return False
     return all(l.weight.dtype == torch.float32 and l.bias is not None and l.weight.is_cuda for l in list(layers) + [head])
 
 
-def mlp_head(x, layers, head, n_grad_cols=None):
+def mlp_head(x, layers, head, n_grad_cols=None, activation=torch.relu):
     params = []
     for l in list(layers) + [head]:
         params += [l.weight, l.bias]
     nc = x.shape[1] if n_grad_cols is None else int(n_grad_cols)
-    return MlpHead.apply(x, nc, *params)
+    return MlpHead.apply(x, nc, _kind(activation, "activation"), *params)
 
 
 class GatheredInput:
@@ -293,54 +319,55 @@ def fused_rows_available():
 
 
 class GatherMlpHead(torch.autograd.Function):
-    """out = head(relu-MLP([ctx2d[idx] | x])) without forming the concatenated input: apply(ctx2d, idx, x, W1, b1, ..., Wh, bh).
+    """out = head(MLP([ctx2d[idx] | x])) without forming the concatenated input: apply(ctx2d, idx, x, act, W1, b1, ..., Wh, bh),
+    `act` the hidden layers' activation ("relu", "tanh" or "sigmoid").
     The first layer's product gathers the context rows and appends the state columns on its way into LDS
     (`egp_gemm_desc.a_rows / A2`), its weight gradient does the same along k (`b_krows / B2`), and its data gradient writes the
     context rows it belongs to (`c_rows`; idx must not repeat). Gradient w.r.t. ctx2d only, as GatherConcat + MlpHead."""
 
     @staticmethod
-    def forward(ctx, ctx2d, idx, x, *params):
+    def forward(ctx, ctx2d, idx, x, act, *params):
         Ws, bs = params[0::2], params[1::2]
         ctx2d, x = ctx2d.contiguous(), (x if x.stride(1) == 1 else x.contiguous())
-        h = gemm(ctx2d, Ws[0].contiguous(), True, True, bias=bs[0], relu=len(Ws) > 1, a_rows=idx, a2=x)
+        h = gemm(ctx2d, Ws[0].contiguous(), True, True, bias=bs[0], act=act if len(Ws) > 1 else None, a_rows=idx, a2=x)
         hs = [h]
         for i in range(1, len(Ws)):
-            hs.append(linear_fwd(hs[-1], Ws[i].contiguous(), bs[i], relu=i < len(Ws) - 1))
+            hs.append(linear_fwd(hs[-1], Ws[i].contiguous(), bs[i], act=act if i < len(Ws) - 1 else None))
         ctx.save_for_backward(ctx2d, idx, x, *hs[:-1], *Ws)
-        ctx.n_layers = len(Ws)
+        ctx.n_layers, ctx.act = len(Ws), act
         return hs[-1]
 
     @staticmethod
     def backward(ctx, dout):
         nl = ctx.n_layers
         ctx2d, idx, x = ctx.saved_tensors[:3]
-        hs, Ws = ctx.saved_tensors[3:3 + nl - 1], ctx.saved_tensors[3 + nl - 1:]        # hs[i - 1] = relu output feeding layer i
+        hs, Ws = ctx.saved_tensors[3:3 + nl - 1], ctx.saved_tensors[3 + nl - 1:]        # hs[i - 1] = activation output feeding layer i
         dz = dout.contiguous()
         grads = [None] * (2 * nl)
         for i in range(nl - 1, 0, -1):
-            need_w, need_b = ctx.needs_input_grad[3 + 2 * i], ctx.needs_input_grad[4 + 2 * i]
+            need_w, need_b = ctx.needs_input_grad[4 + 2 * i], ctx.needs_input_grad[5 + 2 * i]
             if need_w or need_b:
                 dW, db = linear_wgrad(dz, hs[i - 1], want_bias=True)
                 grads[2 * i], grads[2 * i + 1] = (dW if need_w else None), (db if need_b else None)
-            dz = linear_dgrad(dz, Ws[i].contiguous(), mask=hs[i - 1])
+            dz = linear_dgrad(dz, Ws[i].contiguous(), mask=hs[i - 1], act=ctx.act)
         H, S = ctx2d.shape[1], x.shape[1]
-        if ctx.needs_input_grad[3] or ctx.needs_input_grad[4]:
+        if ctx.needs_input_grad[4] or ctx.needs_input_grad[5]:
             n = dz.shape[0]
             dW, db = gemm(dz, ctx2d, False, False, splits=pick_splits(dz.shape[1], H + S + 1, n), want_bias_grad=True, b_krows=idx, b2=x)
-            grads[0], grads[1] = (dW if ctx.needs_input_grad[3] else None), (db if ctx.needs_input_grad[4] else None)
+            grads[0], grads[1] = (dW if ctx.needs_input_grad[4] else None), (db if ctx.needs_input_grad[5] else None)
         dctx = None
         if ctx.needs_input_grad[0]:
             dctx = torch.zeros_like(ctx2d)
             gemm(dz, Ws[0][:, :H], True, False, out=dctx, c_rows=idx)
-        return (dctx, None, None, *grads)
+        return (dctx, None, None, None, *grads)
 
 
-def gather_mlp_head(gi, layers, head):
-    """head(relu-MLP([ctx2d[idx] | x])), one launch per layer and direction (GatherMlpHead)."""
+def gather_mlp_head(gi, layers, head, activation=torch.relu):
+    """head(MLP([ctx2d[idx] | x])), one launch per layer and direction (GatherMlpHead)."""
     params = []
     for l in list(layers) + [head]:
         params += [l.weight, l.bias]
-    return GatherMlpHead.apply(gi.ctx2d, gi.idx, gi.x, *params)
+    return GatherMlpHead.apply(gi.ctx2d, gi.idx, gi.x, _kind(activation, "activation"), *params)
 
 
 class GatherConcat(torch.autograd.Function):

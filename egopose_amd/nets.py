@@ -163,9 +163,9 @@ class PolicyGaussian(Policy):
             # video-context columns of that input carry a gradient -- any other input gets the full gradient
             # (set by the agent): only the leading video-context columns of the input carry a gradient
             if isinstance(x, _gemm.GatheredInput):      # [context | state] never formed: the first layer gathers it itself
-                mean = _gemm.gather_mlp_head(x, self.net.affine_layers, self.action_mean)
+                mean = _gemm.gather_mlp_head(x, self.net.affine_layers, self.action_mean, self.net.activation)
             else:
-                mean = _gemm.mlp_head(x, self.net.affine_layers, self.action_mean, getattr(x, "_egp_ctx_cols", None))
+                mean = _gemm.mlp_head(x, self.net.affine_layers, self.action_mean, getattr(x, "_egp_ctx_cols", None), self.net.activation)
         else:
             if isinstance(x, _gemm.GatheredInput):
                 x = x.materialize()
@@ -202,8 +202,8 @@ class Value(nn.Module):
     def forward(self, x):
         if _gemm.mlp_head_available(x, getattr(self.net, "affine_layers", ()), self.value_head, getattr(self.net, "activation", None)):
             if isinstance(x, _gemm.GatheredInput):
-                return _gemm.gather_mlp_head(x, self.net.affine_layers, self.value_head)
-            return _gemm.mlp_head(x, self.net.affine_layers, self.value_head, getattr(x, "_egp_ctx_cols", None))
+                return _gemm.gather_mlp_head(x, self.net.affine_layers, self.value_head, self.net.activation)
+            return _gemm.mlp_head(x, self.net.affine_layers, self.value_head, getattr(x, "_egp_ctx_cols", None), self.net.activation)
         if isinstance(x, _gemm.GatheredInput):
             x = x.materialize()
         x, n = bucket_rows(x)
@@ -227,8 +227,8 @@ class Discriminator(nn.Module):
     def logits(self, x):
         if _gemm.mlp_head_available(x, getattr(self.net, "affine_layers", ()), self.logic, getattr(self.net, "activation", None)):
             if isinstance(x, _gemm.GatheredInput):
-                return _gemm.gather_mlp_head(x, self.net.affine_layers, self.logic)
-            return _gemm.mlp_head(x, self.net.affine_layers, self.logic, getattr(x, "_egp_ctx_cols", None))
+                return _gemm.gather_mlp_head(x, self.net.affine_layers, self.logic, self.net.activation)
+            return _gemm.mlp_head(x, self.net.affine_layers, self.logic, getattr(x, "_egp_ctx_cols", None), self.net.activation)
         if isinstance(x, _gemm.GatheredInput):
             x = x.materialize()
         x, n = bucket_rows(x)

@@ -258,7 +258,7 @@ int egp_gae_standardize_f32(float *adv, int32_t n, const double *stats, void *st
  * float32 matrix products of the PPO update on the bf16 matrix cores with split operands (csrc/egp_gemm.hip): replaces
  * the rocBLAS / hipBLASLt calls behind the reference's nn.Linear layers (models/mlp.py:22-25, core/policy_gaussian.py:19-24,
  * core/critic.py:15-18) and behind the LSTM input projection / weight gradients (models/rnn.py:45-61 under autograd).
- *   C[M][N] = A[M][K] B[K][N]  (+ bias[n]) (ReLU) (* (mask[m][n] > 0))
+ *   C[M][N] = A[M][K] B[K][N]  (+ bias[n]) (ReLU | tanh | sigmoid) (* (mask[m][n] > 0) | * act'(mask[m][n]))
  *   a_kcontig: A is given as [m][k] (element (m, k) at A[m*lda + k]); otherwise as [k][m] (A[k*lda + m])
  *   b_kcontig: B is given as [n][k] (B[n*ldb + k], e.g. an nn.Linear weight in a forward pass); otherwise [k][n]
  *   terms = 3: every operand is split x = hi + lo (two bf16) and a product is hi*hi + hi*lo + lo*hi in float32
@@ -296,6 +296,14 @@ typedef struct egp_gemm_desc {
     const int64_t *b_krows; const float *B2; int64_t ldb2; int32_t b_split; int64_t b_src_rows;
     const int64_t *c_rows;
     const int64_t *a_krows;
+    /* Activations other than ReLU, and their derivatives in a data gradient. Zero (a zero-filled tail) = the fields above decide.
+     *   act_kind:  0 `relu` decides, 1 tanh, 2 sigmoid -- applied after the bias, where ReLU is.
+     *   mask_kind: 0 the gate mask > 0, 1 the result times 1 - m^2, 2 times m (1 - m), m = mask[r][c]: the derivative of tanh /
+     *              sigmoid from the layer's OUTPUT, so `mask` is the same saved activation that a ReLU layer passes.
+     * (Not the codes of egp_policy_desc.activation, where 0 is tanh: here zero has to mean "as before".) Refused with
+     * EGP_E_INVALID: relu != 0 together with act_kind != 0, a kind outside 0..2, mask_kind != 0 without mask, and either kind on a
+     * split-K / bias-gradient launch (no epilogue there). */
+    int32_t act_kind, mask_kind;
 } egp_gemm_desc;
 /* ------------------------------------------------------------------------------------ update: losses and the optimizer step
  * (csrc/egp_update.hip) The element-wise tail of a PPO epoch in two launches instead of ~45 small library kernels.
