@@ -888,7 +888,7 @@ class AgentVGAIL(AgentEgo):
         src_host = self._expert_src(v_metas, masks)         # (first: a slice that leaves its take is reported as such)
         self._init_discrim_context(masks, v_metas, _adopt)
         vs = self.cn.discrim_vs_net
-        if self._fused_discrim() and vs._gather_unique and vs._buckets is None and states.shape[0] > 0:
+        if self._fused_discrim() and vs._gather_unique and states.shape[0] > 0:
             return self._update_discriminator_fused(states, src_host)
         return self._update_discriminator_plain(states, masks, v_metas)
 

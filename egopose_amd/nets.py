@@ -13,13 +13,13 @@ otherwise a cell loop over pre-projected gates) instead of 2*T LSTMCell calls at
 """
 from __future__ import annotations
 
+import collections
 import math
+import os
 
 import numpy as np
 import torch
 import torch.nn as nn
-
-import os
 
 from . import dist as _dist
 from . import gemm as _gemm
@@ -28,11 +28,10 @@ from . import lstm as _hip_lstm
 from . import tcn as _tcn
 from .tcn import TemporalConvNet  # noqa: F401  (models/tcn.py: part of the nets' public surface)
 
-# Length buckets of the train-mode forward LSTM (1 = off: measured SLOWER on the MI355X -- the persistent LSTM kernel is
-# bound by its per-timestep latency, not by the batch, so four short launches in a row cost more than one long one; the
-# code path stays for throughput-bound shapes, a module attribute, no switch). Running the two directions on two HIP streams
-# was also tried: no gain in the update, and an intermittent stall next to the resident K1 streams -- removed.
-_FWD_BUCKETS = 1
+# Running the train-mode forward LSTM per length bucket was measured SLOWER on the MI355X -- the persistent sweep is bound by
+# its per-timestep latency, not by the batch, so several short launches cost more than one long one -- and the ragged sweeps
+# (lstm.ragged_order) replaced it. Running the two directions on two HIP streams was also tried: no gain in the update, and
+# an intermittent stall next to the resident K1 streams -- removed.
 _LSTM_IMPL = os.environ.get("EGP_LSTM", "hip")      # "torch" forces the MIOpen / cell-loop paths (A/B runs)
 
 _ACT = {"tanh": torch.tanh, "relu": torch.relu, "sigmoid": torch.sigmoid}
@@ -333,7 +332,123 @@ def _run_video_net(v_net, x):
     return v_net.forward_tm(x) if isinstance(v_net, _tcn.TemporalConvNet) else v_net(x)
 
 
-class VideoStateNet(nn.Module):
+_Episodes = collections.namedtuple("_Episodes", "ends starts lens max_len covered ep_of indices meta")
+
+
+def _segment_episodes(masks, v_metas):
+    """The flat batch cut into episodes at masks == 0 (models/video_state_net.py:40-51): per episode its last sample, its first
+    one and its length; `max_len`; per sample its episode `ep_of` and `indices` = episode * max_len + offset, its cell of an
+    (n_ep, max_len) grid -- the samples from `covered` on, behind the last episode end, keep their own number; `meta`, the
+    (take, start frame) row of every episode. One device-to-host sync, then one collective: the padded window length is a
+    batch-wide quantity in the reference (one process, one batch) and stays global when the batch is sharded over ranks."""
+    ends = torch.nonzero(masks == 0).flatten().cpu().numpy()
+    starts = np.concatenate(([0], ends[:-1] + 1))
+    lens = ends - starts + 1
+    max_len = _dist.global_max(int(lens.max()), masks.device)
+    ep_of = np.repeat(np.arange(len(ends)), lens)
+    covered = int(ends[-1]) + 1
+    idx = np.arange(masks.shape[0])
+    idx[:covered] = ep_of * max_len + (np.arange(covered) - np.repeat(starts, lens))
+    return _Episodes(ends, starts, lens, max_len, covered, ep_of, idx, np.asarray(v_metas)[ends])
+
+
+class _VideoFrontEnd(nn.Module):
+    """The host side that VideoStateNet and VideoForecastNet share: the feature table, the rows of its windows, the train-mode
+    batch cut into episodes with their windows gathered, the test-mode input. No parameters, buffers or submodules of its own.
+    A subclass states its window through `_extent`."""
+
+    # the part of a train-mode context both nets hold: the same for every net that sees the same batch through the same table
+    _SHARED_CONTEXT = ("indices", "gather_indices", "cnn_feat_ctx", "_ctx_key")
+
+    def __init__(self):
+        super().__init__()
+        self.mode = "test"
+        self.v_out = None
+        self.t = 0
+        for k in self._SHARED_CONTEXT:
+            setattr(self, k, None)
+        self._cnn_table = None          # optional (device table, take offsets) installed by the env
+        self._take_offset_host = self._take_len = None
+
+    def set_mode(self, mode):
+        self.mode = mode
+
+    def forward_v_net(self, x):
+        return _run_video_net(self.v_net, x)
+
+    def _to_params(self, x):
+        p = next(self.parameters())
+        return x.to(device=p.device, dtype=p.dtype)
+
+    def attach_feature_table(self, table, take_offset):
+        """Device-resident concatenation of all takes' features (+ row offsets) for gather-built contexts."""
+        host = np.asarray(take_offset, dtype=np.int64)
+        if self._cnn_table is not None and self._cnn_table[0] is table and np.array_equal(self._take_offset_host, host):
+            return                     # (same table as last time: no upload -- a copy from pageable memory blocks the host until the stream drains)
+        self._cnn_table = (table, torch.as_tensor(host, dtype=torch.long, device=table.device))
+        self._take_offset_host = host.copy()
+        self._take_len = _take_lengths(take_offset, table.shape[0])
+
+    def _table_on(self, device):
+        return self._cnn_table[0] if self._cnn_table is not None and self._cnn_table[0].device == device else None
+
+    def _same_table(self, other):
+        return (self._cnn_table is not None and other._cnn_table is not None
+                and self._cnn_table[0].data_ptr() == other._cnn_table[0].data_ptr()
+                and np.array_equal(self._take_offset_host, other._take_offset_host))
+
+    def _extent(self, length):
+        """(before, after): a window of `length` frames from `start` covers the table rows [start - before, start + after)."""
+        raise NotImplementedError
+
+    def check_windows(self, expert_ind, start_ind, length):
+        """Every window must lie inside its own take: the table is the concatenation of all takes, so a window that leaves
+        its take would silently read a neighbour's frames (the reference's numpy slice comes up short and raises on
+        assignment, models/video_state_net.py:52-55)."""
+        _check_windows(self._take_len, expert_ind, start_ind, *self._extent(length))
+
+    def window_features(self, expert_ind, start_ind, length):
+        """Gather the windows of the given takes -> (before + after, B, D) on device."""
+        table, off = self._cnn_table
+        before, after = self._extent(length)
+        base = off[expert_ind.long()] + start_ind.long() - before
+        rows = base.unsqueeze(0) + torch.arange(before + after, device=table.device).unsqueeze(1)
+        return table[rows]
+
+    def _train_windows(self, ep, cnn_feat, device, dtype, length, rows=None):
+        """`cnn_feat_ctx` and `_ctx_key` of the episodes `ep`: their windows of `length` as one (before + after, n_ep, D) block,
+        gathered from the feature table when it lives on `device`, else cut from the takes' arrays `cnn_feat` on the host;
+        with `rows`, on top of a zero block of that many rows. -> `meta` with the rows of the padding episodes."""
+        before, after = self._extent(length)
+        meta = ep.meta
+        if self._table_on(device) is not None:
+            # episode count rounded up to a bucket (gemm_tuning.py): the extra windows repeat episode 0, nothing
+            # gathers from them, so their gradient contribution is exactly zero
+            pad = _tuning.pad_to(len(meta), _tuning.EPISODE_BUCKET) if _tuning.enabled() and len(meta) >= 4 * _tuning.EPISODE_BUCKET else 0
+            if pad:
+                meta = np.concatenate((meta, np.repeat(meta[:1], pad, axis=0)), 0)
+            self.check_windows(meta[:, 0], meta[:, 1], length)
+            ctx = self.window_features(torch.as_tensor(meta[:, 0], device=device), torch.as_tensor(meta[:, 1], device=device), length).to(dtype)
+            if rows is not None:
+                win, ctx = ctx, ctx.new_zeros(rows, meta.shape[0], self.cnn_feat_dim)
+                ctx[:before + after] = win
+        else:
+            ctx = np.zeros((before + after if rows is None else rows, len(meta), self.cnn_feat_dim))
+            for e, (ei, si) in enumerate(meta):
+                ctx[:before + after, e, :] = cnn_feat[int(ei)][int(si) - before: int(si) + after]
+            ctx = torch.as_tensor(ctx, dtype=dtype, device=device)
+        self.cnn_feat_ctx = ctx
+        self._ctx_key = (int(ep.max_len), meta.shape[0], hash(meta.tobytes()))       # which windows cnn_feat_ctx holds
+        return meta
+
+
+def _same_windows(n, n0):
+    """Train-mode net `n` holds the very windows `n0` holds: same batch, same padding, same block."""
+    return (n.mode == "train" and n.cnn_feat_ctx is not None and n._ctx_key == n0._ctx_key
+            and n.cnn_feat_ctx.shape == n0.cnn_feat_ctx.shape and n.cnn_feat_ctx.dtype == n0.cnn_feat_ctx.dtype)
+
+
+class VideoStateNet(_VideoFrontEnd):
     """Temporal net over precomputed CNN features, concatenated in front of the state.
 
     test mode: ``initialize(window)`` with window (T+2m, D) for ONE episode, or (T+2m, B, D) for a batch of
@@ -346,57 +461,21 @@ class VideoStateNet(nn.Module):
 
     def __init__(self, cnn_feat_dim, v_hdim=128, v_margin=10, v_net_type="lstm", v_net_param=None, causal=False):
         super().__init__()
-        self.mode = "test"
         self.cnn_feat_dim, self.v_hdim, self.v_margin, self.v_net_type = cnn_feat_dim, v_hdim, v_margin, v_net_type
         self.v_net = _video_net(cnn_feat_dim, v_hdim, v_net_type, v_net_param, causal)
-        self.v_out = None
-        self.t = 0
-        self.indices = None
-        self.gather_indices = None
         self._gather_tm = None
         self._gather_unique = False
-        self.cnn_feat_ctx = None
-        self._buckets = None
-        self._v_ctx = None
-        self._ctx_key = None
-        self._cnn_table = None   # optional (device table, take offsets) installed by the env
         self._ragged = None      # (order, steps) of the train-mode windows for the grouped HIP sweeps
+        self._frames = None      # (table, first row of every window) when the input projection runs per frame of the table
+        self._v_ctx = None
 
-    def set_mode(self, mode):
-        self.mode = mode
-
-    def forward_v_net(self, x):
-        return _run_video_net(self.v_net, x)
-
-    def attach_feature_table(self, table, take_offset):
-        """Device-resident concatenation of all takes' features (+ row offsets) for gather-built contexts."""
-        host = np.asarray(take_offset, dtype=np.int64)
-        cur = getattr(self, "_cnn_table", None)
-        if cur is not None and cur[0] is table and np.array_equal(getattr(self, "_take_offset_host", None), host):
-            return                     # (same table as last time: no upload -- a copy from pageable memory blocks the host until the stream drains)
-        self._cnn_table = (table, torch.as_tensor(host, dtype=torch.long, device=table.device))
-        self._take_offset_host = host.copy()
-        self._take_len = _take_lengths(take_offset, table.shape[0])
-
-    def check_windows(self, expert_ind, start_ind, length):
-        """Rows [start - m, start + length + m) must lie inside their own take: the table is the concatenation of all
-        takes, so a window that leaves its take would silently read a neighbour's frames (the reference's numpy slice
-        comes up short and raises on assignment, models/video_state_net.py:52-55)."""
-        _check_windows(self._take_len, expert_ind, start_ind, self.v_margin, length + self.v_margin)
-
-    def window_features(self, expert_ind, start_ind, length):
-        """Gather windows [start-m, start+length+m) of the given takes -> (length+2m, B, D) on device."""
-        table, off = self._cnn_table
-        m = self.v_margin
-        base = off[expert_ind.long()] + start_ind.long() - m
-        rows = base.unsqueeze(0) + torch.arange(length + 2 * m, device=table.device).unsqueeze(1)
-        return table[rows]
+    def _extent(self, length):
+        return self.v_margin, length + self.v_margin          # rows [start - m, start + length + m)
 
     def initialize(self, x):
         m = self.v_margin
         if self.mode == "test":
-            p = next(self.parameters())
-            x = x.to(device=p.device, dtype=p.dtype)
+            x = self._to_params(x)
             single = x.dim() == 2
             out = self.forward_v_net(x.unsqueeze(1) if single else x)[m:-m]
             self.v_out = out.squeeze(1) if single else out
@@ -405,42 +484,18 @@ class VideoStateNet(nn.Module):
         masks, cnn_feat, v_metas = x
         device, dtype = masks.device, masks.dtype
         self._frames = None
-        ends = torch.nonzero(masks == 0).flatten().cpu().numpy()
-        n = masks.shape[0]
-        starts = np.concatenate(([0], ends[:-1] + 1))
-        lens = ends - starts + 1
-        # the padded window length is a batch-wide quantity in the reference (one process, one batch):
-        # keep it global when the batch is sharded over ranks
-        max_len = _dist.global_max(int(lens.max()), device)
-        idx = np.arange(n)
-        ep_of = np.repeat(np.arange(len(ends)), lens)
-        covered = int(ends[-1]) + 1
-        idx[:covered] = ep_of * max_len + (np.arange(covered) - np.repeat(starts, lens))
-        self.indices = idx
-        meta = np.asarray(v_metas)[ends]
-        if self._cnn_table is not None and self._cnn_table[0].device == device:
-            # episode count rounded up to a bucket (gemm_tuning.py): the extra windows repeat episode 0, nothing
-            # gathers from them, so their gradient contribution is exactly zero
-            pad = _tuning.pad_to(len(ends), _tuning.EPISODE_BUCKET) if _tuning.enabled() and len(ends) >= 4 * _tuning.EPISODE_BUCKET else 0
-            if pad:
-                meta = np.concatenate((meta, np.repeat(meta[:1], pad, axis=0)), 0)
-            self.check_windows(meta[:, 0], meta[:, 1], max_len)
-            e_ind = torch.as_tensor(meta[:, 0], device=device)
-            s_ind = torch.as_tensor(meta[:, 1], device=device)
-            self.cnn_feat_ctx = self.window_features(e_ind, s_ind, max_len).to(dtype)
-            # The windows are runs of consecutive rows of the feature table: window b starts at row base[b]. When the table is
-            # (much) smaller than the windows laid end to end -- the takes' frames are visited by many episodes -- the LSTMs'
-            # input projection is computed per frame of the table instead of per window row (lstm.LstmGroup, `frames`).
-            table = self._cnn_table[0]
-            n_rows = self.cnn_feat_ctx.shape[0] * self.cnn_feat_ctx.shape[1]
-            if table.dtype == dtype and table.is_contiguous() and 2 * table.shape[0] <= n_rows:
-                base = self._take_offset_host[meta[:, 0].astype(np.int64)] + meta[:, 1].astype(np.int64) - m
-                self._frames = (table, torch.as_tensor(base.astype(np.int32), device=device))
-        else:
-            ctx = np.zeros((max_len + 2 * m, len(ends), self.cnn_feat_dim))
-            for e, (ei, si) in enumerate(meta):
-                ctx[:, e, :] = cnn_feat[int(ei)][int(si) - m: int(si) + max_len + m]
-            self.cnn_feat_ctx = torch.as_tensor(ctx, dtype=dtype, device=device)
+        ep = _segment_episodes(masks, v_metas)
+        self.indices = idx = ep.indices
+        max_len = ep.max_len
+        meta = self._train_windows(ep, cnn_feat, device, dtype, max_len)
+        # The windows are runs of consecutive rows of the feature table: window b starts at row base[b]. When the table is
+        # (much) smaller than the windows laid end to end -- the takes' frames are visited by many episodes -- the LSTMs'
+        # input projection is computed per frame of the table instead of per window row (lstm.LstmGroup, `frames`).
+        table = self._table_on(device)
+        n_rows = self.cnn_feat_ctx.shape[0] * self.cnn_feat_ctx.shape[1]
+        if table is not None and table.dtype == dtype and table.is_contiguous() and 2 * table.shape[0] <= n_rows:
+            base = self._take_offset_host[meta[:, 0].astype(np.int64)] + meta[:, 1].astype(np.int64) - m
+            self._frames = (table, torch.as_tensor(base.astype(np.int32), device=device))
         self.gather_indices = torch.as_tensor(idx, dtype=torch.long, device=device)
         # the same rows addressed in the net's own (time, episode) order: forward() gathers straight from the LSTM output
         # instead of slicing off the margins, transposing and copying it first
@@ -449,32 +504,15 @@ class VideoStateNet(nn.Module):
         # the backward pass's scatter relies on distinct rows. Samples inside episodes have them by construction (episode e,
         # offset < len_e <= max_len -> a distinct (frame, episode) cell); only a batch with samples after its last episode
         # end (idx = the sample's own number there) needs the look
-        self._gather_unique = covered == n or np.unique(tm).size == tm.size
-        self._ctx_key = (int(max_len), meta.shape[0], hash(meta.tobytes()))       # which windows cnn_feat_ctx holds
+        self._gather_unique = ep.covered == masks.shape[0] or np.unique(tm).size == tm.size
         # Ragged sweeps (lstm.ragged_order): the forward direction's output at frame t depends on frames <= t only and only
         # frames [m, m + len_e) of an episode are ever gathered, so it stops after m + len_e steps (workgroups of sequences
         # sorted by length); the backward direction starts at the end of the padded window and runs it all, as in the
         # reference. Windows added to fill an episode bucket need no step at all.
         steps = np.zeros(self.cnn_feat_ctx.shape[1], np.int64)
-        steps[:len(lens)] = lens + m
+        steps[:len(ep.lens)] = ep.lens + m
         lstm_ctx = self.cnn_feat_ctx.is_cuda and isinstance(self.v_net, RNN)         # (a TCN has no sweeps to cut short)
         self._ragged = _hip_lstm.ragged_order(steps, device, T=self.cnn_feat_ctx.shape[0]) if lstm_ctx else None
-        # Length buckets for the forward direction: its output at frame t only depends on frames <= t and only frames
-        # [m, m + len_e) of an episode are ever gathered, so episodes sorted by length let the forward LSTM stop early
-        # (the backward direction starts at the end of the padded window and must run it all, as in the reference).
-        self._buckets = None
-        n_ep = len(ends)
-        if _FWD_BUCKETS > 1 and n_ep >= 4 * _FWD_BUCKETS and self.v_net_type == "lstm":
-            order = np.argsort(-lens, kind="stable")
-            rank = np.empty(n_ep, np.int64)
-            rank[order] = np.arange(n_ep)
-            idx_s = np.arange(n)
-            idx_s[:covered] = rank[ep_of] * max_len + (np.arange(covered) - np.repeat(starts, lens))
-            self._gather_sorted = torch.as_tensor(idx_s, dtype=torch.long, device=device)
-            self._ctx_sorted = self.cnn_feat_ctx.index_select(1, torch.as_tensor(order, device=device))
-            cuts = [n_ep * k // _FWD_BUCKETS for k in range(_FWD_BUCKETS + 1)]
-            lens_sorted = lens[order]
-            self._buckets = [(cuts[k], cuts[k + 1], int(m + lens_sorted[cuts[k]])) for k in range(_FWD_BUCKETS)]
 
     @torch.no_grad()
     def online_contexts(self, x):
@@ -494,8 +532,7 @@ class VideoStateNet(nn.Module):
         if self.mode != "test":
             raise RuntimeError("online_contexts is a test-mode (evaluation) call")
         m = self.v_margin
-        p = next(self.parameters())
-        x = x.to(device=p.device, dtype=p.dtype)
+        x = self._to_params(x)
         if x.dim() != 2 or x.shape[0] < 2 * m + 1:
             raise ValueError("online_contexts takes one take's features (T + 2m, D) with T >= 1, got %s" % (tuple(x.shape),))
         T, net = x.shape[0] - 2 * m, self.v_net
@@ -518,8 +555,7 @@ class VideoStateNet(nn.Module):
             out[:, H:] = net._sweep(net.rnn_b, x[rows], True)[0]
         return out
 
-    _TRAIN_CONTEXT = ("indices", "cnn_feat_ctx", "gather_indices", "_gather_tm", "_gather_unique", "_ctx_key", "_ragged",
-                      "_buckets", "_gather_sorted", "_ctx_sorted", "_frames")
+    _TRAIN_CONTEXT = _VideoFrontEnd._SHARED_CONTEXT + ("_gather_tm", "_gather_unique", "_ragged", "_frames")
 
     def adopt_train_context(self, other, x):
         """``initialize(x)`` in train mode when ``other`` has just been initialised with the SAME ``x``: the episode
@@ -528,28 +564,12 @@ class VideoStateNet(nn.Module):
         (ego_pose/core/agent_ego.py:34-41 initialises one after the other) share them -- one device sync and one pass of
         index arithmetic over the batch instead of two. Falls back to ``initialize`` when the two nets are not alike."""
         alike = (isinstance(other, VideoStateNet) and self.mode == "train" and other.mode == "train" and other.cnn_feat_ctx is not None
-                 and other._ctx_key is not None and self.v_margin == other.v_margin and self.cnn_feat_dim == other.cnn_feat_dim
-                 and self.v_net_type == other.v_net_type and self._cnn_table is not None and other._cnn_table is not None
-                 and self._cnn_table[0].data_ptr() == other._cnn_table[0].data_ptr()
-                 and np.array_equal(self._take_offset_host, other._take_offset_host) and other.cnn_feat_ctx.dtype == x[0].dtype)
+                 and self.v_margin == other.v_margin and self.cnn_feat_dim == other.cnn_feat_dim and self.v_net_type == other.v_net_type
+                 and self._same_table(other) and other.cnn_feat_ctx.dtype == x[0].dtype)
         if not alike:
             return self.initialize(x)
         for k in self._TRAIN_CONTEXT:
-            if hasattr(other, k):
-                setattr(self, k, getattr(other, k))
-
-    def _bucketed_context(self):
-        """(T - 2m, n_ep sorted by length, v_hdim): backward direction over the full window, forward direction per length bucket."""
-        ctx, rnn = self._ctx_sorted, self.v_net
-        T, B, _ = ctx.shape
-        Hd = rnn.rnn_f.hidden_size
-        out_f = ctx.new_zeros(T, B, Hd)
-        for i0, i1, Tb in self._buckets:
-            Tb = min(Tb, T)
-            out_f[:Tb, i0:i1] = rnn._sweep(rnn.rnn_f, ctx[:Tb, i0:i1], False)
-        if not rnn.bi_dir:
-            return out_f
-        return torch.cat((out_f, rnn._sweep(rnn.rnn_b, ctx, True)), 2)
+            setattr(self, k, getattr(other, k))
 
     def forward(self, x, lazy_width=0):
         """`lazy_width` > 0 (train mode; the width of the consumer's first layer, passed per call by an agent whose heads can
@@ -560,14 +580,10 @@ class VideoStateNet(nn.Module):
             out = torch.cat((self.v_out[[self.t], :], x), dim=1)
             self.t += 1
             return out
-        m = self.v_margin
         def tagged(out):
             if not x.requires_grad:
                 out._egp_ctx_cols = self.v_hdim
             return out
-        if self._buckets is not None:
-            ctx = self._bucketed_context()[m:-m].transpose(0, 1).reshape(-1, self.v_hdim)
-            return tagged(torch.cat((ctx.index_select(0, self._gather_sorted), x), dim=1))
         ctx2d = self.context_rows()
         if self._gather_unique and _gemm.gather_concat_available(ctx2d, self._gather_tm, x):
             if lazy_width and _gemm.fused_gather_available(self.v_hdim, lazy_width, x.shape[1]):
@@ -711,7 +727,7 @@ class VideoRegNet(nn.Module):          # (ResNet is defined further down; resolv
         return self._encode(self._frames(x))
 
 
-class VideoForecastNet(nn.Module):
+class VideoForecastNet(_VideoFrontEnd):
     """Policy/value front end of ego_forecast (models/video_forecast_net.py:7-111): the video net sees only the
     `v_margin` frames BEFORE the episode (causal LSTM or causal TCN, last output kept for the whole episode), the state goes through
     its own LSTM (`s_net_type='lstm'`, stepped one env-step at a time while sampling) or through unchanged ('id').
@@ -736,12 +752,8 @@ class VideoForecastNet(nn.Module):
         self.v_net = _video_net(cnn_feat_dim, v_hdim, v_net_type, v_net_param, True)
         if s_net_type == "lstm":
             self.s_net = RNN(state_dim, s_hdim, s_net_type, bi_dir=False)
-        self.v_out = None
-        self.t = 0
-        self.indices = self.gather_indices = self.cnn_feat_ctx = None
         self.num_episode = self.max_episode_len = None
-        self._cnn_table = None
-        self._grp = self._ctx_key = None
+        self._grp = None
         self.set_mode("test")
 
     def set_mode(self, mode):
@@ -749,28 +761,14 @@ class VideoForecastNet(nn.Module):
         if self.s_net_type == "lstm":
             self.s_net.set_mode("batch" if mode == "train" else "step")
 
-    def forward_v_net(self, x):
-        return _run_video_net(self.v_net, x)
+    def _extent(self, length):
+        return self.v_margin, length                          # rows [start - v_margin, start + length)
 
-    def attach_feature_table(self, table, take_offset):
-        host = np.asarray(take_offset, dtype=np.int64)
-        cur = getattr(self, "_cnn_table", None)
-        if cur is not None and cur[0] is table and np.array_equal(getattr(self, "_take_offset_host", None), host):
-            return                     # (same table as last time: no blocking upload)
-        self._cnn_table = (table, torch.as_tensor(host, dtype=torch.long, device=table.device))
-        self._take_offset_host = host.copy()
-        self._take_len = _take_lengths(take_offset, table.shape[0])
-
-    def check_windows(self, expert_ind, start_ind, length=0):
-        """Rows [start - v_margin, start + length) must lie inside their own take (see VideoStateNet.check_windows)."""
-        _check_windows(self._take_len, expert_ind, start_ind, self.v_margin, length)
+    def check_windows(self, expert_ind, start_ind, length=0):        # (the plain context window needs no `length`)
+        super().check_windows(expert_ind, start_ind, length)
 
     def window_features(self, expert_ind, start_ind, length=0):
-        """Rows [start - v_margin, start + length) of the given takes -> (v_margin + length, B, D) on device."""
-        table, off = self._cnn_table
-        base = off[expert_ind.long()] + start_ind.long() - self.v_margin
-        rows = base.unsqueeze(0) + torch.arange(self.v_margin + length, device=table.device).unsqueeze(1)
-        return table[rows]
+        return super().window_features(expert_ind, start_ind, length)
 
     def context(self, window):
         """(v_margin, B, D) -> the per-episode video context (B, v_hdim): last output of the causal net."""
@@ -785,46 +783,19 @@ class VideoForecastNet(nn.Module):
 
     def initialize(self, x):
         if self.mode == "test":
-            p = next(self.parameters())
-            x = x.to(device=p.device, dtype=p.dtype)
+            x = self._to_params(x)
             self.v_out = self.context(x.unsqueeze(1) if x.dim() == 2 else x)
             if self.s_net_type == "lstm":
                 self.s_net.initialize(self.v_out.shape[0])
             self.t = 0
             return
         masks, cnn_feat, v_metas = x
-        device, dtype = masks.device, masks.dtype
-        m = self.v_margin
-        ends = torch.nonzero(masks == 0).flatten().cpu().numpy()
-        n = masks.shape[0]
-        starts = np.concatenate(([0], ends[:-1] + 1))
-        lens = ends - starts + 1
-        max_len = _dist.global_max(int(lens.max()), device)       # batch-wide in the reference; global when sharded
-        self.num_episode, self.max_episode_len = len(ends), max_len
-        idx = np.arange(n)
-        covered = int(ends[-1]) + 1
-        idx[:covered] = np.repeat(np.arange(len(ends)), lens) * max_len + (np.arange(covered) - np.repeat(starts, lens))
-        self.indices = idx
-        meta = np.asarray(v_metas)[ends]
-        T_ctx = m + max_len if self.dynamic_v else m
-        if self._cnn_table is not None and self._cnn_table[0].device == device:
-            # episode count rounded up to a bucket (gemm_tuning.py); nothing gathers from the extra columns
-            pad = _tuning.pad_to(len(ends), _tuning.EPISODE_BUCKET) if _tuning.enabled() and len(ends) >= 4 * _tuning.EPISODE_BUCKET else 0
-            if pad:
-                meta = np.concatenate((meta, np.repeat(meta[:1], pad, axis=0)), 0)
-                self.num_episode = meta.shape[0]
-            self.check_windows(meta[:, 0], meta[:, 1])
-            win = self.window_features(torch.as_tensor(meta[:, 0], device=device), torch.as_tensor(meta[:, 1], device=device)).to(dtype)
-            ctx = win.new_zeros(T_ctx, meta.shape[0], self.cnn_feat_dim)
-            ctx[:m] = win
-        else:
-            ctx = np.zeros((T_ctx, len(ends), self.cnn_feat_dim))
-            for e, (ei, si) in enumerate(meta):
-                ctx[:m, e, :] = cnn_feat[int(ei)][int(si) - m: int(si)]
-            ctx = torch.as_tensor(ctx, dtype=dtype, device=device)
-        self.cnn_feat_ctx = ctx
-        self.gather_indices = torch.as_tensor(idx, dtype=torch.long, device=device)
-        self._ctx_key = (int(max_len), meta.shape[0], hash(meta.tobytes()))       # which windows / episodes this batch holds
+        ep = _segment_episodes(masks, v_metas)
+        self.indices, self.max_episode_len = ep.indices, ep.max_len
+        T_ctx = self.v_margin + ep.max_len if self.dynamic_v else self.v_margin
+        # (the episode bucket's extra columns count as episodes of the padded blocks; nothing gathers from them)
+        self.num_episode = self._train_windows(ep, cnn_feat, masks.device, masks.dtype, 0, rows=T_ctx).shape[0]
+        self.gather_indices = torch.as_tensor(ep.indices, dtype=torch.long, device=masks.device)
         self._grp = None
 
     def state_sequences(self, x):
@@ -866,9 +837,8 @@ def grouped_video_context(nets):
         return False
     n0 = nets[0]
     for n in nets:
-        if not (isinstance(n, VideoStateNet) and n.mode == "train" and n._buckets is None and getattr(n.v_net, "cell_type", None) == "lstm"
-                and n.cnn_feat_ctx is not None and n.cnn_feat_ctx.shape == n0.cnn_feat_ctx.shape and n._ctx_key == n0._ctx_key
-                and n.cnn_feat_ctx.dtype == n0.cnn_feat_ctx.dtype and n.v_net.bi_dir == n0.v_net.bi_dir):
+        if not (isinstance(n, VideoStateNet) and _same_windows(n, n0) and getattr(n.v_net, "cell_type", None) == "lstm"
+                and n.v_net.bi_dir == n0.v_net.bi_dir):
             return False
     cells, revs = [], []
     for n in nets:
@@ -878,8 +848,7 @@ def grouped_video_context(nets):
     x = n0.cnn_feat_ctx                      # same episodes, same windows for every net (initialize() of the same batch)
     if not _hip_lstm.group_available(x, cells):
         return False
-    hs = _hip_lstm.lstm_group(x, cells, revs, pairs=n0.v_net.bi_dir, ragged=n0._ragged,     # bi-directional: (T, B, 2H) per net, no concatenation
-                              frames=getattr(n0, "_frames", None))
+    hs = _hip_lstm.lstm_group(x, cells, revs, pairs=n0.v_net.bi_dir, ragged=n0._ragged, frames=n0._frames)     # bi-directional: (T, B, 2H) per net, no concatenation
     for i, n in enumerate(nets):
         n._v_ctx = (hs[i], torch.is_grad_enabled())
     return True
@@ -893,9 +862,8 @@ def grouped_forecast_context(nets, x):
         return False
     n0 = nets[0]
     for n in nets:
-        if not (isinstance(n, VideoForecastNet) and n.mode == "train" and n.s_net_type == "lstm" and n.cnn_feat_ctx is not None
-                and n._ctx_key is not None and n._ctx_key == n0._ctx_key and n.cnn_feat_ctx.shape == n0.cnn_feat_ctx.shape
-                and n.cnn_feat_ctx.dtype == n0.cnn_feat_ctx.dtype and n.dynamic_v == n0.dynamic_v and n.state_dim == n0.state_dim
+        if not (isinstance(n, VideoForecastNet) and _same_windows(n, n0) and n.s_net_type == "lstm"
+                and n.dynamic_v == n0.dynamic_v and n.state_dim == n0.state_dim
                 and isinstance(n.v_net, RNN) and not n.v_net.bi_dir and not n.s_net.bi_dir and n.v_net.cell_type == "lstm" and n.s_net.cell_type == "lstm"):
             return False
     v_cells, s_cells = [n.v_net.rnn_f for n in nets], [n.s_net.rnn_f for n in nets]

@@ -166,6 +166,42 @@ def test_video_state_net_train_mode_device_gather_matches_reference():
     np.testing.assert_allclose(out.cpu().numpy(), g["train_out"], rtol=1e-10, atol=1e-11)
 
 
+@pytest.mark.parametrize("dynamic_v", [False, True])
+def test_video_forecast_net_train_mode_device_gather_matches_host_loop(dynamic_v):
+    """The forecast counterpart: a float32 VideoForecastNet on the device, initialised from the HBM feature table, holds the
+    same `cnn_feat_ctx` and gives the same forward output as the host loop's initialisation of the same batch (five episodes
+    of 1, 4, 2, 7 and 3 steps over two takes; state LSTM)."""
+    from egopose_amd.nets import VideoForecastNet
+    cdim, hdim, margin, sdim, lens = 6, 8, 3, 5, [1, 4, 2, 7, 3]
+    rng = np.random.RandomState(7)
+    feats = [rng.normal(size=(40, cdim)), rng.normal(size=(30, cdim))]
+    masks, metas = [], []
+    for L in lens:
+        e = int(rng.randint(2))
+        masks += [1.0] * (L - 1) + [0.0]
+        metas += [[e, int(rng.randint(margin, feats[e].shape[0] - max(lens)))]] * L
+    masks = torch.tensor(masks, dtype=torch.float32, device="cuda")
+    metas = np.array(metas)
+    states = torch.tensor(rng.normal(size=(len(metas), sdim)), dtype=torch.float32, device="cuda")
+    torch.manual_seed(7)
+    net = VideoForecastNet(cdim, sdim, hdim, margin, "lstm", None, None, "lstm", dynamic_v).cuda()
+    net.set_mode("train")
+    net.initialize((masks, feats, metas))                    # no table attached: the host loop
+    host_ctx, host_indices = net.cnn_feat_ctx, net.indices
+    with torch.no_grad():
+        host_out = net(states)
+    table = torch.as_tensor(np.concatenate(feats, 0), dtype=torch.float32, device="cuda")
+    net.attach_feature_table(table, [0, feats[0].shape[0]])
+    net.initialize((masks, None, metas))                     # windows come from the table
+    assert net.cnn_feat_ctx is not host_ctx and tuple(net.cnn_feat_ctx.shape) == (margin + 7 if dynamic_v else margin, len(lens), cdim)
+    assert torch.equal(net.cnn_feat_ctx, host_ctx)
+    np.testing.assert_array_equal(net.indices, host_indices)
+    with torch.no_grad():
+        out = net(states)
+    assert tuple(out.shape) == (len(metas), hdim + sdim)
+    np.testing.assert_allclose(out.cpu().numpy(), host_out.cpu().numpy(), rtol=1e-10, atol=1e-11)
+
+
 @pytest.mark.parametrize("grouped", [False, True])
 def test_video_state_net_train_mode_hip_lstm_matches_reference(grouped, monkeypatch):
     """Same row with the float32 persistent recurrences (hidden 64 per direction): the policy's train-mode input of the
