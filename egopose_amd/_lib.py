@@ -160,6 +160,22 @@ class PpoLossMbDesc(C.Structure):
 PPO_LOSS_MB_MAX_ROWS = 16384
 
 
+class PpoStatsDesc(C.Structure):
+    """egp_ppo_stats_desc (include/egopose_hip.h)."""
+    _fields_ = [("n", C.c_int32), ("n_pol", C.c_int32), ("act_dim", C.c_int32),
+                ("rows", vp), ("pred", vp), ("returns", vp),
+                ("mean", vp), ("ld_mean", C.c_int64),
+                ("actions", vp), ("ld_act", C.c_int64),
+                ("log_std", vp), ("adv", vp), ("fixed_logp", vp),
+                ("clip_eps", C.c_double),
+                ("logp_out", vp), ("record", vp), ("workspace", vp)]
+
+
+# the record egp_ppo_stats_f32 writes: index of every field (EGP_PPO_STATS_* in the header)
+PPO_STATS_FIELDS = ("n_pol", "k1", "k3", "clipped", "ratio_min", "ratio_max", "n", "sum_y", "sum_yy", "sum_d", "sum_dd", "nonfinite", "entropy")
+PPO_STATS = {k: i for i, k in enumerate(PPO_STATS_FIELDS)}
+
+
 class TcnDesc(C.Structure):
     """egp_tcn_desc (include/egopose_hip.h)."""
     _fields_ = [("T", C.c_int32), ("B", C.c_int32), ("C_in", C.c_int32), ("C_out", C.c_int32),
@@ -289,6 +305,8 @@ SIGNATURES = {
     "egp_gemm_f32": (C.c_int, [C.POINTER(GemmDesc), vp]),
     "egp_ppo_loss_workspace_bytes": (_i64, [_i32, _i32, _i32]),
     "egp_ppo_loss_f32": (C.c_int, [C.POINTER(PpoLossDesc), vp]),
+    "egp_ppo_stats_workspace_bytes": (_i64, [_i32, _i32, _i32]),
+    "egp_ppo_stats_f32": (C.c_int, [C.POINTER(PpoStatsDesc), vp]),
     "egp_minibatch_plan_f32": (C.c_int, [C.POINTER(MinibatchPlanDesc), vp]),
     "egp_ppo_loss_mb_f32": (C.c_int, [C.POINTER(PpoLossMbDesc), vp]),
     "egp_gail_rows_f32": (C.c_int, [C.POINTER(GailRowsDesc), vp]),

@@ -350,10 +350,76 @@ class AgentPG(Agent):
 
 class AgentPPO(AgentPG):
 
-    def __init__(self, clip_epsilon=0.2, opt_batch_size=64, use_mini_batch=False, policy_grad_clip=None, **kwargs):
+    def __init__(self, clip_epsilon=0.2, opt_batch_size=64, use_mini_batch=False, policy_grad_clip=None, target_kl=None,
+                 update_diagnostics=False, stop_on_nonfinite=False, **kwargs):
+        """The last three keywords switch the update monitor on (all off = the reference's update, nothing added):
+          update_diagnostics  every full-batch epoch also evaluates the monitor's record (optim.ppo_stats: one more launch per
+                              epoch on the fused path; optim.ppo_stats_torch on the plain one). `update_stats` gains one list per
+                              figure of optim.stats_summary with one entry per epoch that took its step, `epochs_run`,
+                              `stop_reason` (None) and `stop_figures` (None). The records are read with the losses, after the
+                              last epoch is queued: no host synchronisation is added.
+          target_kl           stop the epochs once approx_kl (the k3 estimate of KL(sampling policy || current policy), mean over
+                              the exploration rows) exceeds it: `stop_reason` "kl". A NaN estimate (no exploration rows) never stops.
+          stop_on_nonfinite   stop before any step of an epoch whose inputs hold a non-finite value (a NaN advantage, an inf
+                              value): `stop_reason` "nonfinite".
+        Either of the last two makes the host read the epoch's record -- ONE small device-to-host copy per epoch, after the
+        epoch's loss and monitor launches and BEFORE its backward pass -- and, with more than one rank, one all-gather of the
+        records per epoch, so that every rank decides from the same global figures (ranks deciding differently would deadlock
+        in the gradient all-reduce). A stopped epoch takes no backward pass, no gradient exchange and no optimizer step:
+        parameters, Adam moments and step counts are those after the previous epoch; its figures are `stop_figures`."""
         super().__init__(**kwargs)
         self.clip_epsilon, self.opt_batch_size = clip_epsilon, opt_batch_size
         self.use_mini_batch, self.policy_grad_clip = use_mini_batch, policy_grad_clip
+        self.target_kl = None if target_kl is None else float(target_kl)
+        self.update_diagnostics, self.stop_on_nonfinite = bool(update_diagnostics), bool(stop_on_nonfinite)
+        if self.target_kl is not None and not self.target_kl >= 0:
+            raise ValueError("target_kl must be a number >= 0 (or None), got %r" % (target_kl,))
+        if use_mini_batch and self._monitor_on():
+            raise ValueError("the update monitor (target_kl / update_diagnostics / stop_on_nonfinite) covers the full-batch update: with "
+                             "use_mini_batch=True an epoch is thousands of windows, each with its own step")
+
+    # -- the update monitor ----------------------------------------------------------------------------
+    def _monitor_on(self):
+        return self.update_diagnostics or self._monitor_gated()
+
+    def _monitor_gated(self):
+        """True when the host decides after every epoch's record whether the epoch takes its step."""
+        return self.target_kl is not None or self.stop_on_nonfinite
+
+    def _gather_records(self, recs):
+        """`recs` (k, fields) float64, this rank's records of k epochs -> host lists [rank][epoch][field]: one device-to-host
+        copy, after one all-gather when there are several ranks."""
+        if D.world_size() == 1:
+            return [recs.tolist()]
+        mine = recs.to(D._comm_device(recs.device)).contiguous()
+        rows = torch.empty((D.world_size(),) + tuple(mine.shape), dtype=mine.dtype, device=mine.device)
+        if torch.distributed.get_backend() != "gloo":
+            torch.distributed.all_gather_into_tensor(rows, mine)
+        else:
+            torch.distributed.all_gather(list(rows.unbind(0)), mine)
+        D._note()
+        return rows.tolist()
+
+    def _monitor_decide(self, fig):
+        """The stop rule on the GLOBAL figures of one epoch -> "nonfinite", "kl" or None."""
+        if self.stop_on_nonfinite and fig["nonfinite_rows"] > 0:
+            return "nonfinite"
+        if self.target_kl is not None and fig["approx_kl"] > self.target_kl:        # (NaN compares False: no exploration rows, no stop)
+            return "kl"
+        return None
+
+    def _monitor_gate(self, rec):
+        """After an epoch's launches: read its record `rec` (fields,), combine the ranks' -> (figures, stop reason or None)."""
+        fig = O.stats_summary([r[0] for r in self._gather_records(rec.unsqueeze(0))])
+        return fig, self._monitor_decide(fig)
+
+    def _monitor_publish(self, stats, figs, epochs_run, reason):
+        """`figs`: the figures of every epoch evaluated, in order (the stopped one last)."""
+        for k in O.STATS_KEYS:
+            stats[k] = [f[k] for f in figs[:epochs_run]]
+        stats["epochs_run"], stats["stop_reason"] = epochs_run, reason
+        stats["stop_figures"] = figs[epochs_run] if reason is not None else None
+        return stats
 
     def _group_contexts(self, states=None):
         """Hook: prepare the critic's and the actor's state transforms together (AgentEgo). False = nothing prepared."""
@@ -452,6 +518,8 @@ class AgentPPO(AgentPG):
             fixed = first_pass[1].detach()
         adv = advantages if ind is None else advantages[ind]
         losses = []
+        mon, gated = self._monitor_on(), self._monitor_gated()
+        recs, figs, reason = [], [], None
         for epoch in range(self.opt_num_epochs):
             # critic and actor have disjoint parameters: one backward over the sum of the two losses yields exactly the two
             # separate gradients, before the single gradient exchange; the value step precedes the policy step as in the
@@ -460,11 +528,24 @@ class AgentPPO(AgentPG):
             pred, logp = first_pass[:2] if first_pass is not None and epoch == 0 else self._epoch_forward(states, actions, ind, False)
             v_loss = (pred - returns).pow(2).sum() / n_val
             s_loss = self._surrogate(logp, adv, fixed, n_exp)
+            if mon:
+                recs.append(O.ppo_stats_torch(pred.detach(), returns, None, None, getattr(self.cn.policy_net, "action_log_std", None), advantages,
+                                              fixed, self.clip_epsilon, rows=ind, logp=logp.detach()))
+                if gated:
+                    fig, reason = self._monitor_gate(recs[-1])
+                    figs.append(fig)
+                    if reason is not None:
+                        break
             self._zero_grads()
             (v_loss + s_loss).backward()
             self._optim_step()
             losses.append((v_loss.detach(), s_loss.detach()))
         self.update_stats = {"value_loss": [float(v) for v, _ in losses], "surr_loss": [float(s) for _, s in losses]}
+        if mon:
+            if not gated and recs:
+                by_rank = self._gather_records(torch.stack(recs))
+                figs = [O.stats_summary([r[e] for r in by_rank]) for e in range(len(recs))]
+            self._monitor_publish(self.update_stats, figs, len(losses), reason)
 
     # -- shuffled mini-batch epochs (agents/agent_ppo.py:24-44) ----------------------------------------
     def _update_policy_minibatch(self, states, actions, returns, advantages, exps):
@@ -568,7 +649,10 @@ class AgentPPO(AgentPG):
         fixed = torch.empty(n_ind, dtype=torch.float32, device=dev)
         d_pred = torch.empty(n, 1, dtype=torch.float32, device=dev)
         d_mean = torch.empty(n_ind, A, dtype=torch.float32, device=dev)
-        rec = torch.zeros(max(1, self.opt_num_epochs), 2, dtype=torch.float64, device=dev)
+        mon, gated = self._monitor_on(), self._monitor_gated()
+        # one row per epoch: both losses and, with the monitor on, the epoch's record behind them (read together at the end)
+        rec = torch.zeros(max(1, self.opt_num_epochs), 2 + (len(O.L.PPO_STATS_FIELDS) if mon else 0), dtype=torch.float64, device=dev)
+        figs, reason, epochs_run = [], None, 0
         act = actions if actions.stride(1) == 1 else actions.contiguous()
         eval_fixed = first_pass is None and self._dropout_active()
         if eval_fixed:
@@ -577,20 +661,34 @@ class AgentPPO(AgentPG):
                     mean = self._policy_head(states, actions, ind, True)
             # (only `fixed` is kept of this launch: the value columns are placeholders, epoch 0 rewrites rec[0] and the gradients)
             O.ppo_losses(returns.reshape(-1, 1), returns, mean, act, log_std.detach(), advantages, fixed, True, self.clip_epsilon, n_val, n_exp,
-                         rows=ind, d_pred=d_pred, d_mean=d_mean, losses_out=rec[0])
+                         rows=ind, d_pred=d_pred, d_mean=d_mean, losses_out=rec[0, :2])
         for epoch in range(self.opt_num_epochs):
             pred, mean = first_pass[:2] if first_pass is not None and epoch == 0 else self._epoch_forward(states, actions, ind, True)
             self._zero_grads()
             _, _, _, d_ls = O.ppo_losses(pred.detach(), returns, mean.detach(), act, log_std.detach(), advantages, fixed, epoch == 0 and not eval_fixed,
                                          self.clip_epsilon, n_val, n_exp, rows=ind, d_pred=d_pred, d_mean=d_mean,
-                                         want_d_log_std=learn_std, losses_out=rec[epoch])
+                                         want_d_log_std=learn_std, losses_out=rec[epoch, :2])
+            if mon:
+                O.ppo_stats(pred.detach(), returns, mean.detach(), act, log_std.detach(), advantages, fixed, self.clip_epsilon, rows=ind,
+                            out=rec[epoch, 2:])
+                if gated:
+                    fig, reason = self._monitor_gate(rec[epoch, 2:])
+                    figs.append(fig)
+                    if reason is not None:
+                        break
             torch.autograd.backward([pred, mean], [d_pred, d_mean])
             if learn_std:
                 log_std.grad = d_ls.view_as(log_std)
             self._optim_step()
+            epochs_run += 1
         self._epochs_enqueued()              # (the host would only wait from here on: the GPU still works through the epochs)
         host = rec.tolist()
-        self.update_stats = {"value_loss": [r[0] for r in host[:self.opt_num_epochs]], "surr_loss": [r[1] for r in host[:self.opt_num_epochs]]}
+        self.update_stats = {"value_loss": [r[0] for r in host[:epochs_run]], "surr_loss": [r[1] for r in host[:epochs_run]]}
+        if mon:
+            if not gated and epochs_run:
+                by_rank = [[r[2:] for r in host[:epochs_run]]] if D.world_size() == 1 else self._gather_records(rec[:epochs_run, 2:])
+                figs = [O.stats_summary([r[e] for r in by_rank]) for e in range(epochs_run)]
+            self._monitor_publish(self.update_stats, figs, epochs_run, reason)
 
 
 def _quat_v3_marker(fn):

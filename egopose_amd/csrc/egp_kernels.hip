@@ -2052,7 +2052,7 @@ int64_t egp_abi_sizeof(const char *name) {
     EGP_ABI_SIZE(egp_ppo_loss_desc) EGP_ABI_SIZE(egp_adam_segment) EGP_ABI_SIZE(egp_host_probe_result)
     EGP_ABI_SIZE(egp_minibatch_plan_desc) EGP_ABI_SIZE(egp_ppo_loss_mb_desc) EGP_ABI_SIZE(egp_tcn_desc)
     EGP_ABI_SIZE(egp_policy_desc) EGP_ABI_SIZE(egp_gail_rows_desc) EGP_ABI_SIZE(egp_bce_logits_desc)
-    EGP_ABI_SIZE(egp_lstm_desc)
+    EGP_ABI_SIZE(egp_lstm_desc) EGP_ABI_SIZE(egp_ppo_stats_desc)
 #undef EGP_ABI_SIZE
     return -1;
 }

@@ -4,6 +4,8 @@
 //   k_ppo_loss   agents/agent_pg.py:19-26 (critic MSE), agents/agent_ppo.py:58-65 (clipped surrogate) over
 //                core/distributions.py:6-25 / utils/math.py:14-17 (diagonal Gaussian log-density), plus what autograd would
 //                send back to `values_pred` and `action_mean`
+//   k_ppo_stats  the update monitor (no reference counterpart): KL estimators, clip fraction, ratio range, explained-variance moments
+//                and non-finite rows of an epoch as one record of float64 raw sums, from k_ppo_loss's own row_logp
 //   k_minibatch_plan / k_ppo_loss_mb   the mini-batch epochs (agents/agent_ppo.py:24-44): the epoch's shuffle as one gather of the
 //                update's columns + per-window exploration-row counts, and k_ppo_loss for one window with data-independent shapes
 //   k_sqnorm     torch.nn.utils.clip_grad_norm_'s total norm (agents/agent_ppo.py:53-56)
@@ -206,6 +208,145 @@ __global__ __launch_bounds__(LOSS_BLOCK) void k_ppo_loss_final(LossArgs a, int n
             for (int b = 0; b < a.pol_blocks; ++b) d += a.part[(long)b * stride + 2 + j];
             a.d_log_std[j] = (float)d;
         }
+    }
+}
+
+// ------------------------------------------------------------------------------------------------ update monitor
+// k_ppo_stats: what a PPO user reads off an epoch -- KL estimators, clip fraction, ratio range of the policy rows (logp from
+// row_logp, the float32 log-ratio as row_surrogate forms it, everything after that in float64), the moments of returns and
+// residuals for the critic's explained variance, and the number of sample rows with a non-finite operand -- as RAW sums, so that
+// ranks combine by adding. A launch of its own: k_ppo_loss, its registers and its bits stay as they are. Same shape as the loss
+// launch: blocks [0, pol_blocks) take policy rows (16 lanes per row), the rest value elements; per-workgroup float64
+// partials, then one workgroup adds them in index order (k_ppo_stats_final).
+constexpr int STATS_PART = 12;                 // doubles per workgroup: k1, k3, clipped, min r, max r, sum y, y^2, d, d^2, non-finite (+ 2 pad)
+
+struct StatsArgs {
+    int n, n_pol, act_dim;
+    const long long *rows;
+    const float *pred, *returns, *mean, *actions, *log_std, *adv, *fixed_logp;
+    long ld_mean, ld_act;
+    double clip_eps;
+    float *logp_out;
+    double *record;
+    double *part;              // [gridDim.x][STATS_PART]
+    int pol_blocks;
+};
+
+__device__ __forceinline__ double block_min(double v, double *s_red) {
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) v = fmin(v, __shfl_down(v, off, 64));
+    const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+    __syncthreads();
+    if (lane == 0) s_red[wave] = v;
+    __syncthreads();
+    return fmin(fmin(s_red[0], s_red[1]), fmin(s_red[2], s_red[3]));
+}
+
+__device__ __forceinline__ double block_max(double v, double *s_red) {
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) v = fmax(v, __shfl_down(v, off, 64));
+    const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+    __syncthreads();
+    if (lane == 0) s_red[wave] = v;
+    __syncthreads();
+    return fmax(fmax(s_red[0], s_red[1]), fmax(s_red[2], s_red[3]));
+}
+
+// expm1(x) - x, the k3 term, without the cancellation of the subtraction for small |x| (the usual case: x is an epoch's log-ratio):
+// x^2 (1/2 + x/6 + ... + x^14 / 16!) below 0.5 (the first term left out is under 2^-56 of the sum there) -- never negative.
+__device__ __forceinline__ double k3_term(double x) {
+    if (!(fabs(x) < 0.5)) return expm1(x) - x;
+    const double c[15] = {1.0 / 2, 1.0 / 6, 1.0 / 24, 1.0 / 120, 1.0 / 720, 1.0 / 5040, 1.0 / 40320, 1.0 / 362880, 1.0 / 3628800,
+                          1.0 / 39916800, 1.0 / 479001600, 1.0 / 6227020800.0, 1.0 / 87178291200.0, 1.0 / 1307674368000.0,
+                          1.0 / 20922789888000.0};
+    double p = c[14];
+#pragma unroll
+    for (int k = 13; k >= 0; --k) p = fma(x, p, c[k]);
+    return (x * x) * p;
+}
+
+__global__ __launch_bounds__(LOSS_BLOCK) void k_ppo_stats(StatsArgs a) {
+    __shared__ double s_red[4];
+    const int t = threadIdx.x;
+    double k1 = 0.0, k3 = 0.0, clipped = 0.0, rmin = INFINITY, rmax = -INFINITY;
+    double sy = 0.0, syy = 0.0, sd = 0.0, sdd = 0.0, bad = 0.0;
+    if ((int)blockIdx.x >= a.pol_blocks) {
+        // ---- critic: moments of y = returns and d = returns - pred; a row with a non-finite pred / returns is counted here
+        const int vb = blockIdx.x - a.pol_blocks, nvb = gridDim.x - a.pol_blocks;
+        for (long i = (long)vb * LOSS_BLOCK + t; i < a.n; i += (long)nvb * LOSS_BLOCK) {
+            const float p = a.pred[i], y = a.returns[i];
+            const double yd = (double)y, dd = (double)y - (double)p;
+            sy += yd; syy += yd * yd;
+            sd += dd; sdd += dd * dd;
+            if (!(isfinite(p) && isfinite(y))) bad += 1.0;
+        }
+    } else {
+        // ---- actor: a 16-lane group per row, as k_ppo_loss; lane 0 of the group carries the row's terms
+        const int grp = t / LOSS_GROUP, l = t % LOSS_GROUP;
+        constexpr int GPB = LOSS_BLOCK / LOSS_GROUP;
+        for (long r0 = (long)blockIdx.x * GPB; r0 < a.n_pol; r0 += (long)a.pol_blocks * GPB) {
+            const long i = r0 + grp;
+            const bool ok = i < a.n_pol;
+            const long s = ok ? (a.rows ? (long)a.rows[i] : i) : 0;
+            float z[LOSS_MAXD], istd[LOSS_MAXD];
+            const float logp = row_logp(ok, l, a.act_dim, a.actions + s * a.ld_act, a.mean + i * a.ld_mean, a.log_std, z, istd);
+            if (ok && l == 0) {
+                if (a.logp_out) a.logp_out[i] = logp;
+                const float lrf = logp - a.fixed_logp[i];              // the float32 log-ratio row_surrogate exponentiates
+                const double lr = (double)lrf;
+                const double r = exp(lr);
+                k1 -= lr;
+                k3 += k3_term(lr);
+                if (fabs(r - 1.0) > a.clip_eps) clipped += 1.0;
+                rmin = fmin(rmin, r);
+                rmax = fmax(rmax, r);
+                // the sample row is counted once: by the critic's blocks when its pred / returns is non-finite, else here
+                const bool v_ok = s >= a.n || (isfinite(a.pred[s]) && isfinite(a.returns[s]));
+                if (v_ok && !(isfinite(a.adv[s]) && isfinite(logp))) bad += 1.0;
+            }
+        }
+    }
+    double *mine = a.part + (long)blockIdx.x * STATS_PART;
+    const double v[10] = {block_sum(k1, s_red), block_sum(k3, s_red), block_sum(clipped, s_red), block_min(rmin, s_red), block_max(rmax, s_red),
+                          block_sum(sy, s_red), block_sum(syy, s_red), block_sum(sd, s_red), block_sum(sdd, s_red), block_sum(bad, s_red)};
+    if (t == 0) {
+#pragma unroll
+        for (int k = 0; k < 10; ++k) mine[k] = v[k];
+    }
+}
+
+// the partials of `nb` workgroups -> the record (layout: include/egopose_hip.h); nb = 0 writes the record of an empty batch
+__global__ __launch_bounds__(LOSS_BLOCK) void k_ppo_stats_final(StatsArgs a, int nb) {
+    __shared__ double s_red[4];
+    const int t = threadIdx.x;
+    double acc[10] = {0.0, 0.0, 0.0, INFINITY, -INFINITY, 0.0, 0.0, 0.0, 0.0, 0.0};
+    for (int b = t; b < nb; b += LOSS_BLOCK) {               // 256 interleaved slices, combined by the fixed trees below
+        const double *p = a.part + (long)b * STATS_PART;
+#pragma unroll
+        for (int k = 0; k < 10; ++k) acc[k] = k == 3 ? fmin(acc[k], p[k]) : (k == 4 ? fmax(acc[k], p[k]) : acc[k] + p[k]);
+    }
+    double tot[10];
+#pragma unroll
+    for (int k = 0; k < 10; ++k) tot[k] = k == 3 ? block_min(acc[k], s_red) : (k == 4 ? block_max(acc[k], s_red) : block_sum(acc[k], s_red));
+    if (t == 0) {
+        double *o = a.record;
+        o[EGP_PPO_STATS_N_POL] = (double)a.n_pol;
+        o[EGP_PPO_STATS_K1] = tot[0];
+        o[EGP_PPO_STATS_K3] = tot[1];
+        o[EGP_PPO_STATS_CLIPPED] = tot[2];
+        o[EGP_PPO_STATS_RATIO_MIN] = tot[3];
+        o[EGP_PPO_STATS_RATIO_MAX] = tot[4];
+        o[EGP_PPO_STATS_N] = (double)a.n;
+        o[EGP_PPO_STATS_SUM_Y] = tot[5];
+        o[EGP_PPO_STATS_SUM_YY] = tot[6];
+        o[EGP_PPO_STATS_SUM_D] = tot[7];
+        o[EGP_PPO_STATS_SUM_DD] = tot[8];
+        o[EGP_PPO_STATS_NONFINITE] = tot[9];
+        // entropy of N(., diag exp(2 log_std)) with a state-independent log_std: sum_j log_std_j + act_dim / 2 * log(2 pi e)
+        double e = a.log_std ? 0.0 : (double)NAN;              // (no log_std: only allowed without policy rows)
+        if (a.log_std)
+            for (int j = 0; j < a.act_dim; ++j) e += (double)a.log_std[j];
+        o[EGP_PPO_STATS_ENTROPY] = e + 0.5 * (double)a.act_dim * 2.8378770664093453;
     }
 }
 
@@ -526,6 +667,44 @@ int egp_ppo_loss_f32(const egp_ppo_loss_desc *d, void *stream) {
     if (rc != EGP_OK) return rc;
     k_ppo_loss_final<<<dim3(1), dim3(LOSS_BLOCK), 0, (hipStream_t)stream>>>(a, (int)(pb + vb));
     return after_launch("k_ppo_loss_final");
+}
+
+int64_t egp_ppo_stats_workspace_bytes(int32_t n, int32_t n_pol, int32_t act_dim) {
+    (void)n; (void)n_pol; (void)act_dim;
+    return (int64_t)(2 * LOSS_MAX_BLOCKS) * STATS_PART * (int64_t)sizeof(double) + 64;
+}
+
+int egp_ppo_stats_f32(const egp_ppo_stats_desc *d, void *stream) {
+    EGP_REQUIRE(d, "descriptor is NULL");
+    EGP_REQUIRE(d->n >= 0 && d->n_pol >= 0 && d->act_dim >= 0 && d->act_dim <= LOSS_MAX_ACT, "bad sizes (act_dim <= 256)");
+    EGP_REQUIRE(d->record && d->workspace, "NULL record / workspace");
+    EGP_REQUIRE(d->n == 0 || (d->pred && d->returns), "NULL critic operand");
+    EGP_REQUIRE(d->n_pol == 0 || (d->mean && d->actions && d->log_std && d->adv && d->fixed_logp), "NULL actor operand");
+    EGP_REQUIRE(d->n_pol <= 1 || (d->ld_mean >= d->act_dim && d->ld_act >= d->act_dim), "row stride smaller than the row");
+    EGP_REQUIRE(d->clip_eps >= 0.0, "clip_eps must not be negative (or NaN)");
+    StatsArgs a{};
+    a.n = d->n; a.n_pol = d->n_pol; a.act_dim = d->act_dim;
+    a.rows = (const long long *)d->rows;
+    a.pred = d->pred; a.returns = d->returns; a.mean = d->mean; a.actions = d->actions; a.log_std = d->log_std; a.adv = d->adv;
+    a.fixed_logp = d->fixed_logp;
+    a.ld_mean = d->ld_mean; a.ld_act = d->ld_act;
+    a.clip_eps = d->clip_eps;
+    a.logp_out = d->logp_out;
+    a.record = d->record;
+    a.part = (double *)d->workspace;
+    constexpr int GPB = LOSS_BLOCK / LOSS_GROUP;
+    long pb = ((long)d->n_pol + 4 * GPB - 1) / (4 * GPB);          // the loss launch's grid: ~4 passes per block
+    pb = pb < 1 ? (d->n_pol > 0 ? 1 : 0) : (pb > LOSS_MAX_BLOCKS ? LOSS_MAX_BLOCKS : pb);
+    long vb = ((long)d->n + 4 * LOSS_BLOCK - 1) / (4 * LOSS_BLOCK);
+    vb = vb < 1 ? (d->n > 0 ? 1 : 0) : (vb > LOSS_MAX_BLOCKS ? LOSS_MAX_BLOCKS : vb);
+    a.pol_blocks = (int)pb;
+    if (pb + vb > 0) {
+        k_ppo_stats<<<dim3((unsigned)(pb + vb)), dim3(LOSS_BLOCK), 0, (hipStream_t)stream>>>(a);
+        int rc = after_launch("k_ppo_stats");
+        if (rc != EGP_OK) return rc;
+    }
+    k_ppo_stats_final<<<dim3(1), dim3(LOSS_BLOCK), 0, (hipStream_t)stream>>>(a, (int)(pb + vb));
+    return after_launch("k_ppo_stats_final");
 }
 
 int egp_minibatch_plan_f32(const egp_minibatch_plan_desc *d, void *stream) {

@@ -3,6 +3,10 @@
   ppo_losses(...)   critic MSE (agents/agent_pg.py:19-26) + clipped surrogate (agents/agent_ppo.py:58-65 over
                     core/distributions.py:6-25) and their gradients w.r.t. `values_pred` / `action_mean` in ONE launch; the caller
                     back-propagates from those two tensors (no scalar-loss graph)
+  ppo_stats(...) / ppo_stats_torch(...) / stats_summary(...)   the update monitor: one record of float64 raw sums about the tensors
+                    an epoch hands to ppo_losses (KL estimators, clipped rows, ratio range, moments for the critic's explained
+                    variance, non-finite rows, entropy) from a launch of its own, the same definitions in torch ops for any device
+                    and dtype, and the host-side combination of the ranks' records into the figures
   minibatch_plan(...)  one launch per mini-batch epoch (agents/agent_ppo.py:25-31): the update's six columns gathered through the
                     epoch's permutation into the caller's buffers + the number of exploration rows of every window, on the device
   ppo_losses_mb(...)   ppo_losses for ONE window of those buffers with shapes that do not depend on the data: the rows with
@@ -26,6 +30,7 @@ The kernels have no CPU form: on a CPU device (the oracle-side parity tests) the
 from __future__ import annotations
 
 import ctypes as C
+import math
 
 import torch
 
@@ -97,6 +102,121 @@ def ppo_losses(pred, returns, mean, actions, log_std, adv, fixed_logp, write_fix
     d.losses, d.workspace = losses.data_ptr(), ws.data_ptr()
     L.check(lib.egp_ppo_loss_f32(C.byref(d), L.current_stream()), "egp_ppo_loss_f32")
     return losses, d_pred, d_mean, d_ls
+
+
+def ppo_stats(pred, returns, mean, actions, log_std, adv, fixed_logp, clip_eps, rows=None, out=None, logp_out=None):
+    """-> the update monitor's record: float64[len(L.PPO_STATS_FIELDS)] on the device (`out`, or a new tensor), RAW sums over
+    this rank's rows from one `egp_ppo_stats_f32` call on the tensors an epoch hands to `ppo_losses` (same shapes and `rows`;
+    the layout is the header's, index by L.PPO_STATS[name]). `logp_out` (n_pol,) float32 receives the log-probabilities. Nothing
+    is read back; `stats_summary` turns the record of one rank, or those of several, into the figures."""
+    lib = L.load()
+    n, n_pol, A = pred.shape[0], mean.shape[0], mean.shape[1]
+    dev = pred.device
+    pred1, ret1, adv1 = pred.reshape(-1), returns.reshape(-1), adv.reshape(-1)
+    for name, t, want in (("pred", pred1, n), ("returns", ret1, n), ("adv", adv1, n), ("fixed_logp", fixed_logp, n_pol)):
+        _f32_vector(name, t, want)
+    if not (mean.is_cuda and mean.dtype == torch.float32 and mean.dim() == 2 and mean.stride(1) == 1 and (n_pol <= 1 or mean.stride(0) >= A)):
+        raise ValueError("mean must be (n_pol, act_dim) float32 on the HIP device with unit column stride")
+    if not (actions.is_cuda and actions.dtype == torch.float32 and actions.dim() == 2 and actions.stride(1) == 1 and actions.shape == (n, A)
+            and (n <= 1 or actions.stride(0) >= A)):
+        raise ValueError("actions must be (n, act_dim) float32 with unit column stride")
+    if not (log_std.is_cuda and log_std.dtype == torch.float32 and log_std.numel() == A):
+        raise ValueError("log_std must hold act_dim float32 values on the HIP device")
+    ls = log_std.reshape(-1).contiguous()
+    if rows is None and n_pol != n:
+        raise ValueError("without rows every sample is a policy row: mean must have one row per sample")
+    if rows is not None and not (rows.is_cuda and rows.dtype == torch.int64 and rows.is_contiguous() and rows.numel() == n_pol):
+        raise ValueError("rows must be a contiguous int64 tensor with one entry per policy row")
+    if logp_out is not None:
+        _f32_vector("logp_out", logp_out, n_pol)
+    F = len(L.PPO_STATS_FIELDS)
+    rec = out if out is not None else torch.empty(F, dtype=torch.float64, device=dev)
+    if not (rec.is_cuda and rec.dtype == torch.float64 and rec.is_contiguous() and rec.numel() == F):
+        raise ValueError("out must be a contiguous float64 HIP tensor of %d elements" % F)
+    ws = _zeroed_workspace("ppo_stats", lib.egp_ppo_stats_workspace_bytes(n, n_pol, A), dev)     # (per stream; every partial is written before it is read)
+    d = L.PpoStatsDesc()
+    d.n, d.n_pol, d.act_dim = n, n_pol, A
+    d.rows = rows.data_ptr() if rows is not None else None
+    d.pred, d.returns = pred1.data_ptr(), ret1.data_ptr()
+    d.mean, d.ld_mean = mean.data_ptr(), mean.stride(0) if n_pol > 1 else A
+    d.actions, d.ld_act = actions.data_ptr(), actions.stride(0) if n > 1 else A
+    d.log_std, d.adv, d.fixed_logp = ls.data_ptr(), adv1.data_ptr(), fixed_logp.data_ptr()
+    d.clip_eps = float(clip_eps)
+    d.logp_out = logp_out.data_ptr() if logp_out is not None else None
+    d.record, d.workspace = rec.data_ptr(), ws.data_ptr()
+    L.check(lib.egp_ppo_stats_f32(C.byref(d), L.current_stream()), "egp_ppo_stats_f32")
+    return rec
+
+
+def ppo_stats_torch(pred, returns, mean, actions, log_std, adv, fixed_logp, clip_eps, rows=None, out=None, logp_out=None, logp=None):
+    """`ppo_stats` in plain torch ops on any device and dtype: the record's definitions, and what the non-fused update path
+    evaluates. The log-probabilities come from `mean`, `actions[rows]` and `log_std` with the reference's formula
+    (core/distributions.py:6-25 over utils/math.py:14-17) in the inputs' dtype -- or are `logp` (n_pol,) / (n_pol, 1) when the
+    caller has them (then `mean` / `actions` may be None); the log-ratio is formed in that dtype, everything after it in float64.
+    -> float64[len(L.PPO_STATS_FIELDS)] on the inputs' device."""
+    with torch.no_grad():
+        pred1, ret1, adv1 = pred.reshape(-1), returns.reshape(-1), adv.reshape(-1)
+        ls = log_std.reshape(-1) if log_std is not None else None       # (None: a policy without a Gaussian head -- entropy NaN)
+        if logp is None:
+            act = actions if rows is None else actions[rows]
+            var = torch.exp(ls * 2.0)
+            logp = (-(act - mean).pow(2) / (2.0 * var) - 0.5 * math.log(2.0 * math.pi) - ls).sum(1)
+        logp = logp.reshape(-1)
+        if logp_out is not None:
+            logp_out.copy_(logp)
+        n, n_pol = pred1.shape[0], logp.shape[0]
+        lr = (logp - fixed_logp.reshape(-1)).double()
+        r = torch.exp(lr)
+        y, d = ret1.double(), ret1.double() - pred1.double()
+        bad = ~(torch.isfinite(pred1) & torch.isfinite(ret1))
+        pol_bad = ~(torch.isfinite(adv1 if rows is None else adv1[rows]) & torch.isfinite(logp))
+        if rows is None:
+            bad = bad | pol_bad
+        else:
+            bad = bad.index_put((rows,), pol_bad, accumulate=False) | bad
+        seen = r[~torch.isnan(r)]                       # (the kernel's fmin / fmax skip NaN ratios)
+        inf = torch.tensor(float("inf"), dtype=torch.float64, device=pred.device)
+        rec = torch.stack([
+            torch.tensor(float(n_pol), dtype=torch.float64, device=pred.device),
+            (-lr).sum(), (torch.expm1(lr) - lr).sum(), ((r - 1.0).abs() > float(clip_eps)).sum().double(),
+            seen.min() if seen.numel() else inf, seen.max() if seen.numel() else -inf,
+            torch.tensor(float(n), dtype=torch.float64, device=pred.device),
+            y.sum(), (y * y).sum(), d.sum(), (d * d).sum(), bad.sum().double(),
+            ls.double().sum() + 0.5 * ls.shape[0] * (1.0 + math.log(2.0 * math.pi)) if ls is not None else -inf * 0.0])
+        if out is not None:
+            out.copy_(rec)
+            return out
+        return rec
+
+
+def stats_summary(records):
+    """Host side of the update monitor: one record (13 numbers: a list, an array or a tensor) or the records of several ranks
+    (a sequence of them, or a 2-d tensor) -> dict of the derived figures. Ranks combine by adding the sums and counts and taking
+    the min / max of the ratio range (the entropy is every rank's own copy of the same number: the first is taken).
+      approx_kl (k3 mean), approx_kl_k1, clip_frac, ratio_min, ratio_max   over the policy rows
+      explained_var = 1 - Var(d) / Var(y), population variances of y = returns and d = returns - pred
+      entropy, nonfinite_rows
+    Means over zero rows are NaN."""
+    if torch.is_tensor(records):
+        records = records.detach().cpu().tolist()
+    rows = [list(map(float, records))] if len(records) and not hasattr(records[0], "__len__") else [list(map(float, r)) for r in records]
+    I = L.PPO_STATS
+    tot = lambda k: sum(r[I[k]] for r in rows)             # (rank order: every rank that combines the same records gets the same bits)
+    nan = float("nan")
+    n_pol, n = tot("n_pol"), tot("n")
+    mean_pol = lambda k: tot(k) / n_pol if n_pol > 0 else nan
+    if n > 0:
+        my, md = tot("sum_y") / n, tot("sum_d") / n
+        var_y, var_d = tot("sum_yy") / n - my * my, tot("sum_dd") / n - md * md
+        ev = 1.0 - var_d / var_y if var_y != 0 else nan
+    else:
+        ev = nan
+    return {"approx_kl": mean_pol("k3"), "approx_kl_k1": mean_pol("k1"), "clip_frac": mean_pol("clipped"),
+            "ratio_min": min(r[I["ratio_min"]] for r in rows), "ratio_max": max(r[I["ratio_max"]] for r in rows),
+            "explained_var": ev, "entropy": rows[0][I["entropy"]], "nonfinite_rows": int(tot("nonfinite"))}
+
+
+STATS_KEYS = ("approx_kl", "approx_kl_k1", "clip_frac", "ratio_min", "ratio_max", "explained_var", "entropy", "nonfinite_rows")
 
 
 def _f32_vector(name, t, want):

@@ -32,8 +32,10 @@ class Trainer:
     """Everything ego_mimic.py builds at module level, as one object."""
 
     def __init__(self, cfg, device, dtype=torch.float32, num_envs=1024, num_threads=None, num_groups=2, seed_offset=0,
-                 plain_optim=False, gail=None):
-        """`gail` (None, or a dict of AgentVGAIL keywords -- `expert_obs`, `discrim_reward_weight`, `discrim_num_update`,
+                 plain_optim=False, gail=None, monitor=None):
+        """`monitor` (None, or a dict of AgentPPO's update-monitor keywords -- `target_kl`, `update_diagnostics`,
+        `stop_on_nonfinite`): passed to the agent (`--target-kl`, `--diagnostics`, `--stop-on-nonfinite`).
+        `gail` (None, or a dict of AgentVGAIL keywords -- `expert_obs`, `discrim_reward_weight`, `discrim_num_update`,
         `discrim_grad_clip`; {} = the reference's behaviour): train a GAIL discriminator beside the PPO nets (`--gail`).
         `dtype=torch.float64` is the reference driver's set-up (ego_pose/ego_mimic.py:31-32): float64 modules and
         state_dicts; on a GPU the agent computes with float32 shadow copies (agent.ShadowNets). `plain_optim=True`
@@ -76,6 +78,7 @@ class Trainer:
         self.optimizer_policy = self._optimizer(cfg.policy_optimizer, policy_params, cfg.policy_lr, cfg.policy_momentum, cfg.policy_weightdecay)
         self.optimizer_value = self._optimizer(cfg.value_optimizer, value_params, cfg.value_lr, cfg.value_momentum, cfg.value_weightdecay)
         agent_cls, extra = AgentEgo, {}
+        self.monitor = monitor_keywords(monitor)
         if gail is not None:
             if self.forecast:
                 raise NotImplementedError("--gail goes with the ego_mimic task (the discriminator sees states through a VideoStateNet)")
@@ -97,7 +100,7 @@ class Trainer:
                                policy_net=self.policy_net, policy_vs_net=self.policy_vs_net, value_net=self.value_net,
                                value_vs_net=self.value_vs_net, optimizer_policy=self.optimizer_policy,
                                optimizer_value=self.optimizer_value, opt_num_epochs=cfg.num_optim_epoch, gamma=cfg.gamma,
-                               tau=cfg.tau, clip_epsilon=cfg.clip_epsilon, policy_grad_clip=[(policy_params, 40)], **extra)
+                               tau=cfg.tau, clip_epsilon=cfg.clip_epsilon, policy_grad_clip=[(policy_params, 40)], **self.monitor, **extra)
 
     def _optimizer(self, kind, params, lr, momentum, weight_decay):
         if kind == "Adam":
@@ -166,7 +169,41 @@ class Trainer:
         self.env.close()
 
 
-def main():
+MONITOR_KEYS = ("target_kl", "update_diagnostics", "stop_on_nonfinite")
+MONITOR_LOG = ("approx_kl", "clip_frac", "explained_var", "entropy")       # the last epoch's, on the log line and in the scalar summaries
+
+
+def monitor_keywords(monitor):
+    """Trainer's `monitor` argument -> the agent's keywords (unknown keys are an error, not silently dropped)."""
+    monitor = dict(monitor or {})
+    unknown = sorted(set(monitor) - set(MONITOR_KEYS))
+    if unknown:
+        raise ValueError("monitor: unknown keys %s (known: %s)" % (unknown, ", ".join(MONITOR_KEYS)))
+    return monitor
+
+
+def monitor_from_args(args):
+    """The three command-line flags -> Trainer's `monitor` (None when none of them is given)."""
+    m = {}
+    if args.target_kl is not None:
+        m["target_kl"] = args.target_kl
+    if args.diagnostics:
+        m["update_diagnostics"] = True
+    if args.stop_on_nonfinite:
+        m["stop_on_nonfinite"] = True
+    return m or None
+
+
+def monitor_log_fields(update_stats):
+    """[(name, value)] for the per-iteration log: the last epoch's figures and the number of epochs run -- [] without
+    diagnostics (or when the update stopped before its first step)."""
+    if "epochs_run" not in update_stats:
+        return []
+    out = [(k, update_stats[k][-1]) for k in MONITOR_LOG if update_stats.get(k)]
+    return out + [("epochs_run", update_stats["epochs_run"])]
+
+
+def build_parser():
     ap = argparse.ArgumentParser()
     ap.add_argument("--cfg", default="subject_03")
     ap.add_argument("--data", default=".", help="directory holding config/ and datasets/ (cwd of the reference)")
@@ -179,7 +216,14 @@ def main():
     ap.add_argument("--dtype", choices=["float32", "float64"], default="float32")
     ap.add_argument("--task", choices=["egomimic", "egoforecast"], default="egomimic")
     ap.add_argument("--gail", action="store_true", help="train a video-conditioned GAIL discriminator beside PPO (AgentVGAIL)")
-    args = ap.parse_args()
+    ap.add_argument("--target-kl", type=float, default=None, help="stop an update's epochs once the approximate KL to the sampling policy exceeds this")
+    ap.add_argument("--diagnostics", action="store_true", help="per-epoch update diagnostics (approx. KL, clip fraction, explained variance, entropy) in the log")
+    ap.add_argument("--stop-on-nonfinite", action="store_true", help="stop an update before any step when its inputs hold a NaN / inf")
+    return ap
+
+
+def main():
+    args = build_parser().parse_args()
     rank, world, local = D.init_from_env(args.gpu_index)
     gpu = local if args.gpu_index is None else args.gpu_index
     torch.cuda.set_device(gpu)
@@ -193,7 +237,7 @@ def main():
     cfg = (ForecastConfig if args.task == "egoforecast" else Config)(args.cfg, create_dirs=(rank == 0 and args.iter == 0))
     tr = Trainer(cfg, torch.device("cuda", gpu), getattr(torch, args.dtype), num_envs=args.num_envs,
                  num_threads=args.num_threads or None, seed_offset=rank,
-                 gail={} if args.gail else None)
+                 gail={} if args.gail else None, monitor=monitor_from_args(args))
     logger = create_logger(os.path.join(cfg.log_dir, "log.txt"), file_handle=rank == 0)
     tb = Logger(cfg.tb_dir) if rank == 0 else None
     if args.iter > 0:
@@ -210,9 +254,12 @@ def main():
         log, t_s, t_u, _ = tr.iteration(i_iter, cfg.min_batch_size)
         if rank == 0:
             c = log.avg_c_info
-            logger.info("%d\tT_sample %.2f\tT_update %.2f\tR_avg %.4f %s\tR_range (%.4f, %.4f)\teps_len_avg %.2f" % (
+            mon = monitor_log_fields(tr.agent.update_stats)
+            logger.info("%d\tT_sample %.2f\tT_update %.2f\tR_avg %.4f %s\tR_range (%.4f, %.4f)\teps_len_avg %.2f%s" % (
                 i_iter, t_s, t_u, log.avg_c_reward, np.array2string(c, formatter={"all": lambda x: "%.4f" % x}, separator=","),
-                log.min_c_reward, log.max_c_reward, log.avg_episode_reward))
+                log.min_c_reward, log.max_c_reward, log.avg_episode_reward, "".join("\t%s %.4g" % kv for kv in mon)))
+            for k, v in mon:
+                tb.scalar_summary(k, v, i_iter)
             tb.scalar_summary("total_reward", log.avg_c_reward, i_iter)
             tb.scalar_summary("episode_len", log.avg_episode_reward, i_iter)
             for k in range(c.shape[0]):

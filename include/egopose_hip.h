@@ -340,6 +340,54 @@ typedef struct egp_ppo_loss_desc {
 int64_t egp_ppo_loss_workspace_bytes(int32_t n, int32_t n_pol, int32_t act_dim);
 int egp_ppo_loss_f32(const egp_ppo_loss_desc *desc, void *stream);
 
+/* egp_ppo_stats_f32 -- the update monitor: one record of float64 figures about the tensors an epoch hands to egp_ppo_loss_f32
+ * (same meaning of n, n_pol, act_dim, rows, the strides and clip_eps; same limits: act_dim <= 256). Per policy row i: logp_i from the
+ * device function the loss kernel uses, lr_i = logp_i - fixed_logp_i in float32 (what the loss exponentiates), then float64 from
+ * (double)lr_i with r_i = exp(lr_i). Per value row: y = returns, d = returns - pred. The record holds RAW sums and counts (ranks
+ * combine by adding them and taking the min / max of the ratio range); record[k], k = EGP_PPO_STATS_*:
+ *     N_POL      number of policy rows                    K1         sum_i -lr_i          (k1 estimator of KL(old || new))
+ *     K3         sum_i expm1(lr_i) - lr_i  (k3, >= 0: for |lr| < 0.5 evaluated as lr^2 (1/2 + lr/6 + ...), no cancellation)
+ *     CLIPPED    #{i : |r_i - 1| > clip_eps}
+ *     RATIO_MIN  min_i r_i  (+inf without policy rows)    RATIO_MAX  max_i r_i  (-inf without policy rows; both skip NaN)
+ *     N          number of value rows                     SUM_Y, SUM_YY, SUM_D, SUM_DD   sums of y, y^2, d, d^2
+ *     NONFINITE  sample rows where pred, returns, or -- on policy rows only -- adv or logp is non-finite; such rows are counted,
+ *                not removed: the sums hold what IEEE arithmetic gives
+ *     ENTROPY    sum_j log_std_j + act_dim / 2 * log(2 pi e): the policy's entropy (state-independent standard deviation)
+ * logp_out (float32[n_pol], or NULL) receives logp_i. Sums are per-workgroup float64 partials added in a fixed order by a second
+ * launch: two identical calls give identical bits. log_std may be NULL only with n_pol == 0 (ENTROPY is then NaN). `workspace`:
+ * egp_ppo_stats_workspace_bytes bytes of device memory owned by the caller, no initial contents needed. */
+#define EGP_PPO_STATS_N_POL 0
+#define EGP_PPO_STATS_K1 1
+#define EGP_PPO_STATS_K3 2
+#define EGP_PPO_STATS_CLIPPED 3
+#define EGP_PPO_STATS_RATIO_MIN 4
+#define EGP_PPO_STATS_RATIO_MAX 5
+#define EGP_PPO_STATS_N 6
+#define EGP_PPO_STATS_SUM_Y 7
+#define EGP_PPO_STATS_SUM_YY 8
+#define EGP_PPO_STATS_SUM_D 9
+#define EGP_PPO_STATS_SUM_DD 10
+#define EGP_PPO_STATS_NONFINITE 11
+#define EGP_PPO_STATS_ENTROPY 12
+#define EGP_PPO_STATS_FIELDS 13
+struct egp_ppo_stats_desc {
+    int32_t n, n_pol, act_dim;
+    const int64_t *rows;
+    const float *pred; const float *returns;
+    const float *mean; int64_t ld_mean;
+    const float *actions; int64_t ld_act;
+    const float *log_std;
+    const float *adv;
+    const float *fixed_logp;
+    double clip_eps;
+    float *logp_out;
+    double *record;
+    void *workspace;
+};
+typedef struct egp_ppo_stats_desc egp_ppo_stats_desc;
+int64_t egp_ppo_stats_workspace_bytes(int32_t n, int32_t n_pol, int32_t act_dim);
+int egp_ppo_stats_f32(const egp_ppo_stats_desc *desc, void *stream);
+
 /* Mini-batch PPO (agents/agent_ppo.py:24-44): every epoch shuffles the batch and steps on windows of opt_batch_size rows.
  *
  * egp_minibatch_plan_f32 -- one launch per epoch: the six float32 columns of the update gathered through the epoch's
