@@ -84,9 +84,7 @@ int egp_launch_dynamics_strided(egp_ctx *ctx, const double *qpos, long ld_q, con
     else
         k_dynamics<4><<<dim3((n + 3) / 4), dim3(256), lds, stream>>>(tab, qpos, qvel, n, ld_q, ld_v, qM, ld_m, bias, ld_b, xpos, env_doubles,
                                                                      list, list_stride, qM_alt, bias_alt);
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) { egp::set_error("k_dynamics launch failed: %s", hipGetErrorString(e)); return EGP_E_HIP; }
-    return EGP_OK;
+    return after_launch("k_dynamics");
 }
 
 extern "C" {

@@ -19,15 +19,6 @@
 
 namespace {
 
-inline int after_launch(const char *what) {
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) {
-        egp::set_error("launch of %s failed: %s", what, hipGetErrorString(e));
-        return EGP_E_HIP;
-    }
-    return EGP_OK;
-}
-
 constexpr int ROWS_BLOCK = 256;
 constexpr int ROWS_MAX_BLOCKS = 2048;
 

@@ -36,15 +36,6 @@ typedef float f32x4u __attribute__((ext_vector_type(4), aligned(4)));       // 1
 typedef float f32x4 __attribute__((ext_vector_type(4)));
 typedef float f32x2 __attribute__((ext_vector_type(2)));
 
-inline int after_launch(const char *what) {
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) {
-        egp::set_error("launch of %s failed: %s", what, hipGetErrorString(e));
-        return EGP_E_HIP;
-    }
-    return EGP_OK;
-}
-
 constexpr int BM = 128, BK = 32;
 
 // tools/probes/gemm_trace.hip compiles this file with EGP_GEMM_TRACE: cycle stamps of one wave of one workgroup
@@ -639,22 +630,13 @@ __device__ __forceinline__ void split3_pair(float x0, float x1, unsigned &ph, un
 }
 
 // staged registers -> the three LDS images: v[8 u + j] = (row r_first + ROW_STEP u, k = 8 panel + j), one 16-byte store per image
-template <int R, int ROW_STEP, bool FAKE = false>
+template <int R, int ROW_STEP>
 __device__ __forceinline__ void ws_store(const float (&v)[R / 8], __bf16 *dst, int img, int panel, int r_first) {
 #pragma unroll
     for (int u = 0; u < R / 64; ++u) {
         unsigned q[3][4];
 #pragma unroll
-        for (int j = 0; j < 4; ++j) {
-            if constexpr (FAKE) {       // timing probe only (-DEGP_FAKE_SPLIT=1: B, 2: A and B; wrong numerics): what pre-split operands would
-                                        // save. Round 3, in-lease A/B/C (tools/probes/ab3.sh): B's conversion gone = T_update 50.8 -> 49.5 ms, i.e.
-                                        // keeping the weights as three bf16 planes is worth 1.3 ms -- not built
-                q[0][j] = __builtin_amdgcn_perm(__float_as_uint(v[8 * u + 2 * j + 1]), __float_as_uint(v[8 * u + 2 * j]), 0x07060302u);
-                q[1][j] = q[0][j] ^ 0x00010001u; q[2][j] = q[0][j] ^ 0x00020002u;
-            } else {
-                split3_pair(v[8 * u + 2 * j], v[8 * u + 2 * j + 1], q[0][j], q[1][j], q[2][j]);
-            }
-        }
+        for (int j = 0; j < 4; ++j) split3_pair(v[8 * u + 2 * j], v[8 * u + 2 * j + 1], q[0][j], q[1][j], q[2][j]);
         const int off = panel * panel_el(R) + (r_first + ROW_STEP * u) * 8;
 #pragma unroll
         for (int c = 0; c < 3; ++c) *(uint4 *)(dst + c * img + off) = make_uint4(q[c][0], q[c][1], q[c][2], q[c][3]);
@@ -767,9 +749,6 @@ __global__ __launch_bounds__(512) void k_gemm_ws(GemmArgs g) {
             zrel[SET] = kz - k0;
             fla[SET] = sa.flags();
             flb[SET] = sb.flags();
-#if defined(EGP_WS_SKIP) && EGP_WS_SKIP == 3      // timing probe: no operand loads at all (the staged registers hold whatever they held)
-            if (g.M < 0)
-#endif
             if constexpr (FUSED) {
                 const bool a_second = A_KC && g.A2 && k0 >= g.a_split;        // (a_split is a multiple of BK: a k-tile has one source)
                 sa.load(a_second ? g.A2 : g.A, a_second ? g.lda2 : g.lda, a_second ? k0 - g.a_split : k0, wave, ra[SET], a_second,
@@ -803,12 +782,9 @@ __global__ __launch_bounds__(512) void k_gemm_ws(GemmArgs g) {
                 ws_zero_head<BN>(vb, zrel[SET], pb_panel);
             }
             __bf16 *pa = base + buf * BUF_EL, *pb = pa + NIMG * A_EL;
-#ifndef EGP_FAKE_SPLIT
-#define EGP_FAKE_SPLIT 0
-#endif
-            ws_store<BM, SA::ROW_STEP, (EGP_FAKE_SPLIT >= 2)>(va, pa, A_EL, pa_panel, pa_row);
+            ws_store<BM, SA::ROW_STEP>(va, pa, A_EL, pa_panel, pa_row);
             EGP_TRW(1, 34);
-            ws_store<BN, SB::ROW_STEP, (EGP_FAKE_SPLIT >= 1)>(vb, pb, B_EL, pb_panel, pb_row);
+            ws_store<BN, SB::ROW_STEP>(vb, pb, B_EL, pb_panel, pb_row);
         };
         prefetch(); issue(S0); prefetch(); issue(S1); prefetch(); issue(S2); prefetch(); issue(S3);      // k-tiles 0..3 in flight
         prefetch();
@@ -819,10 +795,7 @@ __global__ __launch_bounds__(512) void k_gemm_ws(GemmArgs g) {
             EGP_TRW(1, 30);
             if (p + 1 < P) {
                 prefetch();
-#if !defined(EGP_WS_SKIP) || EGP_WS_SKIP != 2      // (timing probes, garbage numerics: 1 consumers idle, 3 no operand loads; 2 -- no staging --
-                                                   //  ends in a memory access fault since round 6, do not run it)
                 stage(setc, (p + 1) & 1);
-#endif
                 EGP_TRW(1, 31);
                 issue(setc);
             }
@@ -859,40 +832,17 @@ __global__ __launch_bounds__(512) void k_gemm_ws(GemmArgs g) {
         // every fragment of the k-tile is requested before the first MFMA (the matrix pipe then runs the 48 products
         // back to back instead of idling through an LDS round trip in the middle)
         bf16x8 fa[BK / 16][NIMG][MI], fb[BK / 16][NIMG][NJ];
-#ifndef EGP_GEMM_FRAG_ORDER
-#define EGP_GEMM_FRAG_ORDER 0
-#endif
-#define EGP_LD_FA(ks, c, i) fa[ks][c][i] = *(const bf16x8 *)(pa + (c) * A_EL + (2 * (ks) + fkh) * panel_el(BM) + (wm * WROWS + 32 * (i) + frow) * 8)
-#define EGP_LD_FB(ks, c, j) fb[ks][c][j] = *(const bf16x8 *)(pb + (c) * B_EL + (2 * (ks) + fkh) * panel_el(BN) + (wn * 64 + 32 * (j) + frow) * 8)
-#if EGP_GEMM_FRAG_ORDER
-        // the fragments in the order the products below consume them: the first MFMA waits for two reads, not for ten
-#pragma unroll
-        for (int ks = 0; ks < BK / 16; ++ks) {
-            constexpr int CB[3] = {0, 2, 1}, CA[3] = {2, 0, 1};
-#pragma unroll
-            for (int q = 0; q < 3; ++q) { EGP_LD_FB(ks, CB[q], 0); EGP_LD_FA(ks, CA[q], 0); }
-#pragma unroll
-            for (int j = 1; j < NJ; ++j)
-#pragma unroll
-                for (int q = 0; q < 3; ++q) EGP_LD_FB(ks, CB[q], j);
-#pragma unroll
-            for (int i = 1; i < MI; ++i)
-#pragma unroll
-                for (int q = 0; q < 3; ++q) EGP_LD_FA(ks, CA[q], i);
-        }
-#else
 #pragma unroll
         for (int ks = 0; ks < BK / 16; ++ks)
 #pragma unroll
             for (int c = 0; c < NIMG; ++c) {
 #pragma unroll
-                for (int i = 0; i < MI; ++i) EGP_LD_FA(ks, c, i);
+                for (int i = 0; i < MI; ++i)
+                    fa[ks][c][i] = *(const bf16x8 *)(pa + c * A_EL + (2 * ks + fkh) * panel_el(BM) + (wm * WROWS + 32 * i + frow) * 8);
 #pragma unroll
-                for (int j = 0; j < NJ; ++j) EGP_LD_FB(ks, c, j);
+                for (int j = 0; j < NJ; ++j)
+                    fb[ks][c][j] = *(const bf16x8 *)(pb + c * B_EL + (2 * ks + fkh) * panel_el(BN) + (wn * 64 + 32 * j + frow) * 8);
             }
-#endif
-#undef EGP_LD_FA
-#undef EGP_LD_FB
 #pragma unroll
         for (int ks = 0; ks < BK / 16; ++ks)
 #pragma unroll
@@ -1022,9 +972,7 @@ __global__ __launch_bounds__(512) void k_gemm_ws(GemmArgs g) {
     __syncthreads();
     for (int p = 0; p < P; ++p) {
         EGP_TRW(0, 40);
-#if !defined(EGP_WS_SKIP) || EGP_WS_SKIP != 1
         compute(p & 1);
-#endif
         EGP_TRW(0, 41);
         if (cur.s == cur.nst - 1) {
             epilogue();
@@ -1168,53 +1116,42 @@ __global__ __launch_bounds__(256) void k_scatter_rows(const float *__restrict__ 
     for (int j = threadIdx.x; j < H; j += 256) c[j] = d[j];
 }
 
+// One of a kernel's four instantiations over the operands' memory forms, launched; the first launch of each raises its dynamic
+// LDS limit. `kern`: the instantiations for (a_kc, b_kc) = (1, 1), (1, 0), (0, 1), (0, 0).
+using GemmKernel = void (*)(GemmArgs);
+int launch_form(const GemmArgs &g, const GemmKernel (&kern)[4], bool (&attr_set)[4], dim3 grid, dim3 block, size_t lds, hipStream_t s,
+                const char *name) {
+    const int f = (g.a_kc ? 0 : 2) + (g.b_kc ? 0 : 1);
+    if (!attr_set[f]) {
+        EGP_HIP_CHECK(hipFuncSetAttribute((const void *)kern[f], hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
+        attr_set[f] = true;
+    }
+    kern[f]<<<grid, block, lds, s>>>(g);
+    return after_launch(name);
+}
+
 template <int BN, int TERMS>
 int launch_variant(const GemmArgs &g, dim3 grid, size_t lds, hipStream_t s) {
-#define EGP_GEMM_LAUNCH(AK, BKC)                                                                                      \
-    do {                                                                                                              \
-        auto kern = k_gemm_bf16x<BN, TERMS, AK, BKC>;                                                                 \
-        static bool attr_set = false;                                                                                 \
-        if (!attr_set) {                                                                                              \
-            EGP_HIP_CHECK(hipFuncSetAttribute((const void *)kern, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024)); \
-            attr_set = true;                                                                                          \
-        }                                                                                                             \
-        kern<<<grid, dim3(256), lds, s>>>(g);                                                                         \
-    } while (0)
-    if (g.a_kc && g.b_kc) EGP_GEMM_LAUNCH(true, true);
-    else if (g.a_kc && !g.b_kc) EGP_GEMM_LAUNCH(true, false);
-    else if (!g.a_kc && g.b_kc) EGP_GEMM_LAUNCH(false, true);
-    else EGP_GEMM_LAUNCH(false, false);
-#undef EGP_GEMM_LAUNCH
-    return after_launch("k_gemm_bf16x");
+    static const GemmKernel kern[4] = {k_gemm_bf16x<BN, TERMS, true, true>, k_gemm_bf16x<BN, TERMS, true, false>,
+                                       k_gemm_bf16x<BN, TERMS, false, true>, k_gemm_bf16x<BN, TERMS, false, false>};
+    static bool attr_set[4];
+    return launch_form(g, kern, attr_set, grid, dim3(256), lds, s, "k_gemm_bf16x");
 }
 
 template <int BN, bool FUSED>
 int launch_ws(const GemmArgs &g, hipStream_t s) {
-    static int n_cu = 0;                        // one persistent workgroup per CU the process really gets (egp_device_usable_cus: under a
-    if (!n_cu) {                                // CU mask the attribute over-reports, and the workgroups without a CU would be a second round)
-        int dev = 0;
-        EGP_HIP_CHECK(hipGetDevice(&dev));
-        n_cu = egp_device_usable_cus(dev);
-        if (n_cu <= 0) EGP_HIP_CHECK(hipDeviceGetAttribute(&n_cu, hipDeviceAttributeMultiprocessorCount, dev));
-    }
+    // one persistent workgroup per CU the process really gets (egp_device_usable_cus, cached per device: under a CU mask the
+    // attribute over-reports, and the workgroups without a CU would be a second round)
+    int dev = 0, n_cu = 0;
+    EGP_HIP_CHECK(hipGetDevice(&dev));
+    n_cu = egp_device_usable_cus(dev);
+    if (n_cu <= 0) EGP_HIP_CHECK(hipDeviceGetAttribute(&n_cu, hipDeviceAttributeMultiprocessorCount, dev));
     const size_t lds = (size_t)2 * 3 * (tile_el(BM) + tile_el(BN)) * sizeof(__bf16) + 4 * 32 * (64 + 4) * sizeof(float);   // + the epilogue patches
     const dim3 grid((unsigned)(g.n_items < n_cu ? g.n_items : n_cu));
-#define EGP_GEMM_WS_LAUNCH(AK, BKC)                                                                                   \
-    do {                                                                                                              \
-        auto kern = k_gemm_ws<BN, AK, BKC, FUSED>;                                                                    \
-        static bool attr_set = false;                                                                                 \
-        if (!attr_set) {                                                                                              \
-            EGP_HIP_CHECK(hipFuncSetAttribute((const void *)kern, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024)); \
-            attr_set = true;                                                                                          \
-        }                                                                                                             \
-        kern<<<grid, dim3(512), lds, s>>>(g);                                                                         \
-    } while (0)
-    if (g.a_kc && g.b_kc) EGP_GEMM_WS_LAUNCH(true, true);
-    else if (g.a_kc && !g.b_kc) EGP_GEMM_WS_LAUNCH(true, false);
-    else if (!g.a_kc && g.b_kc) EGP_GEMM_WS_LAUNCH(false, true);
-    else EGP_GEMM_WS_LAUNCH(false, false);
-#undef EGP_GEMM_WS_LAUNCH
-    return after_launch("k_gemm_ws");
+    static const GemmKernel kern[4] = {k_gemm_ws<BN, true, true, FUSED>, k_gemm_ws<BN, true, false, FUSED>,
+                                       k_gemm_ws<BN, false, true, FUSED>, k_gemm_ws<BN, false, false, FUSED>};
+    static bool attr_set[4];
+    return launch_form(g, kern, attr_set, grid, dim3(512), lds, s, "k_gemm_ws");
 }
 
 }  // namespace

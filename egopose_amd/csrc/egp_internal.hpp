@@ -27,6 +27,20 @@ void set_error(const char *fmt, ...);
         }                                            \
     } while (0)
 
+}  // namespace egp
+
+// after a kernel launch: the launch's error, if any, as the library's error string and code
+inline int after_launch(const char *what) {
+    hipError_t e = hipGetLastError();
+    if (e != hipSuccess) {
+        egp::set_error("launch of %s failed: %s", what, hipGetErrorString(e));
+        return EGP_E_HIP;
+    }
+    return EGP_OK;
+}
+
+namespace egp {
+
 // Reward coefficients, passed to the kernel by value (SGPR-resident).
 struct RewardW {
     double w_p, w_v, w_e, w_rp, w_rv, w_sum;

@@ -2190,15 +2190,6 @@ int egp_upload_experts(egp_ctx *ctx, const egp_expert_table *t) {
 }  // extern "C"
 
 // ---------------------------------------------------------------------------------------- launchers
-static inline int after_launch(const char *what) {
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) {
-        set_error("launch of %s failed: %s", what, hipGetErrorString(e));
-        return EGP_E_HIP;
-    }
-    return EGP_OK;
-}
-
 template <typename T>
 static int launch_body_quat(egp_ctx *ctx, const T *qpos, int n, T *bquat, void *stream) {
     EGP_REQUIRE(ctx, "ctx is NULL");

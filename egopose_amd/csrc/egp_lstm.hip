@@ -53,20 +53,11 @@ typedef float f32x4 __attribute__((ext_vector_type(4)));
 
 // The save-set (activated gates, cell states: written once by the forward sweep, read once by the backward sweep a few
 // milliseconds later, 1.3 GB per grouped sweep of the update) and d_pre go past the caches with the non-temporal hint
-// (EGP_LSTM_NT bit 0: save-set stores and loads, bit 1: d_pre stores; default both. A/B/C inside one lease, tools/probes/abn.sh +
-// update_time.py, three rounds: T_update 44.85 / 44.55 / 44.84 ms without, 44.29 / 45.17 / 44.86 with bit 0, 44.04 / 44.31 / 44.56 with both.)
-#ifndef EGP_LSTM_NT
-#define EGP_LSTM_NT 3
-#endif
-template <typename V> __device__ __forceinline__ void st_save(V *p, V v) {
-    if constexpr ((EGP_LSTM_NT & 1) != 0) __builtin_nontemporal_store(v, p); else *p = v;
-}
-template <typename V> __device__ __forceinline__ V ld_save(const V *p) {
-    if constexpr ((EGP_LSTM_NT & 1) != 0) return __builtin_nontemporal_load(p); else return *p;
-}
-template <typename V> __device__ __forceinline__ void st_dpre(V *p, V v) {
-    if constexpr ((EGP_LSTM_NT & 2) != 0) __builtin_nontemporal_store(v, p); else *p = v;
-}
+// (A/B/C inside one lease, tools/probes/abn.sh + update_time.py, three rounds: T_update 44.85 / 44.55 / 44.84 ms with plain accesses,
+// 44.29 / 45.17 / 44.86 with the hint on the save-set alone, 44.04 / 44.31 / 44.56 with it on both.)
+template <typename V> __device__ __forceinline__ void st_save(V *p, V v) { __builtin_nontemporal_store(v, p); }
+template <typename V> __device__ __forceinline__ V ld_save(const V *p) { return __builtin_nontemporal_load(p); }
+template <typename V> __device__ __forceinline__ void st_dpre(V *p, V v) { __builtin_nontemporal_store(v, p); }
 
 // Several sweeps over the same (T, B) in one launch (blockIdx.y = problem): the directions of a bi-LSTM, or the LSTMs of
 // the critic's and the actor's video nets -- a sweep is latency-bound and 320 workgroups leave 64 CUs with double
@@ -128,18 +119,6 @@ __device__ long long g_lstm_trace[8];
 #define EGP_LT(i) do { } while (0)
 #define EGP_LT_END(steps) do { } while (0)
 #endif
-#ifndef EGP_LSTM_PD1
-#define EGP_LSTM_PD1 (NQ == 1 ? 4 : 4)
-#endif
-#ifndef EGP_LSTM_KCH
-#define EGP_LSTM_KCH (NQ == 1 && LH == 64 ? 32 : 64)
-#endif
-#ifndef EGP_LSTM_BPD
-#define EGP_LSTM_BPD ((NQ == 1 && LH == 64) ? 4 : 2)
-#endif
-#ifndef EGP_LSTM_BKCH
-#define EGP_LSTM_BKCH 64
-#endif
 // STORE = what a step leaves in memory. LSTM_ST_STEP: h_out at every step (inference). LSTM_ST_TRAIN: h_out and the save-set
 // (activated gates, cell states). LSTM_ST_LAST: nothing per step -- only the hidden state after the last step, one row per
 // sequence at h_out + b * ld_h (egp_lstm_desc.last_only: inference over windows of a frame table). The step itself is the same
@@ -160,7 +139,9 @@ __global__ __launch_bounds__(4 * LH) void k_lstm_fwd_mfma(const float *__restric
     float *__restrict__ h_out = grp.h[prob];
     gx += prob * LG; w_hh += (long)prob * LG * LH;
     if (TRAIN) { gates_out += prob * LG; c_out += prob * grp.c_stride; }
-    constexpr int PD = LH == 128 ? 2 : EGP_LSTM_PD1;   // steps per unrolled iteration = input-projection tiles in flight (even)
+    // steps per unrolled iteration = input-projection tiles in flight (even). Hidden 64, four rows: 4 in place of 8, with the hidden
+    // tile read in two halves (KCH below), is 220 -> 160 VGPRs = three workgroups per CU, -2 % per sweep
+    constexpr int PD = LH == 128 ? 2 : 4;
     __shared__ __attribute__((aligned(16))) float s_h[2][ROWS][LH + 4];     // +4: the 4 rows of a read hit distinct banks
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const int u = 16 * wave + (lane >> 2), sub = lane & 3;                   // sub = gate index as A, row-in-quad as B / D
@@ -205,7 +186,7 @@ __global__ __launch_bounds__(4 * LH) void k_lstm_fwd_mfma(const float *__restric
         f32x4 acc[NQ], acc2[NQ];
 #pragma unroll
         for (int q = 0; q < NQ; ++q) { acc[q] = init[q]; acc2[q] = f32x4{0.f, 0.f, 0.f, 0.f}; }
-        constexpr int KCH = EGP_LSTM_KCH;
+        constexpr int KCH = NQ == 1 && LH == 64 ? 32 : 64;
 #pragma unroll
         for (int kc = 0; kc < LH; kc += KCH) {
             float4 hv[NQ][KCH / 4];
@@ -309,7 +290,10 @@ __global__ __launch_bounds__(4 * LH) void k_lstm_bwd_mfma(const float *__restric
     const float *__restrict__ dh_out = grp.dh[prob];
     gates += prob * LG; dpre += prob * LG; cells += prob * grp.c_stride; w_hh += (long)prob * LG * LH;
     constexpr int NP = (ROWS * LH + NT - 1) / NT;     // = NQ: (row, unit) pairs per thread in the pointwise phase
-    constexpr int PD = EGP_LSTM_BPD;   // steps per unrolled iteration = operand sets in flight
+    constexpr int PD = NQ == 1 && LH == 64 ? 4 : 2;   // steps per unrolled iteration = operand sets in flight
+    // d-gate columns per register chunk: 64 (32 with PD = 2 gives three workgroups per CU, 224 -> 164 VGPRs: 0.577 against 0.555 ms per
+    // sweep, no better)
+    constexpr int BKCH = 64;
     __shared__ __attribute__((aligned(16))) float s_d[ROWS][LG + 4];     // d-gates of the step, [row][unit][gate]
     __shared__ float s_part[4][ROWS][LH + 1];
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
@@ -384,15 +368,15 @@ __global__ __launch_bounds__(4 * LH) void k_lstm_bwd_mfma(const float *__restric
 #pragma unroll
         for (int qd = 0; qd < NQ; ++qd) acc[qd] = acc2[qd] = f32x4{0.f, 0.f, 0.f, 0.f};
 #pragma unroll
-        for (int kc = 0; kc < LH; kc += EGP_LSTM_BKCH) {
-            float4 dv[NQ][EGP_LSTM_BKCH / 4];
+        for (int kc = 0; kc < LH; kc += BKCH) {
+            float4 dv[NQ][BKCH / 4];
 #pragma unroll
             for (int qd = 0; qd < NQ; ++qd)
 #pragma unroll
-                for (int c4 = 0; c4 < EGP_LSTM_BKCH / 4; ++c4) dv[qd][c4] = *reinterpret_cast<const float4 *>(&s_d[4 * qd + sub][q * LH + kc + 4 * c4]);
+                for (int c4 = 0; c4 < BKCH / 4; ++c4) dv[qd][c4] = *reinterpret_cast<const float4 *>(&s_d[4 * qd + sub][q * LH + kc + 4 * c4]);
             __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
-            for (int c4 = 0; c4 < EGP_LSTM_BKCH / 4; ++c4)
+            for (int c4 = 0; c4 < BKCH / 4; ++c4)
 #pragma unroll
                 for (int qd = 0; qd < NQ; ++qd) {
                     acc[qd] = __builtin_amdgcn_mfma_f32_4x4x1f32(w[kc + 4 * c4 + 0], dv[qd][c4].x, acc[qd], 0, 0, 0);
@@ -476,15 +460,6 @@ using namespace egp;
 // latencies overlap)
 static int lstm_quads(int B) { return B >= 4096 ? 2 : 1; }
 
-static int lstm_launch_check(const char *what) {
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) {
-        set_error("launch of %s failed: %s", what, hipGetErrorString(e));
-        return EGP_E_HIP;
-    }
-    return EGP_OK;
-}
-
 template <int NQ, int LH>
 static void launch_fwd_mfma_t(bool full, bool train, bool last, int P, const float *gx, const float *w_hh, int T, int B, const LstmGroup &g,
                               float *gates_save, float *cells_save, hipStream_t s) {
@@ -566,7 +541,7 @@ static int lstm_sweep(const egp_lstm_desc *d, bool bwd, void *stream) {
         g.seq_base = d->seq_base;
         launch_fwd_mfma(H, P, d->gates_x, d->w_hh, T, B, g, d->gates_save, d->cells_save, (hipStream_t)stream, last);
     }
-    return lstm_launch_check(bwd ? "k_lstm_bwd_mfma" : "k_lstm_fwd_mfma");
+    return after_launch(bwd ? "k_lstm_bwd_mfma" : "k_lstm_fwd_mfma");
 }
 
 extern "C" {

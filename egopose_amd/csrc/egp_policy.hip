@@ -791,9 +791,7 @@ extern "C" int egp_mlp_pack_f32(const float *weight, int64_t ldw, int32_t in_dim
     const int threads = 256;
     const long blocks = (total + threads - 1) / threads;
     k_mlp_pack<<<dim3((unsigned)(blocks < 4096 ? blocks : 4096)), dim3(threads), 0, (hipStream_t)stream>>>(weight, (long)ldw, in_dim, out_dim, packed, total);
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) { egp::set_error("k_mlp_pack launch failed: %s", hipGetErrorString(e)); return EGP_E_HIP; }
-    return EGP_OK;
+    return after_launch("k_mlp_pack");
 }
 
 // The kernels' layer table from `front` (optional: the forecast step's cell) and layers[0 .. n_layers), validated. `in0`: width of
@@ -834,12 +832,6 @@ static int pol_lds(const PolLayers &L, int kmax, int cell_floats, int ms_doubles
     *xs = ((kmax + 31) & ~31) + 4;                    // rows 0..3 of a broadcast read sit on different banks
     *lds = (size_t)pol_carve<POL_R, POL_NW>(*xs, L.sum_out4, L.out_dim[L.n - 1], cell_floats, ms_doubles).end * sizeof(float);
     EGP_REQUIRE(*lds <= 150 * 1024, "layers too wide for the LDS tile");
-    return EGP_OK;
-}
-
-static int pol_launched(const char *what) {
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) { egp::set_error("%s launch failed: %s", what, hipGetErrorString(e)); return EGP_E_HIP; }
     return EGP_OK;
 }
 
@@ -916,12 +908,12 @@ extern "C" int egp_policy_step_f32(const egp_policy_desc *d, void *stream) {
         POL_GO(k_policy_gaussian_w4, d->ctx_rows, (long)d->ctx_row_stride, ctx_dim, t_idx, d->state, state_dim, n, L, d->activation, xs, d->log_std,
                d->noise, d->action, d->mean_out, d->stage_bytes ? (const unsigned *)d->stage_src : nullptr, (unsigned *)d->stage_dst,
                (int)(d->stage_bytes / 4), F);
-        return pol_launched("k_policy_gaussian");
+        return after_launch("k_policy_gaussian");
     }
     if (cell) {
         POL_GO(k_policy_forecast_w4, d->ctx_rows, (long)d->ctx_row_stride, ctx_dim, t_idx, d->state, state_dim, d->h, d->c, (long)d->hc_row_stride, hs, n,
                L, d->activation, xs, d->log_std, d->noise, d->action, d->mean_out, F);
-        return pol_launched("k_policy_forecast");
+        return after_launch("k_policy_forecast");
     }
     // the critic's own layer table and carve-up; the launch's dynamic LDS is the larger of the two
     EGP_REQUIRE(d->n_vlayers >= 1 && d->n_vlayers <= POL_MAX_LAYERS, "1..8 layers per net (hidden layers + output layer)");
@@ -938,5 +930,5 @@ extern "C" int egp_policy_step_f32(const egp_policy_desc *d, void *stream) {
     grid.y = 2;
     POL_GO(k_policy_value_w4, P, t_idx, d->state, state_dim, n, d->log_std, d->noise, d->action, d->mean_out, d->value_out, F);
 #undef POL_GO
-    return pol_launched("k_policy_value");
+    return after_launch("k_policy_value");
 }

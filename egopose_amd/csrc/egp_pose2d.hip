@@ -145,9 +145,7 @@ int egp_pose2d_f64(egp_ctx *ctx, const double *qpos, const double *gt, const int
     kp.l_hip_body = kp.body[kp.l_upleg]; kp.r_hip_body = kp.body[kp.r_upleg];
     k_pose2d<<<dim3((unsigned)((n + P2_WAVES - 1) / P2_WAVES)), dim3(P2_WAVES * 64), lds, (hipStream_t)stream>>>(
         (const DynTables *)ctx->dyn_tables, kp, qpos, (long)ctx->dm.nq, gt, flip, p_out, dist, valid, (long)n, fk_doubles);
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) { egp::set_error("k_pose2d launch failed: %s", hipGetErrorString(e)); return EGP_E_HIP; }
-    return EGP_OK;
+    return after_launch("k_pose2d");
 }
 
 }  // extern "C"

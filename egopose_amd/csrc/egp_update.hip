@@ -22,15 +22,6 @@
 
 namespace {
 
-inline int after_launch(const char *what) {
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) {
-        egp::set_error("launch of %s failed: %s", what, hipGetErrorString(e));
-        return EGP_E_HIP;
-    }
-    return EGP_OK;
-}
-
 constexpr int LOSS_BLOCK = 256;
 constexpr int LOSS_GROUP = 16;                 // lanes per policy row
 constexpr int LOSS_MAX_BLOCKS = 1024;

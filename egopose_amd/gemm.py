@@ -222,6 +222,33 @@ def linear_wgrad(dy, x, want_bias=True, terms=None):
     return gemm(dy, x, False, False, terms=terms, splits=pick_splits(M, n_out, K), want_bias_grad=want_bias)
 
 
+def ws_enabled():
+    """The persistent three-piece kernel takes the products it can (the library's switch; off: k_gemm_bf16x for everything). Read
+    per call, as the library does: tests switch it."""
+    return os.environ.get("EGP_GEMM_WS", "1") != "0"
+
+
+def _layers_above_fwd(h, Ws, bs, act):
+    """Layers 1 .. of head(MLP(.)) on the first layer's output h -> [h, h_2, ..., out]."""
+    hs = [h]
+    for i in range(1, len(Ws)):
+        hs.append(linear_fwd(hs[-1], Ws[i].contiguous(), bs[i], act=act if i < len(Ws) - 1 else None))
+    return hs
+
+
+def _layers_above_bwd(dz, hs, Ws, act, needs):
+    """The backward pass down to the first layer's output: hs[i - 1] = activation output feeding layer i, needs[2 i], needs[2 i + 1] =
+    whether W_i, b_i want a gradient. Returns (dz of the first layer's output, [dW_0, db_0, dW_1, ...] with layer 0's still None)."""
+    grads = [None] * (2 * len(Ws))
+    for i in range(len(Ws) - 1, 0, -1):
+        need_w, need_b = needs[2 * i], needs[2 * i + 1]
+        if need_w or need_b:
+            dW, db = linear_wgrad(dz, hs[i - 1], want_bias=True)
+            grads[2 * i], grads[2 * i + 1] = (dW if need_w else None), (db if need_b else None)
+        dz = linear_dgrad(dz, Ws[i].contiguous(), mask=hs[i - 1], act=act)
+    return dz, grads
+
+
 class MlpHead(torch.autograd.Function):
     """out = head(MLP(x)): apply(x, n_grad_cols, act, W1, b1, ..., Wh, bh), `act` the hidden layers' activation ("relu",
     "tanh" or "sigmoid"). Gradient w.r.t. x only for its first n_grad_cols columns (the video context; the state columns of
@@ -230,35 +257,30 @@ class MlpHead(torch.autograd.Function):
     @staticmethod
     def forward(ctx, x, n_grad_cols, act, *params):
         Ws, bs = params[0::2], params[1::2]
-        hs = [x.contiguous()]
-        for i, (W, b) in enumerate(zip(Ws, bs)):
-            hs.append(linear_fwd(hs[-1], W.contiguous(), b, act=act if i < len(Ws) - 1 else None))
-        ctx.save_for_backward(*hs[:-1], *Ws)
+        x = x.contiguous()
+        hs = _layers_above_fwd(linear_fwd(x, Ws[0].contiguous(), bs[0], act=act if len(Ws) > 1 else None), Ws, bs, act)
+        ctx.save_for_backward(x, *hs[:-1], *Ws)
         ctx.n_layers, ctx.n_grad_cols, ctx.act = len(Ws), int(n_grad_cols), act
         return hs[-1]
 
     @staticmethod
     def backward(ctx, dout):
         nl = ctx.n_layers
-        hs, Ws = ctx.saved_tensors[:nl], ctx.saved_tensors[nl:]
-        dz = dout.contiguous()
-        grads = [None] * (2 * nl)
+        x, hs, Ws = ctx.saved_tensors[0], ctx.saved_tensors[1:nl], ctx.saved_tensors[nl:]
+        need = ctx.needs_input_grad
+        dz, grads = _layers_above_bwd(dout.contiguous(), hs, Ws, ctx.act, need[3:])
+        if need[3] or need[4]:
+            dW, db = linear_wgrad(dz, x, want_bias=True)
+            grads[0], grads[1] = (dW if need[3] else None), (db if need[4] else None)
         dx = None
-        for i in range(nl - 1, -1, -1):
-            need_w, need_b = ctx.needs_input_grad[3 + 2 * i], ctx.needs_input_grad[4 + 2 * i]
-            if need_w or need_b:
-                dW, db = linear_wgrad(dz, hs[i], want_bias=True)
-                grads[2 * i], grads[2 * i + 1] = (dW if need_w else None), (db if need_b else None)
-            if i > 0:
-                dz = linear_dgrad(dz, Ws[i].contiguous(), mask=hs[i], act=ctx.act)         # hs[i] = activation output feeding layer i
-            elif ctx.needs_input_grad[0]:
-                nc = ctx.n_grad_cols
-                W0 = Ws[0].contiguous()
-                if nc >= W0.shape[1]:
-                    dx = linear_dgrad(dz, W0)
-                else:
-                    dx = torch.zeros(dz.shape[0], W0.shape[1], dtype=dz.dtype, device=dz.device)
-                    gemm(dz, W0[:, :nc], True, False, out=dx[:, :nc])
+        if need[0]:
+            nc = ctx.n_grad_cols
+            W0 = Ws[0].contiguous()
+            if nc >= W0.shape[1]:
+                dx = linear_dgrad(dz, W0)
+            else:
+                dx = torch.zeros(dz.shape[0], W0.shape[1], dtype=dz.dtype, device=dz.device)
+                gemm(dz, W0[:, :nc], True, False, out=dx[:, :nc])
         return (dx, None, None, *grads)
 
 
@@ -307,15 +329,12 @@ def fused_gather_available(H, n_hidden, S):
     """The first MLP layer can read [ctx[idx] | state] itself: three-piece products on the persistent kernel, the context
     width H a multiple of the 128-column tile (the weight gradient switches source between column tiles), at least one
     k-tile of state columns S (a k-tile reads one source)."""
-    import os
-    return enabled() and default_terms() == 6 and os.environ.get("EGP_GEMM_WS", "1") != "0" and H % 128 == 0 and n_hidden % 4 == 0 \
-        and S >= 32
+    return fused_rows_available() and H % 128 == 0 and n_hidden % 4 == 0 and S >= 32
 
 
 def fused_rows_available():
     """Row / k-row index operands (a_rows, c_rows, a_krows, b_krows) need three-piece products on the persistent kernel."""
-    import os
-    return enabled() and default_terms() == 6 and os.environ.get("EGP_GEMM_WS", "1") != "0"
+    return enabled() and default_terms() == 6 and ws_enabled()
 
 
 class GatherMlpHead(torch.autograd.Function):
@@ -330,9 +349,7 @@ class GatherMlpHead(torch.autograd.Function):
         Ws, bs = params[0::2], params[1::2]
         ctx2d, x = ctx2d.contiguous(), (x if x.stride(1) == 1 else x.contiguous())
         h = gemm(ctx2d, Ws[0].contiguous(), True, True, bias=bs[0], act=act if len(Ws) > 1 else None, a_rows=idx, a2=x)
-        hs = [h]
-        for i in range(1, len(Ws)):
-            hs.append(linear_fwd(hs[-1], Ws[i].contiguous(), bs[i], act=act if i < len(Ws) - 1 else None))
+        hs = _layers_above_fwd(h, Ws, bs, act)
         ctx.save_for_backward(ctx2d, idx, x, *hs[:-1], *Ws)
         ctx.n_layers, ctx.act = len(Ws), act
         return hs[-1]
@@ -341,15 +358,8 @@ class GatherMlpHead(torch.autograd.Function):
     def backward(ctx, dout):
         nl = ctx.n_layers
         ctx2d, idx, x = ctx.saved_tensors[:3]
-        hs, Ws = ctx.saved_tensors[3:3 + nl - 1], ctx.saved_tensors[3 + nl - 1:]        # hs[i - 1] = activation output feeding layer i
-        dz = dout.contiguous()
-        grads = [None] * (2 * nl)
-        for i in range(nl - 1, 0, -1):
-            need_w, need_b = ctx.needs_input_grad[4 + 2 * i], ctx.needs_input_grad[5 + 2 * i]
-            if need_w or need_b:
-                dW, db = linear_wgrad(dz, hs[i - 1], want_bias=True)
-                grads[2 * i], grads[2 * i + 1] = (dW if need_w else None), (db if need_b else None)
-            dz = linear_dgrad(dz, Ws[i].contiguous(), mask=hs[i - 1], act=ctx.act)
+        hs, Ws = ctx.saved_tensors[3:3 + nl - 1], ctx.saved_tensors[3 + nl - 1:]
+        dz, grads = _layers_above_bwd(dout.contiguous(), hs, Ws, ctx.act, ctx.needs_input_grad[4:])
         H, S = ctx2d.shape[1], x.shape[1]
         if ctx.needs_input_grad[4] or ctx.needs_input_grad[5]:
             n = dz.shape[0]

@@ -81,6 +81,22 @@ class MLP(nn.Module):
         return x
 
 
+def mlp_head(net, head, x):
+    """head(net(x)) for an MLP trunk `net` and an nn.Linear `head`. x: a tensor, or a gemm.GatheredInput ([context | state] not formed)."""
+    if _gemm.mlp_head_available(x, getattr(net, "affine_layers", ()), head, getattr(net, "activation", None)):
+        # the whole head(MLP(x)) as one autograd node on the split-operand bf16 GEMM kernel (gemm.py)
+        if isinstance(x, _gemm.GatheredInput):      # the first layer gathers [context | state] itself
+            return _gemm.gather_mlp_head(x, net.affine_layers, head, net.activation)
+        # `_egp_ctx_cols` (a tag VideoStateNet.forward leaves on the tensor it returns, not a module attribute): only the leading
+        # video-context columns of that input carry a gradient -- any other input gets the full gradient
+        return _gemm.mlp_head(x, net.affine_layers, head, getattr(x, "_egp_ctx_cols", None), net.activation)
+    if isinstance(x, _gemm.GatheredInput):
+        x = x.materialize()
+    x, n = bucket_rows(x)
+    out = head(net(x))
+    return out if n is None else out[:n]
+
+
 class _DiagLogProb(torch.autograd.Function):
     """sum_j log N(value_j; loc_j, exp(log_std_j)) per row (core/distributions.py: normal_log_density + sum(1, keepdim)) in four
     full-size element-wise kernels forward and two backward (torch.distributions.Normal.log_prob takes about eight each way,
@@ -156,22 +172,7 @@ class PolicyGaussian(Policy):
         self.action_log_std = nn.Parameter(torch.full((1, action_dim), float(log_std)), requires_grad=not fix_std)
 
     def mean_std(self, x):
-        if _gemm.mlp_head_available(x, getattr(self.net, "affine_layers", ()), self.action_mean, getattr(self.net, "activation", None)):
-            # the whole head(MLP(x)) as one autograd node on the split-operand bf16 GEMM kernel (gemm.py); `_egp_ctx_cols`
-            # (a tag VideoStateNet.forward leaves on the tensor it returns, not a module attribute): only the leading
-            # video-context columns of that input carry a gradient -- any other input gets the full gradient
-            # (set by the agent): only the leading video-context columns of the input carry a gradient
-            if isinstance(x, _gemm.GatheredInput):      # [context | state] never formed: the first layer gathers it itself
-                mean = _gemm.gather_mlp_head(x, self.net.affine_layers, self.action_mean, self.net.activation)
-            else:
-                mean = _gemm.mlp_head(x, self.net.affine_layers, self.action_mean, getattr(x, "_egp_ctx_cols", None), self.net.activation)
-        else:
-            if isinstance(x, _gemm.GatheredInput):
-                x = x.materialize()
-            x, n = bucket_rows(x)
-            mean = self.action_mean(self.net(x))
-            if n is not None:
-                mean = mean[:n]
+        mean = mlp_head(self.net, self.action_mean, x)
         return mean, torch.exp(self.action_log_std).expand_as(mean)         # (a view: no (n, d) tensor of standard deviations)
 
     def forward(self, x):
@@ -199,15 +200,7 @@ class Value(nn.Module):
             self.value_head.bias.zero_()
 
     def forward(self, x):
-        if _gemm.mlp_head_available(x, getattr(self.net, "affine_layers", ()), self.value_head, getattr(self.net, "activation", None)):
-            if isinstance(x, _gemm.GatheredInput):
-                return _gemm.gather_mlp_head(x, self.net.affine_layers, self.value_head, self.net.activation)
-            return _gemm.mlp_head(x, self.net.affine_layers, self.value_head, getattr(x, "_egp_ctx_cols", None), self.net.activation)
-        if isinstance(x, _gemm.GatheredInput):
-            x = x.materialize()
-        x, n = bucket_rows(x)
-        out = self.value_head(self.net(x))
-        return out if n is None else out[:n]
+        return mlp_head(self.net, self.value_head, x)
 
 
 class Discriminator(nn.Module):
@@ -224,15 +217,7 @@ class Discriminator(nn.Module):
             self.logic.bias.zero_()
 
     def logits(self, x):
-        if _gemm.mlp_head_available(x, getattr(self.net, "affine_layers", ()), self.logic, getattr(self.net, "activation", None)):
-            if isinstance(x, _gemm.GatheredInput):
-                return _gemm.gather_mlp_head(x, self.net.affine_layers, self.logic, self.net.activation)
-            return _gemm.mlp_head(x, self.net.affine_layers, self.logic, getattr(x, "_egp_ctx_cols", None), self.net.activation)
-        if isinstance(x, _gemm.GatheredInput):
-            x = x.materialize()
-        x, n = bucket_rows(x)
-        out = self.logic(self.net(x))
-        return out if n is None else out[:n]
+        return mlp_head(self.net, self.logic, x)
 
     def forward(self, x):
         return torch.sigmoid(self.logits(x))

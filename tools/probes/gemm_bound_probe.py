@@ -1,6 +1,19 @@
-"""The update's product shapes alone, on random operands (no rollout, no indices: safe for the timing-only builds of egp_gemm.hip --
-EGP_WS_SKIP=1 consumers idle, =2 producers do not stage, EGP_FAKE_SPLIT=2 no operand split -- whose numerics are garbage).
-Inputs rotate over 3 sets so that nothing is re-read from the Infinity Cache. us per call, float32-equivalent TFLOP/s, TB/s."""
+"""The update's product shapes alone, on random operands (no rollout, no indices: safe for the timing-only builds of egp_gemm.hip,
+whose numerics are garbage). Inputs rotate over 3 sets so that nothing is re-read from the Infinity Cache. us per call,
+float32-equivalent TFLOP/s, TB/s.
+
+The timing-only builds are not in the product's source: gemm_bound_probe.patch (this folder) adds them to a COPY of egp_gemm.hip --
+-DEGP_WS_SKIP=1 consumers idle, -DEGP_WS_SKIP=3 producers issue no operand loads, -DEGP_FAKE_SPLIT=1 / 2 no split of B / of A and B.
+After `python -m egopose_amd.build` (the other objects), from the repository root, per variant:
+
+    mkdir -p build_variants && cp egopose_amd/csrc/egp_gemm.hip build_variants/egp_gemm_probe.hip
+    patch build_variants/egp_gemm_probe.hip tools/probes/gemm_bound_probe.patch
+    hipcc <FLAGS of egopose_amd/build.py> -DEGP_WS_SKIP=1 -I egopose_amd/csrc -x hip -c build_variants/egp_gemm_probe.hip -o build_variants/gemm_skip1.o
+    hipcc --offload-arch=gfx950 -shared -fPIC -pthread build_variants/gemm_skip1.o $(ls egopose_amd/csrc/_obj/*.o | grep -v egp_gemm.o) -o build_variants/libg_skip1.so
+    tools/probes/abn.sh build_variants/libg_skip1.so [...] -- python tools/probes/gemm_bound_probe.py
+
+Run such a library with this script only. (A variant whose producers do not stage ended in a memory access fault and is not in the
+patch.) Measured: profiles/r06_gemm_bound_probe.txt."""
 import os, sys
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__)))))
 import torch
