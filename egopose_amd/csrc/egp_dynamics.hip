@@ -15,8 +15,10 @@
 // child transforms are identities and a sweep level is a handful of cross products.
 // Conventions are MuJoCo's: qvel[0:3] root linear velocity (world), qvel[3:6] root angular velocity in the BODY frame,
 // MJCF coordinate="global" (all body frames axis aligned at the zero pose), armature on the hinge diagonal.
-// Parity: MuJoCo is not available to pin against; tests/test_dynamics_gpu.py checks the kernel against
-// oracle/dynamics.py (Jacobian-sum M, finite-difference Newton-Euler bias, kinetic-energy identity).
+// Parity: MuJoCo is not available to pin against; tests/test_dynamics.py checks the kernel on the humanoid against
+// oracle/dynamics.py (Jacobian-sum M, finite-difference Newton-Euler bias, kinetic-energy identity), and
+// tests/test_dynamics_reference_gpu.py on synthetic trees (tests/tree_fixture.py: general axes, full inertias, welded bodies,
+// tilted gravity, nv up to 64); tests/test_dynamics_trees.py pins the oracle itself on those trees.
 #include <hip/hip_runtime.h>
 
 #include <math.h>
@@ -95,7 +97,8 @@ int egp_dyn_trace_read(long long *out16) { return hipMemcpyFromSymbol(out16, HIP
 
 int egp_set_dynamics_model(egp_ctx *ctx, const egp_dynamics_desc *d) {
     EGP_REQUIRE(ctx && d, "NULL pointer");
-    EGP_REQUIRE(d->nbody >= 1 && d->nbody <= DY_MAXB && d->njoint >= 0 && d->njoint <= DY_MAXJ - 6, "tree too large");
+    EGP_REQUIRE(d->nbody >= 1 && d->nbody <= DY_MAXB && d->njoint >= 0 && d->njoint <= DY_MAXJ - 6,
+                "tree too large: at most 24 bodies and 58 hinges");
     EGP_REQUIRE(d->body_parent && d->body_pos && d->body_com && d->body_inertia && d->body_mass && d->body_ndof && d->joint_axis && d->joint_anchor,
                 "NULL table");
     EGP_REQUIRE(6 + d->njoint == ctx->dm.nv && d->nbody == ctx->dm.nbody, "dynamics tree does not match the context's model");

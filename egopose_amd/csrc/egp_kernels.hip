@@ -2062,12 +2062,12 @@ int egp_create(const egp_model_desc *d, int device, egp_ctx **out) {
     EGP_REQUIRE(d && out, "desc/out is NULL");
     EGP_REQUIRE(d->nv > 6 && d->nv <= EGP_MAX_NV, "nv must be in (6, 64]");
     EGP_REQUIRE(d->nq == d->nv + 1 && d->nu == d->nv - 6, "expects one free root joint + hinges (nq=nv+1, nu=nv-6)");
-    EGP_REQUIRE(d->nbody >= 2 && d->nbody + 5 <= EGP_MAX_BODY, "nbody must be in [2, 27]");
-    EGP_REQUIRE(d->nM > 0 && d->nM <= PD_NM_MAX, "nM out of range");
+    EGP_REQUIRE(d->nbody >= 2 && d->nbody + 5 <= EGP_MAX_BODY && 26 + 4 * (d->nbody - 1) <= 106 && 106 + 3 * (d->nbody - 1) <= EGP_EXPERT_ROW,
+                "nbody must be in [2, 21] (the packed expert row holds 20 non-root bodies)");
+    EGP_REQUIRE(d->nM > 0 && d->nM <= PD_NM_MAX, "nM must be in (0, 960] (the stable-PD kernels stage the sparse inertia row in LDS)");
     EGP_REQUIRE(d->body_qpos_start && d->body_ndof && d->dof_parentid && d->dof_Madr && d->ee_body, "skeleton table is NULL");
     EGP_REQUIRE(d->jkp && d->jkd && d->a_ref && d->a_scale && d->torque_lim && d->b_diffw, "gain table is NULL");
     EGP_REQUIRE(d->sub_dt > 0 && d->frame_skip > 0, "timestep/frame_skip must be positive");
-    EGP_REQUIRE(26 + 4 * (d->nbody - 1) <= 106 && 106 + 3 * (d->nbody - 1) <= EGP_EXPERT_ROW, "expert row overflow");
     EGP_HIP_CHECK(hipSetDevice(device));
     egp_ctx *ctx = new egp_ctx();
     ctx->device = device;
@@ -2153,6 +2153,11 @@ int egp_set_pd_variant(egp_ctx *ctx, int variant) {
     ctx->pd_variant = variant == 3 ? 0 : variant;
     ctx->pd_grid = variant == 0;
     return EGP_OK;
+}
+
+int egp_get_pd_variant(const egp_ctx *ctx) {
+    if (!ctx) return -1;
+    return ctx->pd_variant == 0 && !ctx->pd_grid ? 3 : ctx->pd_variant;
 }
 
 int egp_upload_experts(egp_ctx *ctx, const egp_expert_table *t) {

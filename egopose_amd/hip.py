@@ -173,6 +173,11 @@ class EgpContext:
     def set_pd_variant(self, variant: int):
         L.check(self.lib.egp_set_pd_variant(self.handle, int(variant)), "egp_set_pd_variant")
 
+    @property
+    def pd_variant(self) -> int:
+        """The stable-PD kernel `pd_torque` launches (include/egopose_hip.h: egp_set_pd_variant)."""
+        return int(self.lib.egp_get_pd_variant(self.handle))
+
     def upload_experts(self, takes):
         """takes: list of dicts with the expert keys of gen_expert.py:28-83 (float64 arrays)."""
         if not takes:

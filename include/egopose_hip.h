@@ -104,6 +104,8 @@ const char *egp_version(void);
  * binding check its own mirror of the layout before the first call */
 int64_t egp_abi_sizeof(const char *name);
 
+/* Limits of the model (anything outside is EGP_E_INVALID): one free root joint + hinges, nv in (6, 64], nM <= 960, and
+ * nbody in [2, 21] -- the packed expert row (EGP_EXPERT_ROW) holds the quaternions and angular velocities of 20 non-root bodies. */
 int egp_create(const egp_model_desc *desc, int device, egp_ctx **out);
 int egp_destroy(egp_ctx *ctx);
 /* replaces reward weights in place (cfg.reward_weights can change between iterations) */
@@ -112,6 +114,8 @@ int egp_set_reward_weights(egp_ctx *ctx, const egp_model_desc *desc);
  * one substep runs it on a 4 x 16 lane grid per env), 3 = the same with one lane per matrix row (what the resident
  * engine kernel uses), 2 = dense in-register Gauss-Jordan (any tree with nv == 58), 1 = generic LDS kernel (any nv <= 64) */
 int egp_set_pd_variant(egp_ctx *ctx, int variant);
+/* the K1 implementation the next egp_pd_torque launch runs: 0 (lane grid), 3 (one lane per row), 2 or 1; -1 for a NULL ctx */
+int egp_get_pd_variant(const egp_ctx *ctx);
 /* HumanoidEnv.load_experts (ego_pose/envs/humanoid_v1.py:47-54): packs the reward rows into HBM */
 int egp_upload_experts(egp_ctx *ctx, const egp_expert_table *tbl);
 
@@ -623,7 +627,9 @@ int egp_lstm_bwd_f32(const egp_lstm_desc *desc, void *stream);
  * (mjData.qfrc_bias) -- the mjData fields compute_torque / get_ee_pos read (ego_pose/envs/humanoid_v1.py:98-111,130-144).
  * Conventions are MuJoCo's (root angular velocity in the body frame, MJCF coordinate="global", armature on the hinge
  * diagonal). Tables are HOST arrays describing the zero pose in global coordinates; bodies parents-first, body 0 = root.
- * qM / qfrc_bias / xpos may each be NULL. MuJoCo is not available to pin against: see oracle/dynamics.py. */
+ * qM / qfrc_bias / xpos may each be NULL. MuJoCo is not available to pin against: see oracle/dynamics.py.
+ * Limits: the tree must match the context's model (so nbody <= 21, njoint = nv - 6 <= 58, see egp_create), bodies listed depth
+ * first, at most 4 children per body; 0-dof (welded) bodies, general hinge axes, full inertia tensors and any gravity are fine. */
 typedef struct egp_dynamics_desc {
     int32_t nbody, njoint;
     const int32_t *body_parent;   /* [nbody], -1 for the root */

@@ -157,13 +157,14 @@ def body_kinematics_fd(skel, qpos, qvel, h=1e-4):
     return v, a, w, wdot
 
 
-def bias_force(skel, qpos, qvel, h=1e-4):
+def bias_force(skel, qpos, qvel, h=1e-4, gravity=GRAVITY):
     """qfrc_bias = inverse dynamics at zero joint acceleration: sum_b JvT m (a_b - g) + JwT (I w' + w x I w)."""
     Jv, Jw, _, Iw = jacobians(skel, qpos)
     _, a, w, wdot = body_kinematics_fd(skel, qpos, qvel, h)
+    gravity = np.asarray(gravity, float)
     tau = np.zeros(skel.nv)
     for b in range(len(skel.body_names)):
-        f = skel.body_mass[b] * (a[b] - GRAVITY)
+        f = skel.body_mass[b] * (a[b] - gravity)
         n = Iw[b] @ wdot[b] + np.cross(w[b], Iw[b] @ w[b])
         tau += Jv[b].T @ f + Jw[b].T @ n
     return tau
@@ -190,7 +191,7 @@ def _inertia_apply(m, hvec, Ibar, s):
     return np.r_[Ibar @ w + np.cross(hvec, v), m * v + np.cross(w, hvec)]
 
 
-def crba_rne_spatial(skel, qpos, qvel):
+def crba_rne_spatial(skel, qpos, qvel, gravity=GRAVITY):
     """Composite-rigid-body M (dense) and recursive Newton-Euler bias, all spatial vectors in world coordinates about
     the world origin -- the algorithm of csrc/egp_dynamics.hip."""
     R, p, axis_w, anchor_w = fk(skel, qpos)
@@ -223,7 +224,7 @@ def crba_rne_spatial(skel, qpos, qvel):
     M[np.arange(6, nv), np.arange(6, nv)] += skel.armature
     # RNE with zero joint acceleration; gravity enters as the base acceleration -g
     vb, ab = np.zeros((nb, 6)), np.zeros((nb, 6))
-    a0 = np.r_[np.zeros(3), -GRAVITY]
+    a0 = np.r_[np.zeros(3), -np.asarray(gravity, float)]
     own = [list(range(6))]
     d = 6
     for b in range(1, nb):

@@ -66,7 +66,7 @@ def test_dynamics_kernel_matches_oracle(ctx, skel, n):
     out = ctx.dynamics(torch.as_tensor(q, device=dev), torch.as_tensor(v, device=dev), want_xpos=True)
     qM, bias, xpos = (out[k].cpu().numpy() for k in ("qM", "bias", "xpos"))
     assert qM.shape == (n, skel.nM) and bias.shape == (n, skel.nv) and xpos.shape == (n, len(skel.body_names), 3)
-    for i in range(min(n, 12)):
+    for i in range(n):                               # every env: at n = 131 the last workgroup is ragged (131 = 32 * 4 + 3)
         np.testing.assert_allclose(xpos[i], skel.body_xpos(q[i]), rtol=0, atol=1e-12)
         Ms, Cs, _ = D.crba_rne_spatial(skel, q[i], v[i])
         np.testing.assert_allclose(skel.full_from_sparse(qM[i]), Ms, rtol=0, atol=1e-10)
