@@ -11,9 +11,12 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 OBJ = os.path.join(CSRC, "_obj")
 LIB = os.path.join(HERE, "libegopose_hip.so")
-SOURCES = ["egp_kernels.hip", "egp_lstm.hip", "egp_policy.hip", "egp_gemm.hip", "egp_dynamics.hip", "egp_pose2d.hip", "egp_engine.hip", "egp_update.hip", "egp_probe.hip", "egp_tcn.hip", "egp_gail.hip",
+# (the three units that take longest to compile come first: the pool starts them in this order)
+SOURCES = ["egp_gemm.hip", "egp_pd.hip", "egp_pd_server.hip", "egp_context.hip", "egp_reward.hip", "egp_obs.hip", "egp_gae.hip",
+           "egp_lstm.hip", "egp_policy.hip", "egp_dynamics.hip", "egp_pose2d.hip", "egp_engine.hip", "egp_update.hip", "egp_probe.hip", "egp_tcn.hip", "egp_gail.hip",
            "egp_physics.cpp"]
-HEADERS = ["egp_internal.hpp", "egp_quat.hpp", "egp_filter_dev.hpp", "egp_act_dev.hpp", "egp_dynamics_dev.hpp", "egp_tree58.inc", "egp_pd_grid.hpp", os.path.join("..", "..", "include", "egopose_hip.h")]
+HEADERS = ["egp_internal.hpp", "egp_quat.hpp", "egp_filter_dev.hpp", "egp_act_dev.hpp", "egp_dynamics_dev.hpp", "egp_tree58.inc", "egp_pd_dev.hpp", "egp_pd_grid.hpp",
+           os.path.join("..", "..", "include", "egopose_hip.h")]
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-pthread", "-Wno-unused-result", "-Xarch_host", "-mavx2", "-Xarch_host", "-mfma"]
 
 
@@ -47,7 +50,8 @@ def build(force=False, verbose=False):
     todo = [s for s in SOURCES if _obj_stale(s, force)]
     if not todo and os.path.exists(LIB) and all(os.path.getmtime(_obj_of(s)) <= os.path.getmtime(LIB) for s in SOURCES):
         return LIB
-    with ThreadPoolExecutor(max_workers=max(1, min(len(todo), os.cpu_count() or 1))) as pool:
+    jobs = min(len(todo), os.cpu_count() or 1, int(os.environ.get("MAX_JOBS", 16)))
+    with ThreadPoolExecutor(max_workers=max(1, jobs)) as pool:
         list(pool.map(lambda s: _compile(s, verbose), todo))
     cmd = [_hipcc(), "--offload-arch=gfx950", "-shared", "-fPIC", "-pthread"] + [_obj_of(s) for s in SOURCES] + ["-o", LIB]
     if verbose:

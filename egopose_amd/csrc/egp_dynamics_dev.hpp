@@ -1,5 +1,5 @@
 // Device side of K8 (see egp_dynamics.hip): the per-env dynamics pass as a wave-level function, shared by the stand-alone
-// kernel k_dynamics and the resident stable-PD kernel (egp_kernels.hip: k_pd_server_tree58<true>), which runs it on the
+// kernel k_dynamics and the resident stable-PD kernel (egp_pd_server.hip: k_pd_server_tree58<true>), which runs it on the
 // state rows it has just read instead of taking qM / qfrc_bias from the host.
 #pragma once
 #include <hip/hip_runtime.h>

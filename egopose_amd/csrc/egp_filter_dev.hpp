@@ -1,4 +1,4 @@
-// Device pieces of K3 (observation) and K6 (running filter) shared by the rollout kernels (egp_kernels.hip) and the fused
+// Device pieces of K3 (observation) and K6 (running filter) shared by the rollout kernels (egp_obs.hip) and the fused
 // policy step (egp_policy.hip): one element of get_full_obs, the row source of the filter kernels, the ordered Chan merge of
 // the tile statistics, and the host-side tiling rule.
 #pragma once

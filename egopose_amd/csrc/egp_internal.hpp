@@ -1,4 +1,4 @@
-// Internal declarations shared by the kernel, physics and engine translation units.
+// Internal declarations shared by the context, kernel, physics and engine translation units.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -68,6 +68,11 @@ struct DevModel {
     int action_torque;            // cfg.action_type == 'torque': torque = clip(a_ref + action * a_scale), K1 solves nothing
 };
 
+// packed expert row (egp_upload_experts writes it, the reward kernel K2 reads it):
+//                    [0] qpos_z | [1:4] rlinv_local | [4:7] rangv | [7:11] rq_rmh | [11:26] ee_pos |
+//                    [26:26+4(nb-1)] bquat[4:] | [106:106+3(nb-1)] bangvel[3:]
+constexpr int ER_Z = 0, ER_RLINV = 1, ER_RANGV = 4, ER_RQ = 7, ER_EE = 11, ER_BQ = 26, ER_BAV = 106;
+
 }  // namespace egp
 
 struct egp_ctx {
@@ -91,7 +96,8 @@ struct egp_ctx {
     bool pose2d_set = false;
 };
 
-// launches used by the engine (same TU as the kernels)
+// launches used by the engine, defined next to their kernels: egp_pd.hip (one-launch K1), egp_pd_server.hip (resident K1),
+// egp_dynamics.hip (K8)
 int egp_launch_pd_torque_strided(egp_ctx *ctx, const double *qpos, long ld_qpos, const double *qvel, long ld_qvel,
                                  const double *bias, long ld_bias, const double *qM, long ld_qM, const double *action,
                                  int32_t n, double *torque, hipStream_t stream, unsigned *done_counter,

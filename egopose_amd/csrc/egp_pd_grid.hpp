@@ -18,8 +18,15 @@
 // table of egp_tree58.inc. The products are associated as M[i][k] * (M[k][j] / d) instead of (M[i][k] / d) * M[k][j]:
 // results agree with the row kernels to round-off, not bit for bit.
 //
-// Included by egp_kernels.hip (needs Tree58, fast_rcp, DevModel, PdLd, PdDone).
+// Launched by egp_pd.hip (launch_pd); egp_context.hip builds the kernel's gather table with grid58_offsets below.
+// Tree58, PdLd, PdDone, PD_NV and PD_NM_MAX come from egp_pd_dev.hpp.
 #pragma once
+#include <utility>
+#include <vector>
+
+#include "egp_pd_dev.hpp"
+
+namespace egp {
 
 struct Grid58 {
     static constexpr int NV = Tree58::NV;
@@ -295,3 +302,5 @@ static inline std::vector<unsigned short> grid58_offsets(const std::vector<short
             }
     return off;
 }
+
+}  // namespace egp

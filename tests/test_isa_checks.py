@@ -19,7 +19,7 @@ HIPCC = shutil.which("hipcc") or "/opt/rocm/bin/hipcc"
 @pytest.mark.skipif(not os.path.exists(HIPCC), reason="needs hipcc")
 def test_grid_kernel_listing_has_no_dpp_hazard_and_no_scratch(tmp_path):
     asm = tmp_path / "k.s"
-    src = os.path.join(ROOT, "egopose_amd", "csrc", "egp_kernels.hip")
+    src = os.path.join(ROOT, "egopose_amd", "csrc", "egp_pd.hip")
     subprocess.run([HIPCC, "--offload-arch=gfx950", "-O3", "-std=c++17", "--cuda-device-only", "-S", "-o", str(asm), src],
                    check=True, capture_output=True, timeout=600)
     for kernel in ("k_pd_torque_grid58IdE", "k_pd_torque_grid58IfE"):

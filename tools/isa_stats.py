@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
 """Instruction mix, register use and DPP hazards of one kernel in a gfx950 assembly listing.
-   hipcc --offload-arch=gfx950 -O3 -std=c++17 --cuda-device-only -S -o k.s egopose_amd/csrc/egp_kernels.hip
+   hipcc --offload-arch=gfx950 -O3 -std=c++17 --cuda-device-only -S -o k.s egopose_amd/csrc/egp_pd.hip
    python tools/isa_stats.py k.s k_pd_torque_grid58IdE
 The DPP check: a VALU write of a VGPR needs two wait states before a DPP read of it; the compiler does not look into inline
 asm, so the listing is checked instead (v_*_dpp source 0 against the destinations of the two instructions before it)."""
