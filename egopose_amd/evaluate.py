@@ -433,7 +433,8 @@ def compute_metrics(results, dt=1.0 / 30.0, algo="ego_mimic", verbose=False):
 def main(argv=None):
     """`python -m egopose_amd.evaluate --cfg subject_03 --iter 3000 --data test [--fail-safe naivefs] [--causal] [--num-envs N] [--sequential]`:
     the non-rendering part of ego_pose/ego_mimic_eval.py (checkpoint + state-net loading: :60-80) followed by the
-    statistics of ego_pose/eval_pose.py (--mode stats)."""
+    statistics of ego_pose/eval_pose.py (--mode stats). `--mode stats [--statereg-cfg S --statereg-iter M] [--joint-pos] [--keep-hands]
+    [--host]` is that script's stats mode on the saved results; `--joint-pos` adds the joint-position metrics (`egopose_amd.pose3d`)."""
     import argparse
     from .config import Config
     from .env import HumanoidEnv
@@ -451,14 +452,21 @@ def main(argv=None):
                     help="> 1: takes side by side on that many env slots (BatchedEvaluator; with --causal BatchedOnlineEvaluator)")
     ap.add_argument("--sequential", action="store_true", help="take by take (Evaluator) whatever --num-envs says")
     ap.add_argument("--test-feat", default=None, help="evaluate the feature-only takes of datasets/features/cnn_feat_<NAME>.p (no MoCap)")
-    ap.add_argument("--mode", default="eval", choices=["eval", "wild-stats"], help="wild-stats: 2D keypoint statistics of saved --test-feat results")
-    ap.add_argument("--statereg-cfg", default=None, help="wild-stats: also score the state regressor's results of this config")
+    ap.add_argument("--mode", default="eval", choices=["eval", "wild-stats", "stats"],
+                    help="wild-stats: 2D keypoint statistics of saved --test-feat results; stats: the statistics of saved --data results")
+    ap.add_argument("--statereg-cfg", default=None, help="wild-stats, stats: also score the state regressor's results of this config")
     ap.add_argument("--statereg-iter", type=int, default=100)
-    ap.add_argument("--host", action="store_true", help="wild-stats: the per-frame numpy loop instead of the GPU kernel")
+    ap.add_argument("--host", action="store_true", help="wild-stats, stats, --joint-pos: the per-frame numpy loop instead of the GPU kernel")
+    ap.add_argument("--joint-pos", action="store_true", help="eval, stats: also the joint-position metrics (MPJPE, PA-MPJPE; egopose_amd.pose3d)")
+    ap.add_argument("--keep-hands", action="store_true", help="--joint-pos: count the hands too (left out by default: noisy in some captures)")
     args = ap.parse_args(argv)
     cfg = Config(args.cfg, create_dirs=False)
     if args.mode == "wild-stats":
         return _wild_stats(cfg, args)
+    if args.mode == "stats":
+        return _stats(cfg, args)
+    if args.joint_pos and args.test_feat is not None:
+        raise SystemExit("--joint-pos needs MoCap: not with --test-feat")
     dev, dtype = torch.device("cuda", args.gpu_index), torch.float32
     env = HumanoidEnv(cfg)
     env.seed(cfg.seed)
@@ -508,7 +516,51 @@ def main(argv=None):
     path = ev.save(results, rmeta, args.iter, args.data)
     print("num reset: %d, saved results to %s" % (rmeta["num_reset"], path))
     compute_metrics(results, verbose=True)
+    if args.joint_pos:
+        _joint_pos(results, cfg, args, "ego_mimic", table=False)
     env.close()
+
+
+def _joint_pos(results, cfg, args, algo, table=True, ctx=None):
+    """The `--joint-pos` figures of `results`: the 3D line in millimetres (and the per-body table), hands out of the mask unless --keep-hands."""
+    from . import pose3d
+    from .skeleton import load_skeleton
+    skel = load_skeleton()
+    mask = pose3d.body_mask(skel, () if args.keep_hands else pose3d.HANDS)
+    out = pose3d.compute_joint_metrics(results, skel, mask=mask, backend="host" if args.host else "hip", ctx=ctx, cfg=cfg, algo=algo,
+                                       verbose=table, device_index=args.gpu_index)
+    if not table:
+        print(pose3d.format_line([out[k] for k in pose3d.FIGURES]))
+    return out
+
+
+def _stats(cfg, args):
+    """eval_pose.py --mode stats (:72-87): the three numbers of the SAVED ego_mimic result and, with --statereg-cfg, of the state
+    regressor's beside it, after remove_noisy_hands on copies; with --joint-pos also the joint-position figures of both."""
+    from .statereg import StateRegConfig
+    fs_tag = "" if args.fail_safe == "valuefs" else "_" + args.fail_safe
+    jobs = [("ego mimic", "%s/iter_%04d_%s%s%s.p" % (cfg.result_dir, args.iter, args.data, fs_tag, "_causal" if args.causal else ""))]
+    if args.statereg_cfg is not None:
+        sr_cfg = StateRegConfig(args.statereg_cfg, create_dirs=False)
+        jobs.append(("state reg", "%s/iter_%04d_%s.p" % (sr_cfg.result_dir, args.statereg_iter, args.data)))
+    ctx = None
+    if args.joint_pos and not args.host:
+        from .pose2d import context_of
+        ctx = context_of(cfg, device_index=args.gpu_index)
+    out = {}
+    try:
+        for algo, path in jobs:
+            with open(path, "rb") as f:
+                saved, _ = pickle.load(f)
+            res = {k: {take: np.array(tr, float, copy=True) for take, tr in saved[k].items()} for k in ("traj_pred", "traj_orig")}
+            metrics.remove_noisy_hands(res)
+            out[algo] = metrics.compute_metrics(res, algo=algo, verbose=True)
+            if args.joint_pos:
+                out[algo]["joint_pos"] = _joint_pos(res, cfg, args, algo, ctx=ctx)
+    finally:
+        if ctx is not None:
+            ctx.close()
+    return out
 
 
 def _wild_stats(cfg, args):

@@ -268,7 +268,9 @@ def build_parser():
     ap.add_argument("--mode", default="eval", choices=["eval", "wild-stats"], help="wild-stats: 2D keypoint statistics of saved --test-feat results")
     ap.add_argument("--test-feat", default=None, help="forecast on the feature-only takes of features/cnn_feat_<NAME>.p, from the wild ego_mimic result iter_<N>_<NAME>.p")
     ap.add_argument("--horizon", type=int, default=30)
-    ap.add_argument("--host", action="store_true", help="wild-stats: the per-frame numpy loop instead of the GPU kernel")
+    ap.add_argument("--host", action="store_true", help="wild-stats, --joint-pos: the per-frame numpy loop instead of the GPU kernel")
+    ap.add_argument("--joint-pos", action="store_true", help="eval: also the joint-position metrics at each horizon (egopose_amd.pose3d)")
+    ap.add_argument("--keep-hands", action="store_true", help="--joint-pos: count the hands too (left out by default)")
     return ap
 
 
@@ -282,9 +284,22 @@ def _wild_stats(cfg, args):
                                            pose_ctx=pose_ctx, verbose=True, device_index=args.gpu_index)
 
 
+def _joint_pos(stats, cfg, args, horizon, ctx=None):
+    """The `--joint-pos` line of one horizon: the joint-position metrics (egopose_amd.pose3d) over frames [m, m + horizon) of every window."""
+    from . import pose3d
+    from .skeleton import load_skeleton
+    skel = load_skeleton()
+    out = pose3d.compute_forecast_joint_metrics(stats, skel, cfg.fr_margin, horizon, backend="host" if args.host else "hip", ctx=ctx, cfg=cfg,
+                                                mask=pose3d.body_mask(skel, () if args.keep_hands else pose3d.HANDS),
+                                                device_index=args.gpu_index)
+    print(pose3d.format_line([out[k] for k in pose3d.FIGURES], "all - horizon: %d" % horizon))
+    return out
+
+
 def main(argv=None):
-    """`python -m egopose_amd.evaluate_forecast --cfg subject_03 --iter N --data test [--gt-init] [--num-envs 1024] [--gpu-index 0]`:
-    ego_forecast_eval.py in save mode (checkpoint loading: :57-79) followed by the statistics of eval_forecast.py (--mode stats)."""
+    """`python -m egopose_amd.evaluate_forecast --cfg subject_03 --iter N --data test [--gt-init] [--num-envs 1024] [--gpu-index 0]
+    [--joint-pos [--keep-hands] [--host]]`: ego_forecast_eval.py in save mode (checkpoint loading: :57-79) followed by the statistics
+    of eval_forecast.py (--mode stats); `--joint-pos` adds the joint-position line of each horizon."""
     import copy
     import torch
     from .config import Config as EgoMimicConfig, ForecastConfig
@@ -298,6 +313,8 @@ def main(argv=None):
         return _wild_stats(cfg, args)
     if args.gt_init and args.test_feat is not None:
         raise SystemExit("--gt-init needs MoCap: not with --test-feat")
+    if args.joint_pos and args.test_feat is not None:
+        raise SystemExit("--joint-pos needs MoCap: not with --test-feat")
     cfg.random_cur_t = False
     cfg.env_init_noise = 0.0
     dev = torch.device("cuda", args.gpu_index)
@@ -334,6 +351,8 @@ def main(argv=None):
     metrics.remove_noisy_hands(stats)
     for horizon in (30, 90):
         metrics.compute_forecast_metrics(stats, cfg.fr_margin, horizon, verbose=True)
+        if args.joint_pos:
+            _joint_pos(stats, cfg, args, horizon)
     env.close()
 
 

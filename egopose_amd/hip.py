@@ -360,6 +360,36 @@ class EgpContext:
                                         n, _stream()), "egp_pose2d_f64")
         return out
 
+    # ------------------------------------------------------------------ K10: joint-position metrics against MoCap
+    def pose3d(self, qpos_pred, qpos_gt, body_mask=None, want_err=False, want_xpos=False, out=None):
+        """qpos_pred, qpos_gt float64 [n][nq] -> dict(per_frame [n][4]: g_mpjpe, mpjpe, pa_mpjpe, root_err in metres; with want_err
+        err [n][nbody]: the root-relative distance of every body, 0 outside the mask; with want_xpos xpos_pred, xpos_gt [n][nbody][3])
+        in one launch (egp_pose3d_f64). `body_mask`: bit b = body b counts (default: all bodies; at least 3). `out`: a dict of
+        preallocated per_frame / err / xpos_pred / xpos_gt tensors to write into."""
+        if not getattr(self, "_has_dynamics", False):
+            self.set_dynamics_model()
+        n = qpos_pred.shape[0]
+        _need(qpos_pred, (n, self.nq), torch.float64, "qpos_pred")
+        _need(qpos_gt, (n, self.nq), torch.float64, "qpos_gt")
+        mask = (1 << self.nbody) - 1 if body_mask is None else int(body_mask)
+        if mask < 0 or mask >> self.nbody:
+            raise ValueError("body_mask has bits at or above nbody = %d" % self.nbody)
+        if bin(mask).count("1") < 3:
+            raise ValueError("body_mask must select at least 3 bodies")
+        out = dict(out or {})
+        shapes = dict(per_frame=(n, 4), err=(n, self.nbody), xpos_pred=(n, self.nbody, 3), xpos_gt=(n, self.nbody, 3))
+        wanted = ["per_frame"] + (["err"] if want_err else []) + (["xpos_pred", "xpos_gt"] if want_xpos else [])
+        for key in wanted:
+            if key not in out:
+                out[key] = torch.empty(shapes[key], dtype=torch.float64, device=qpos_pred.device)
+        for key, t in out.items():
+            if key not in shapes:
+                raise ValueError("out: unknown key %r" % (key,))
+            _need(t, shapes[key], torch.float64, key)
+        L.check(self.lib.egp_pose3d_f64(self.handle, _ptr(qpos_pred), _ptr(qpos_gt), mask, _ptr(out["per_frame"]), _ptr(out.get("err")),
+                                        _ptr(out.get("xpos_pred")), _ptr(out.get("xpos_gt")), n, _stream()), "egp_pose3d_f64")
+        return out
+
     def pose_features(self, cur_qpos, prev_qpos, ee_wpos, expert_convention=False):
         """-> dict(qvel, rlinv_local, rangv, rq_rmh, ee_pos, bquat, bangvel) device tensors (K7)."""
         n, dt = cur_qpos.shape[0], cur_qpos.dtype

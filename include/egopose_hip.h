@@ -661,6 +661,20 @@ int egp_pose2d_f64(egp_ctx *ctx, const double *qpos /*[n][nq]*/, const double *g
                    const int32_t *flip /*[n]*/, double *p_out /*[n][12][2], may be NULL*/, double *dist /*[n]*/,
                    int32_t *valid /*[n]*/, int64_t n, void *stream);
 
+/* ----------------------------------------------------------------------------------------
+ * K10: joint-position metrics of n predicted rows against n MoCap rows in one launch (egp_set_dynamics_model must have been
+ * called): forward kinematics of both rows (the FK phases of K8) -> body positions X, Y in metres. `body_mask` selects the bodies
+ * B that count (bit b = body b; at least 3 bits, none at or above nbody). Per frame, in per_frame[4]:
+ *   g_mpjpe  = mean_B |X_b - Y_b|                       nothing aligned
+ *   mpjpe    = mean_B |(X_b - X_0) - (Y_b - Y_0)|       root-relative; body 0 is the root whether or not its bit is set
+ *   pa_mpjpe = mean_B |s R (X_b - mx) + my - Y_b|       mx, my the centroids over B, (s, R) the least-squares similarity of X onto Y
+ *                                                       over B with R a proper rotation (a reflection is never used)
+ *   root_err = |X_0 - Y_0|
+ * err (optional): the root-relative distance of every body, 0 where the mask bit is clear; xpos_pred / xpos_gt (optional): X and Y.
+ * n == 0 returns EGP_OK; a NULL required pointer or a bad mask is EGP_E_INVALID; no dynamics model is EGP_E_STATE. */
+int egp_pose3d_f64(egp_ctx *ctx, const double *qpos_pred /*[n][nq]*/, const double *qpos_gt /*[n][nq]*/, uint32_t body_mask,
+                   double *per_frame /*[n][4]: g_mpjpe, mpjpe, pa_mpjpe, root_err*/, double *err /*[n][nbody] or NULL*/,
+                   double *xpos_pred /*[n][nbody][3] or NULL*/, double *xpos_gt /*[n][nbody][3] or NULL*/, int64_t n, void *stream);
 
 /* ----------------------------------------------------------------------------------------
  * Rollout-time policy step in one launch (replaces, for all envs of a group at once, the chain
