@@ -319,8 +319,9 @@ def test_gae_golden(ctx, dtype, tol):
 
 def test_gae_sizes_vs_oracle(ctx):
     rng = np.random.RandomState(3)
-    # chunk edges (8 samples per thread), block edges (2 048 per workgroup), the config-2 sweep size, and more than 1 024 blocks
-    # (the single-block scan of the block maps then takes several per thread)
+    # chunk edges (4 samples per thread), tile edges (2 048 per workgroup), the config-2 sweep size, and more than 1 024 tiles
+    # (k_gae_stats then merges several tile partials per thread). gamma tau = 0.9025: every look to the right ends after one tile;
+    # the longer looks are test_scan_reference_gpu.py's
     for n in (1, 2, 7, 8, 9, 31, 32, 33, 1000, 2047, 2048, 2049, 204800, 2048 * 1024 + 5):
         r = rng.uniform(0, 1.2, size=n)
         m = (rng.uniform(size=n) > 0.02).astype(float)
@@ -347,7 +348,7 @@ def test_gae_sizes_vs_oracle(ctx):
 @pytest.mark.parametrize("n", [134656, 204800])
 def test_gae_f32_at_update_batch_size_vs_oracle(ctx, n):
     """north_star: "returns/advantages within 1e-4 fp32 given identical trajectories" at the batch sizes the update really runs
-    the float32 kernel on (k_gae_replay<float>: ~134 k rows per iteration of config 2, 204 800 = the slot sweep's), against the
+    the float32 kernel on (k_gae_onepass<float>: ~134 k rows per iteration of config 2, 204 800 = the slot sweep's), against the
     oracle's reverse sweep (core/common.py:5-25) on episodes of the rollout's shape: rewards in [0, 1.2], 30-200-step episodes."""
     rng = np.random.RandomState(n)
     r = rng.uniform(0, 1.2, size=n)
