@@ -8,6 +8,7 @@
 #include <stdio.h>
 #include <string.h>
 
+#include <cmath>
 #include <vector>
 
 #include "egp_internal.hpp"
@@ -39,13 +40,16 @@ static int dev_copy(egp_ctx *ctx, const T *host, size_t count, const T **out) {
 }
 
 static int fill_reward(egp_ctx *ctx, const egp_model_desc *d) {
+    // Checked before anything is written: a refused set of weights leaves the context's previous ones in place. v_ord = inf
+    // would be the reference's max-norm (np.linalg.norm(ord=inf)); K2's pow(pow(|d|, inf), 0) is 1 instead, and NaN fails every
+    // comparison: neither may reach the kernel.
+    EGP_REQUIRE(std::isfinite(d->v_ord) && d->v_ord >= 1.0, "v_ord must be finite and >= 1 (the max-norm, v_ord = inf, is not implemented)");
+    EGP_REQUIRE(d->episode_len > 0, "episode_len must be positive");
     RewardW &w = ctx->rw;
     w.w_p = d->w_p; w.w_v = d->w_v; w.w_e = d->w_e; w.w_rp = d->w_rp; w.w_rv = d->w_rv;
     w.w_sum = d->w_p + d->w_v + d->w_e + d->w_rp + d->w_rv;
     w.k_p = d->k_p; w.k_v = d->k_v; w.k_e = d->k_e; w.k_rh = d->k_rh; w.k_rq = d->k_rq; w.k_rl = d->k_rl; w.k_ra = d->k_ra;
     w.v_ord = d->v_ord; w.decay = d->decay; w.episode_len = d->episode_len;
-    EGP_REQUIRE(d->v_ord >= 1.0, "v_ord must be >= 1");
-    EGP_REQUIRE(d->episode_len > 0, "episode_len must be positive");
     return EGP_OK;
 }
 

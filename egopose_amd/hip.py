@@ -167,8 +167,13 @@ class EgpContext:
 
     # ------------------------------------------------------------------ configuration
     def set_reward_weights(self, reward_weights):
+        before = self.reward_weights
         desc = self._desc(reward_weights)
-        L.check(self.lib.egp_set_reward_weights(self.handle, C.byref(desc)), "egp_set_reward_weights")
+        try:
+            L.check(self.lib.egp_set_reward_weights(self.handle, C.byref(desc)), "egp_set_reward_weights")
+        except Exception:
+            self.reward_weights = before          # refused (v_ord not finite or < 1): the library kept its weights, so does the binding
+            raise
 
     def set_pd_variant(self, variant: int):
         L.check(self.lib.egp_set_pd_variant(self.handle, int(variant)), "egp_set_pd_variant")

@@ -60,7 +60,9 @@ typedef struct egp_model_desc {
     int32_t episode_len;                  /* env_episode_len (200) */
     double w_p, w_v, w_e, w_rp, w_rv;     /* reward blend weights */
     double k_p, k_v, k_e, k_rh, k_rq, k_rl, k_ra;
-    double v_ord;                         /* norm order of the body-angular-velocity term (2) */
+    double v_ord;                         /* norm order of the body-angular-velocity term (2): finite and >= 1, anything else is
+                                           * EGP_E_INVALID and leaves the context's weights as they were (inf, the max-norm, is not
+                                           * implemented) */
     int32_t decay;                        /* reward *= 1 - t/episode_len */
     /* observation variants of HumanoidEnv.get_full_obs (humanoid_v1.py:73-96, defaults of egomimic_config.py:99-103 = all
      * zero here): obs = [heading angle]? ++ qpos[2:] (root quaternion de-headed unless obs_keep_root_heading)

@@ -1,6 +1,7 @@
 """Shared by the tree-kernel tests (test_dynamics_trees.py on the CPU, test_dynamics_reference_gpu.py on the GPU): free-root
 hinge trees that are generated, not shipped -- general hinge axes, full inertia tensors, arbitrary anchors and centres of
-mass, 0-, 1-, 2- and 3-dof bodies -- with their contexts, states, and a restatement of the library's host-side limits."""
+mass, 0-, 1-, 2- and 3-dof bodies -- with their contexts, states, and a restatement of the library's host-side limits.
+reward_fixture.py builds the reward and pose-feature cases of test_reward_reference_*.py on the same trees."""
 import dataclasses
 import functools
 
@@ -160,12 +161,13 @@ def gains_for(sk, seed, scale=1.0):
                 torque_lim=rng.uniform(50.0, 200.0, sk.nu), b_diffw=np.ones(len(sk.body_names) - 1))
 
 
-def context_for(sk, seed, gains=None):
-    """An EgpContext over `sk` (limits checked first); the gains it was made with are kept as `.gains`."""
+def context_for(sk, seed, gains=None, obs_options=None):
+    """An EgpContext over `sk` (limits checked first); the gains it was made with are kept as `.gains`. `obs_options`: as
+    EgpContext's (None: the shipped configs' defaults)."""
     from egopose_amd.hip import EgpContext
     check_limits(sk)
     g = gains if gains is not None else gains_for(sk, seed)
-    cx = EgpContext(sk, g["jkp"], g["jkd"], g["a_ref"], g["a_scale"], g["torque_lim"], g["b_diffw"])
+    cx = EgpContext(sk, g["jkp"], g["jkd"], g["a_ref"], g["a_scale"], g["torque_lim"], g["b_diffw"], obs_options=obs_options)
     cx.gains = g
     return cx
 
