@@ -335,6 +335,8 @@ SIGNATURES = {
     "egp_set_pose2d_bodies": (C.c_int, [vp, c_int_p, c_int_p]),
     "egp_pose2d_f64": (C.c_int, [vp, vp, vp, vp, vp, vp, vp, C.c_int64, vp]),
     "egp_pose3d_f64": (C.c_int, [vp, vp, vp, C.c_uint32, vp, vp, vp, vp, C.c_int64, vp]),
+    "egp_set_contact_points": (C.c_int, [vp, c_int_p, c_dbl_p, _i32]),
+    "egp_contact_f64": (C.c_int, [vp, vp, vp, vp, _f64, _f64, vp, vp, C.c_int64, vp]),
     "egp_mlp_pack_floats": (C.c_int64, [_i32, _i32]),
     "egp_mlp_pack_f32": (C.c_int, [vp, C.c_int64, _i32, _i32, vp, vp]),
     "egp_policy_step_f32": (C.c_int, [C.POINTER(PolicyDesc), vp]),

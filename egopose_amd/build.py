@@ -13,7 +13,7 @@ OBJ = os.path.join(CSRC, "_obj")
 LIB = os.path.join(HERE, "libegopose_hip.so")
 # (the three units that take longest to compile come first: the pool starts them in this order)
 SOURCES = ["egp_gemm.hip", "egp_pd.hip", "egp_pd_server.hip", "egp_context.hip", "egp_reward.hip", "egp_obs.hip", "egp_gae.hip",
-           "egp_lstm.hip", "egp_policy.hip", "egp_dynamics.hip", "egp_pose2d.hip", "egp_pose3d.hip", "egp_engine.hip", "egp_update.hip", "egp_probe.hip", "egp_tcn.hip", "egp_gail.hip",
+           "egp_lstm.hip", "egp_policy.hip", "egp_dynamics.hip", "egp_pose2d.hip", "egp_pose3d.hip", "egp_contact.hip", "egp_engine.hip", "egp_update.hip", "egp_probe.hip", "egp_tcn.hip", "egp_gail.hip",
            "egp_physics.cpp"]
 HEADERS = ["egp_internal.hpp", "egp_quat.hpp", "egp_filter_dev.hpp", "egp_act_dev.hpp", "egp_dynamics_dev.hpp", "egp_horn_dev.hpp", "egp_tree58.inc", "egp_pd_dev.hpp", "egp_pd_grid.hpp",
            os.path.join("..", "..", "include", "egopose_hip.h")]

@@ -94,6 +94,8 @@ struct egp_ctx {
     void *dyn_tables = nullptr;        // device copy of the dynamics tree (egp_set_dynamics_model), owned through allocs
     int pose2d_body[EGP_POSE2D_NKP] = {}, pose2d_role[6] = {};   // egp_set_pose2d_bodies: body of every keypoint row, rows with a role
     bool pose2d_set = false;
+    void *contact_tab = nullptr;       // device copy of the contact set (egp_set_contact_points), owned through allocs
+    int contact_K = 0;                 // its number of points; 0 = none set
 };
 
 // launches used by the engine, defined next to their kernels: egp_pd.hip (one-launch K1), egp_pd_server.hip (resident K1),

@@ -434,7 +434,9 @@ def main(argv=None):
     """`python -m egopose_amd.evaluate --cfg subject_03 --iter 3000 --data test [--fail-safe naivefs] [--causal] [--num-envs N] [--sequential]`:
     the non-rendering part of ego_pose/ego_mimic_eval.py (checkpoint + state-net loading: :60-80) followed by the
     statistics of ego_pose/eval_pose.py (--mode stats). `--mode stats [--statereg-cfg S --statereg-iter M] [--joint-pos] [--keep-hands]
-    [--host]` is that script's stats mode on the saved results; `--joint-pos` adds the joint-position metrics (`egopose_amd.pose3d`)."""
+    [--host]` is that script's stats mode on the saved results; `--joint-pos` adds the joint-position metrics (`egopose_amd.pose3d`);
+    `--physical [--contacts FILE] [--contact-height H] [--ground-z Z]` adds foot skate, ground penetration and floating
+    (`egopose_amd.plausibility`) in the modes eval, stats and wild-stats."""
     import argparse
     from .config import Config
     from .env import HumanoidEnv
@@ -456,9 +458,11 @@ def main(argv=None):
                     help="wild-stats: 2D keypoint statistics of saved --test-feat results; stats: the statistics of saved --data results")
     ap.add_argument("--statereg-cfg", default=None, help="wild-stats, stats: also score the state regressor's results of this config")
     ap.add_argument("--statereg-iter", type=int, default=100)
-    ap.add_argument("--host", action="store_true", help="wild-stats, stats, --joint-pos: the per-frame numpy loop instead of the GPU kernel")
+    ap.add_argument("--host", action="store_true", help="wild-stats, stats, --joint-pos, --physical: the per-frame numpy loop instead of the GPU kernel")
     ap.add_argument("--joint-pos", action="store_true", help="eval, stats: also the joint-position metrics (MPJPE, PA-MPJPE; egopose_amd.pose3d)")
     ap.add_argument("--keep-hands", action="store_true", help="--joint-pos: count the hands too (left out by default: noisy in some captures)")
+    from . import plausibility
+    plausibility.add_arguments(ap)             # --physical [--contacts FILE] [--contact-height H] [--ground-z Z]: eval, stats, wild-stats
     args = ap.parse_args(argv)
     cfg = Config(args.cfg, create_dirs=False)
     if args.mode == "wild-stats":
@@ -502,6 +506,8 @@ def main(argv=None):
         results, rmeta = ev.run()
         path = ev.save(results, rmeta, args.iter, args.test_feat)
         print("num reset: %d, saved results to %s" % (ev.num_reset, path))
+        if args.physical:
+            plausibility.from_args(results, cfg, args, "ego_mimic")
         env.close()
         return
     if cls is not Evaluator:                           # BatchedEvaluator, or BatchedOnlineEvaluator for --causal
@@ -518,6 +524,8 @@ def main(argv=None):
     compute_metrics(results, verbose=True)
     if args.joint_pos:
         _joint_pos(results, cfg, args, "ego_mimic", table=False)
+    if args.physical:
+        plausibility.from_args(results, cfg, args, "ego_mimic", which=("traj_pred", "traj_orig"))
     env.close()
 
 
@@ -544,12 +552,12 @@ def _stats(cfg, args):
         sr_cfg = StateRegConfig(args.statereg_cfg, create_dirs=False)
         jobs.append(("state reg", "%s/iter_%04d_%s.p" % (sr_cfg.result_dir, args.statereg_iter, args.data)))
     ctx = None
-    if args.joint_pos and not args.host:
+    if (args.joint_pos or args.physical) and not args.host:
         from .pose2d import context_of
         ctx = context_of(cfg, device_index=args.gpu_index)
     out = {}
     try:
-        for algo, path in jobs:
+        for i, (algo, path) in enumerate(jobs):
             with open(path, "rb") as f:
                 saved, _ = pickle.load(f)
             res = {k: {take: np.array(tr, float, copy=True) for take, tr in saved[k].items()} for k in ("traj_pred", "traj_orig")}
@@ -557,6 +565,10 @@ def _stats(cfg, args):
             out[algo] = metrics.compute_metrics(res, algo=algo, verbose=True)
             if args.joint_pos:
                 out[algo]["joint_pos"] = _joint_pos(res, cfg, args, algo, ctx=ctx)
+            if args.physical:                  # one row per algorithm, and after the last one what MoCap itself reaches
+                from . import plausibility
+                which = ("traj_pred", "traj_orig") if i == len(jobs) - 1 else ("traj_pred",)
+                out[algo]["physical"] = plausibility.from_args(res, cfg, args, algo, which=which, ctx=ctx, what=algo)
     finally:
         if ctx is not None:
             ctx.close()
@@ -578,6 +590,9 @@ def _wild_stats(cfg, args):
             res, _ = pickle.load(f)
         out[algo] = pose2d.eval_pose_wild_stats(res, meta, loader, cfg, backend="host" if args.host else "hip", pose_ctx=pose_ctx,
                                                 algo=algo, verbose=True, device_index=args.gpu_index)
+        if args.physical:                      # the only 3D figures of takes without MoCap
+            from . import plausibility
+            out[algo]["physical"] = plausibility.from_args(res, cfg, args, algo, what=algo)
     return out
 
 

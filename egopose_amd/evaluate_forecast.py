@@ -21,6 +21,10 @@ seat / history rows (`wild_window_init_state`) are here, `ForecastEvaluator(...,
 table comes from the pickle, seat and history from the wild ego_mimic result, there is no expert, no `sync_traj`, no `traj_orig` and no per-take head bound (`failed` is
 only logged against the env's `fix_head_lb`, if set) -- and `--mode wild-stats` scores the saved results with the 2D keypoint
 metric (`egopose_amd.pose2d`). `--test-feat NAME` selects this path.
+
+`--mode stats` scores the SAVED result of `--data` at `--horizon` without running anything. `--physical [--contacts FILE]
+[--contact-height H] [--ground-z Z]` adds foot skate, ground penetration and floating (`egopose_amd.plausibility`) in every mode;
+with MoCap also the `mocap` row, what MoCap itself reaches.
 """
 from __future__ import annotations
 
@@ -265,12 +269,15 @@ def build_parser():
     ap.add_argument("--gt-init", action="store_true")
     ap.add_argument("--num-envs", type=int, default=1024)
     ap.add_argument("--gpu-index", type=int, default=0)
-    ap.add_argument("--mode", default="eval", choices=["eval", "wild-stats"], help="wild-stats: 2D keypoint statistics of saved --test-feat results")
+    ap.add_argument("--mode", default="eval", choices=["eval", "wild-stats", "stats"],
+                    help="wild-stats: 2D keypoint statistics of saved --test-feat results; stats: the statistics of saved --data results at --horizon")
     ap.add_argument("--test-feat", default=None, help="forecast on the feature-only takes of features/cnn_feat_<NAME>.p, from the wild ego_mimic result iter_<N>_<NAME>.p")
     ap.add_argument("--horizon", type=int, default=30)
     ap.add_argument("--host", action="store_true", help="wild-stats, --joint-pos: the per-frame numpy loop instead of the GPU kernel")
     ap.add_argument("--joint-pos", action="store_true", help="eval: also the joint-position metrics at each horizon (egopose_amd.pose3d)")
     ap.add_argument("--keep-hands", action="store_true", help="--joint-pos: count the hands too (left out by default)")
+    from . import plausibility
+    plausibility.add_arguments(ap)                 # --physical [--contacts FILE] [--contact-height H] [--ground-z Z]: stats, wild-stats
     return ap
 
 
@@ -280,8 +287,34 @@ def _wild_stats(cfg, args):
     meta, pose_ctx, loader = pose2d.wild_stats_front(cfg, args.test_feat)
     with open("%s/iter_%04d_%s.p" % (cfg.result_dir, args.iter, args.test_feat), "rb") as f:
         res, _ = pickle.load(f)
-    return pose2d.eval_forecast_wild_stats(res, meta, loader, cfg, horizon=args.horizon, backend="host" if args.host else "hip",
-                                           pose_ctx=pose_ctx, verbose=True, device_index=args.gpu_index)
+    out = pose2d.eval_forecast_wild_stats(res, meta, loader, cfg, horizon=args.horizon, backend="host" if args.host else "hip",
+                                          pose_ctx=pose_ctx, verbose=True, device_index=args.gpu_index)
+    if args.physical:                              # the only 3D figures of takes without MoCap
+        out["physical"] = _physical(res, cfg, args, args.horizon, which=("traj_pred",))
+    return out
+
+
+def _physical(stats, cfg, args, horizon, which=("traj_pred", "traj_orig")):
+    """The `--physical` line(s) of one horizon: foot skate, ground penetration and floating (egopose_amd.plausibility) over frames
+    [m, m + horizon) of every window; with MoCap also the `mocap` row."""
+    from . import plausibility
+    return plausibility.from_args(stats, cfg, args, "ego forecast", which=which, forecast=(cfg.fr_margin, horizon),
+                                  what="all - horizon: %d" % horizon)
+
+
+def _stats(cfg, args):
+    """eval_forecast.py --mode stats on the SAVED forecast result of --data at --horizon; `--joint-pos` and `--physical` add their lines."""
+    import copy
+    with open(result_path(cfg, args.iter, args.data, args.gt_init), "rb") as f:
+        saved, _ = pickle.load(f)
+    stats = copy.deepcopy({k: saved[k] for k in ("traj_pred", "traj_orig")})
+    metrics.remove_noisy_hands(stats)
+    out = metrics.compute_forecast_metrics(stats, cfg.fr_margin, args.horizon, verbose=True)
+    if args.joint_pos:
+        out["joint_pos"] = _joint_pos(stats, cfg, args, args.horizon)
+    if args.physical:
+        out["physical"] = _physical(stats, cfg, args, args.horizon)
+    return out
 
 
 def _joint_pos(stats, cfg, args, horizon, ctx=None):
@@ -311,6 +344,8 @@ def main(argv=None):
     cfg = ForecastConfig(args.cfg, create_dirs=False)
     if args.mode == "wild-stats":
         return _wild_stats(cfg, args)
+    if args.mode == "stats":
+        return _stats(cfg, args)
     if args.gt_init and args.test_feat is not None:
         raise SystemExit("--gt-init needs MoCap: not with --test-feat")
     if args.joint_pos and args.test_feat is not None:
@@ -353,6 +388,8 @@ def main(argv=None):
         metrics.compute_forecast_metrics(stats, cfg.fr_margin, horizon, verbose=True)
         if args.joint_pos:
             _joint_pos(stats, cfg, args, horizon)
+        if args.physical:
+            _physical(stats, cfg, args, horizon)
     env.close()
 
 

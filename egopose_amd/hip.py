@@ -395,6 +395,61 @@ class EgpContext:
                                         _ptr(out.get("xpos_pred")), _ptr(out.get("xpos_gt")), n, _stream()), "egp_pose3d_f64")
         return out
 
+    # ------------------------------------------------------------------ K11: foot skate, ground penetration and floating
+    def set_contact_points(self, cs):
+        """`cs`: a plausibility.ContactSet (body int32 [K], offset float64 [K][3] in the zero pose's global axes relative to the
+        body's position, 1 <= K <= 32). A device copy stays on the context until the next call."""
+        body, off = _np_i32(cs.body), _np_f64(cs.offset)
+        K = int(body.shape[0]) if body.ndim == 1 else -1
+        if not 1 <= K <= 32 or off.shape != (K, 3):
+            raise ValueError("a contact set has 1 to 32 points: body [K] and offset [K][3]")
+        if body.min() < 0 or body.max() >= self.nbody:
+            raise ValueError("contact body out of range [0, %d)" % self.nbody)
+        if not np.isfinite(off).all():
+            raise ValueError("contact offsets must be finite")
+        L.check(self.lib.egp_set_contact_points(self.handle, _ip(body), _dp(off), K), "egp_set_contact_points")
+        self._contact_K = K
+
+    def contact(self, qpos, nxt, row=None, ground_z=0.0, contact_height=0.02, want_points=False, out=None, validate=True):
+        """qpos float64 [N][nq], nxt int64 [n] (the following row of every item, -1: none), row int64 [n] (the item's own row; None:
+        item i is row i, so n <= N) -> dict(per_frame [n][6]: pen, gap, n_contact, n_skate, skate, skate_max in metres and counts;
+        with want_points points [n][K][3]: the world contact points of the row) in one launch (egp_contact_f64). `out`: a dict of
+        preallocated per_frame / points tensors to write into. `set_contact_points` must have been called. The kernel trusts the
+        row indices, so `validate` checks them against N first (one device reduction and a sync); validate=False is for a
+        caller that has checked them itself."""
+        if not getattr(self, "_has_dynamics", False):
+            self.set_dynamics_model()
+        K = getattr(self, "_contact_K", None)
+        if K is None:
+            raise RuntimeError("set_contact_points must be called before contact")
+        N, n = qpos.shape[0], nxt.shape[0]
+        _need(qpos, (N, self.nq), torch.float64, "qpos")
+        _need(nxt, (n,), torch.int64, "nxt")
+        if row is not None:
+            _need(row, (n,), torch.int64, "row")
+        elif n > N:
+            raise ValueError("without `row` item i scores row i: n = %d items but %d rows" % (n, N))
+        if not (np.isfinite(ground_z) and np.isfinite(contact_height)):
+            raise ValueError("ground_z and contact_height must be finite")
+        if validate and n:
+            ok = ((nxt >= -1) & (nxt < N)).all()
+            if row is not None:
+                ok = ok & ((row >= 0) & (row < N)).all()
+            if not bool(ok):
+                raise ValueError("row must lie in [0, %d) and nxt in [-1, %d)" % (N, N))
+        out = dict(out or {})
+        shapes = dict(per_frame=(n, 6), points=(n, K, 3))
+        for key in ["per_frame"] + (["points"] if want_points else []):
+            if key not in out:
+                out[key] = torch.empty(shapes[key], dtype=torch.float64, device=qpos.device)
+        for key, t in out.items():
+            if key not in shapes:
+                raise ValueError("out: unknown key %r" % (key,))
+            _need(t, shapes[key], torch.float64, key)
+        L.check(self.lib.egp_contact_f64(self.handle, _ptr(qpos), _ptr(nxt), _ptr(row), float(ground_z), float(contact_height),
+                                         _ptr(out["per_frame"]), _ptr(out.get("points")), n, _stream()), "egp_contact_f64")
+        return out
+
     def pose_features(self, cur_qpos, prev_qpos, ee_wpos, expert_convention=False):
         """-> dict(qvel, rlinv_local, rangv, rq_rmh, ee_pos, bquat, bangvel) device tensors (K7)."""
         n, dt = cur_qpos.shape[0], cur_qpos.dtype

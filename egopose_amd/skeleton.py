@@ -178,6 +178,11 @@ class Skeleton:
         axis-aligned and sits at ``body_pos``; hinges of a body rotate it (and its
         subtree) about their anchor, applied in joint order x->y->z.
         """
+        return self.body_frames(qpos)[1]
+
+    def body_frames(self, qpos: np.ndarray):
+        """World frames of the bodies for one qpos -> (R (nb,3,3), p (nb,3)): a point fixed to body b at offset o (zero pose's
+        global axes, relative to ``body_pos[b]``) sits at ``p[b] + R[b] @ o``. The forward kinematics of `body_xpos`."""
         nb = len(self.body_names)
         R = [None] * nb
         p = [None] * nb
@@ -199,7 +204,7 @@ class Skeleton:
                 pb = anchor_w - Rb @ anchor_local
                 jidx += 1
             R[b], p[b] = Rb, pb
-        return np.stack(p)
+        return np.stack(R), np.stack(p)
 
     # ------------------------------------------------------------------ (de)serialisation
     def to_json(self) -> dict:

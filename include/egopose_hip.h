@@ -679,6 +679,29 @@ int egp_pose3d_f64(egp_ctx *ctx, const double *qpos_pred /*[n][nq]*/, const doub
                    double *xpos_pred /*[n][nbody][3] or NULL*/, double *xpos_gt /*[n][nbody][3] or NULL*/, int64_t n, void *stream);
 
 /* ----------------------------------------------------------------------------------------
+ * K11: physical plausibility against the ground for n items in one launch; no ground truth (egp_set_dynamics_model must have been
+ * called). A contact set is K points (1 <= K <= EGP_CONTACT_MAXK), point k fixed to body[k] at offset[k]: in the zero pose's global
+ * axes, relative to that body's position (the convention of the centres of mass); its world point is P_k = p_b + R_b offset[k].
+ * egp_set_contact_points keeps a device copy on the context; K out of range, a body index outside [0, nbody) or a non-finite
+ * offset is EGP_E_INVALID. Item i scores row `row[i]` of qpos (row i when `row` is NULL) against the following row `nxt[i]` (-1:
+ * none; points P'_k); with z measured from ground_z, per_frame[6] is
+ *   pen       = max_k max(0, -z_k)                          ground penetration, metres
+ *   gap       = max(0, min_k z_k)                           floating, metres
+ *   n_contact = #{k: z_k <= contact_height}
+ *   n_skate   = #{k: z_k <= contact_height and z'_k <= contact_height}; 0 when nxt[i] < 0
+ *   skate     = mean over those k of |(P'_k - P_k)_xy|      metres per frame step; 0 when n_skate = 0
+ *   skate_max = max over the same k                         0 when n_skate = 0
+ * points (optional): the K world points of row[i]. The caller guarantees 0 <= row[i] < N and -1 <= nxt[i] < N for the N rows
+ * of qpos: the entry does not know N. n == 0 returns EGP_OK; a NULL required pointer is EGP_E_INVALID; no dynamics model or no
+ * contact set is EGP_E_STATE. */
+#define EGP_CONTACT_MAXK 32
+int egp_set_contact_points(egp_ctx *ctx, const int32_t *body /*[K]*/, const double *offset /*[K][3]*/, int32_t K);
+int egp_contact_f64(egp_ctx *ctx, const double *qpos /*[N][nq]*/, const int64_t *nxt /*[n]*/, const int64_t *row /*[n] or NULL*/,
+                    double ground_z, double contact_height,
+                    double *per_frame /*[n][6]: pen, gap, n_contact, n_skate, skate, skate_max*/,
+                    double *points /*[n][K][3] or NULL*/, int64_t n, void *stream);
+
+/* ----------------------------------------------------------------------------------------
  * Rollout-time policy step in one launch (replaces, for all envs of a group at once, the chain
  * VideoStateNet.forward concat (models/video_state_net.py:37-43) -> MLP (models/mlp.py:5-25) ->
  * PolicyGaussian.forward / select_action (models/policy_gaussian.py:19-27, core/agent.py:38-44)):
