@@ -161,13 +161,13 @@ def gains_for(sk, seed, scale=1.0):
                 torque_lim=rng.uniform(50.0, 200.0, sk.nu), b_diffw=np.ones(len(sk.body_names) - 1))
 
 
-def context_for(sk, seed, gains=None, obs_options=None):
+def context_for(sk, seed, gains=None, obs_options=None, **kw):
     """An EgpContext over `sk` (limits checked first); the gains it was made with are kept as `.gains`. `obs_options`: as
-    EgpContext's (None: the shipped configs' defaults)."""
+    EgpContext's (None: the shipped configs' defaults); further keywords (episode_len, ...) go to EgpContext as they are."""
     from egopose_amd.hip import EgpContext
     check_limits(sk)
     g = gains if gains is not None else gains_for(sk, seed)
-    cx = EgpContext(sk, g["jkp"], g["jkd"], g["a_ref"], g["a_scale"], g["torque_lim"], g["b_diffw"], obs_options=obs_options)
+    cx = EgpContext(sk, g["jkp"], g["jkd"], g["a_ref"], g["a_scale"], g["torque_lim"], g["b_diffw"], obs_options=obs_options, **kw)
     cx.gains = g
     return cx
 
